@@ -34,6 +34,15 @@ The JSON line also carries `roofline` (algorithmic bytes of SURVEY §8d over the
 measured GPU time of the integrate pipeline, per-stage times from HIP events on
 the library's own stream, HBM traffic from the committed PMC passes) and under
 "frontend" the per-frame front end — N = 1 only.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.
+Everything else — the other chisel mode, the steady-state, first-lap and
+UpdateMap-sized legs, the parity check against the oracle and the CPU
+baselines, the voxblox configs[3] leg, the front end, the per-phase times and
+the other scaling rule of N > 1 — runs with --full (the --no-* switches turn
+single legs of such a run off), which also writes the full result to
+bench_out/bench_full.json.  --dump-outputs DIR writes what the last timed step
+left for its caller (stats, updated chunk ids, their voxels) as .npy files.
 """
 import argparse
 import ctypes
@@ -83,16 +92,52 @@ def parse():
                          "(plvs_hip_tsdf_chisel_integrate_depth_batch_dev: GeneratePointCloudInCameraFrameBGRA + InsertCloud in one "
                          "call, the default since round 5)")
     ap.add_argument("--verbose-line", action="store_true",
-                    help="print the full result (every leg with its prose) instead of the compact line; the full result is "
-                         "always written to gpurun_out/bench_full.json")
+                    help="print the full result (every leg with its prose) instead of the compact line; a --full run also "
+                         "writes the full result to bench_out/bench_full.json")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg (other chisel mode, steady state, first lap and "
+                         "UpdateMap-sized calls, parity check and CPU baselines, voxblox configs[3], front end; at N > 1 the "
+                         "per-phase times and the other scaling rule); default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left for its caller as DIR/<name>.npy "
+                         "(float32 / float64): its stats, the ids of the chunks it updated and their voxels (a fixed, seeded "
+                         f"sample of {DUMP_MAX_CHUNKS} chunks where it updated more)")
     return ap.parse_args()
 
 
+DUMP_MAX_CHUNKS = 512      # 512 chunks x 4096 voxels x 24 B: 50 MB of voxels, within the 64 MB of a dump
+
+
+def dump_outputs(tsdf, out_dir, stats, vbx):
+    """--dump-outputs: the arrays a caller of the timed path receives after its last step — last_stats(), the sorted ids of
+    the chunks (voxblox: blocks) the step updated, and those chunks' voxels as get_chunk() downloads them (every chunk, or
+    a sample of DUMP_MAX_CHUNKS drawn with a fixed seed).  Integers go out as float64 (exact), sdf / weight as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    keys = ("visits", "points", "new_chunks", "updated_chunks", "voxels", "max_run")
+    np.save(os.path.join(out_dir, "last_step_stats.npy"), np.array([stats[k] for k in keys], np.float64))
+    ids = tsdf.updated_chunk_ids()
+    ids = ids[np.lexsort(ids.T[::-1])] if len(ids) else ids.reshape(0, 3)
+    np.save(os.path.join(out_dir, "updated_chunk_ids.npy"), ids.astype(np.float64))
+    pick = np.arange(len(ids))
+    if len(ids) > DUMP_MAX_CHUNKS:
+        pick = np.sort(np.random.default_rng(0).choice(len(ids), DUMP_MAX_CHUNKS, replace=False))
+    np.save(os.path.join(out_dir, "dumped_chunk_ids.npy"), ids[pick].astype(np.float64))
+    names = ("distance", "weight", "rgba") if vbx else ("sdf", "weight", "kfid", "colour")
+    cols = [[] for _ in names]
+    for cid in ids[pick]:
+        for c, a in zip(cols, tsdf.get_chunk(*cid)):
+            c.append(a)
+    for name, c in zip(names, cols):
+        a = np.stack(c) if c else np.zeros((0, 4096))
+        np.save(os.path.join(out_dir, f"chunk_{name}.npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def compact_line(r):
-    """The one JSON line of the driver's contract, numbers only (round 5).  The full result — every leg with the prose that
-    says what it is — goes to gpurun_out/bench_full.json and is described in DESIGN.md §4.6; the driver keeps the contract
-    keys, the scalar members of `config`, `roofline` and `cpu_baseline`, and the last 2 KB of the line, so the key figures of
-    every leg are lifted into those three objects as flat scalars and repeated in `summary`, the LAST key of the line."""
+    """The one JSON line of the driver's contract, numbers only (round 5).  The full result of a --full run — every leg with
+    the prose that says what it is — goes to bench_out/bench_full.json and is described in DESIGN.md §4.6; the driver keeps
+    the contract keys, the scalar members of `config`, `roofline` and `cpu_baseline`, and the last 2 KB of the line, so the
+    key figures of every leg are lifted into those three objects as flat scalars and repeated in `summary`, the LAST key of
+    the line."""
     def g(d, *path, default=None):
         for k in path:
             if not isinstance(d, dict) or k not in d:
@@ -169,7 +214,8 @@ def compact_line(r):
     for k in ("phases_ms", "other_scaling_leg"):
         if k in r:
             out[k] = r[k]
-    out["full_result"] = "gpurun_out/bench_full.json (every leg of a default run; a run with legs switched off: bench_partial.json)"
+    if r.get("legs_present") is not None:
+        out["full_result"] = "bench_out/bench_full.json (every leg of a --full run; a run with legs switched off: bench_partial.json)"
     out["summary"] = summary
     return out
 
@@ -1337,12 +1383,15 @@ def main():
         first = (s * step_kfs) % n_poses
         if first not in built:
             sel = [kfs[(first + j) % n_poses] for j in range(step_kfs)]
-            xyz = torch.from_numpy(np.concatenate([k["xyz"] for k in sel])).cuda()
-            rgb = torch.from_numpy(np.concatenate([k["rgba" if vbx else "rgb"] for k in sel])).cuda()
-            kfid = torch.from_numpy(np.concatenate([k["kfid"] for k in sel]).astype(np.int32)).cuda()
-            Twc = torch.from_numpy(np.stack([k["Twc"] for k in sel])).cuda()
             offsets = np.cumsum([0] + [k["xyz"].shape[0] for k in sel]).astype(np.int32)
-            built[first] = (xyz, rgb, kfid, offsets, Twc)
+            if depth_input and not args.full:     # (the point streams serve only the --full legs: kept off the device)
+                built[first] = (None, None, None, offsets, None)
+            else:
+                xyz = torch.from_numpy(np.concatenate([k["xyz"] for k in sel])).cuda()
+                rgb = torch.from_numpy(np.concatenate([k["rgba" if vbx else "rgb"] for k in sel])).cuda()
+                kfid = torch.from_numpy(np.concatenate([k["kfid"] for k in sel]).astype(np.int32)).cuda()
+                Twc = torch.from_numpy(np.stack([k["Twc"] for k in sel])).cuda()
+                built[first] = (xyz, rgb, kfid, offsets, Twc)
             if depth_input:
                 built_depth[first] = pack_depth(sel)
         batches.append(built[first])
@@ -1416,6 +1465,8 @@ def main():
     else:
         stage_ms, calls = tsdf.stage_ms()
         tsdf.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(tsdf, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), st, vbx)
 
     # ---- N > 1 (ray-sharded): where a step's time goes, and the other scaling leg
     # phases_ms: three more steps run with a device synchronisation after each phase (walk / pack / exchange / apply /
@@ -1423,7 +1474,7 @@ def main():
     # other_leg: the same job under the OTHER scaling rule (weak: --batch key frames per GPU per step; strong: --batch
     # key frames per step whatever N), so one run of `bench.py --gpus N` gives both curves.
     phases_ms, other_leg = None, None
-    if vbx_sharded:
+    if vbx_sharded and args.full:
         tim = {}
         for s in range(3):
             sharded_integrate_voxblox(tsdf, *[batches[s % len(batches)][i] for i in (0, 1, 3, 4)], timings=tim)
@@ -1431,7 +1482,7 @@ def main():
         t = torch.tensor([tim.get(k, 0.0) / 3.0 for k in names], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         phases_ms = {k: round(float(v), 4) for k, v in zip(names, t.tolist())}
-    if ray_sharded:
+    if ray_sharded and args.full:
         tim = {}
         for s in range(3):
             sharded_integrate(tsdf, *[batches[s % len(batches)][i] for i in (0, 1, 2, 3, 4)], timings=tim)
@@ -1556,28 +1607,29 @@ def main():
         if other_leg is not None:
             result["other_scaling_leg"] = other_leg
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_realistic_calls(C)
+    if args.full:      # every leg beside the headline
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_realistic_calls(C)
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_steady_state(C)
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_steady_state(C)
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_other_chisel_mode(C)
-    if hasattr(C, 't2'):
-        t2 = C.t2
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_other_chisel_mode(C)
+        if hasattr(C, 't2'):
+            t2 = C.t2
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_parity_and_cpu_baseline(C)
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_parity_and_cpu_baseline(C)
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_voxblox_configs3(C)
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_voxblox_configs3(C)
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_frontend(C)
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_frontend(C)
 
-    C.__dict__.update(locals())   # (the leg reads main's locals through C)
-    leg_cpu_baseline_alone(C)
+        C.__dict__.update(locals())   # (the leg reads main's locals through C)
+        leg_cpu_baseline_alone(C)
 
     if rank == 0:
         try:      # (whatever the runtime's C libraries — RCCL's banner — still hold in stdio comes out BEFORE the line)
@@ -1585,17 +1637,19 @@ def main():
             _c.CDLL(None).fflush(None)
         except Exception:
             pass
-        full = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpurun_out")
+        full = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_out")
         try:      # every leg with its prose (what each leg is: DESIGN.md §4.6)
-            os.makedirs(full, exist_ok=True)
-            # (bench_full.json is the DEFAULT run's record — every leg; a run with legs switched off, another backend or
-            # other sizes — the profiling passes of scripts/ — writes bench_partial.json and leaves it alone)
-            whole = not (args.no_other_mode_leg or args.no_voxblox_leg or args.no_realistic_legs or args.no_steady_state_leg or
-                         args.no_frontend or args.no_cpu_baseline or args.no_parity_check or args.steady_state or args.ordered or
-                         args.cloud_input or args.sharded_at_one or args.backend != "chisel" or world != 1 or args.batch != 100)
-            result["legs_present"] = sorted(k for k in result if isinstance(result[k], dict) and k not in ("config", "roofline"))
-            with open(os.path.join(full, "bench_full.json" if whole else "bench_partial.json"), "w") as f:
-                json.dump(result, f, indent=1)
+            if args.full:
+                os.makedirs(full, exist_ok=True)
+                # (bench_full.json is the record of a --full run with the default sizes — every leg; a run with legs switched
+                # off, another backend or other sizes — the profiling passes of scripts/ — writes bench_partial.json and
+                # leaves it alone)
+                whole = not (args.no_other_mode_leg or args.no_voxblox_leg or args.no_realistic_legs or args.no_steady_state_leg or
+                             args.no_frontend or args.no_cpu_baseline or args.no_parity_check or args.steady_state or args.ordered or
+                             args.cloud_input or args.sharded_at_one or args.backend != "chisel" or world != 1 or args.batch != 100)
+                result["legs_present"] = sorted(k for k in result if isinstance(result[k], dict) and k not in ("config", "roofline"))
+                with open(os.path.join(full, "bench_full.json" if whole else "bench_partial.json"), "w") as f:
+                    json.dump(result, f, indent=1)
         except OSError:
             pass
         sys.stdout.flush()

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG="${1:-r04}"; O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 R=$PWD
-COMMON="--steps 20 --warmup 5 --no-frontend --no-cpu-baseline --no-realistic-legs"
+COMMON="--full --steps 20 --warmup 5 --no-frontend --no-cpu-baseline --no-realistic-legs"
 ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o r -- python $R/bench.py $COMMON 2>&1 | tail -2 ) > $O/rocprof.log 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $R/$O/pmc_$C -o r -- python $R/bench.py --steps 4 --warmup 2 --no-frontend --no-cpu-baseline --no-other-mode-leg --no-voxblox-leg --no-realistic-legs --no-steady-state-leg 2>&1 | tail -2 ) > $O/pmc_$C.log 2>&1

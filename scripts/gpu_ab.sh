@@ -5,7 +5,7 @@ TAG="$1"; VARIANTS="$2"; shift 2
 O="gpurun_out/$TAG"; mkdir -p "$O"
 for V in $VARIANTS; do
   if [ "$V" = "-" ]; then unset PLVS_HIP_LIB; N=product; else export PLVS_HIP_LIB="$PWD/plvs_amd/lib/libplvs_hip_$V.so"; N=$V; fi
-  ( timeout 300 python bench.py --no-frontend --no-cpu-baseline --no-other-mode-leg --no-voxblox-leg "$@" 2>&1 | tail -3 ) > "$O/bench_$N.log" 2>&1
+  ( timeout 300 python bench.py --full --no-frontend --no-cpu-baseline --no-other-mode-leg --no-voxblox-leg "$@" 2>&1 | tail -3 ) > "$O/bench_$N.log" 2>&1
 done
 unset PLVS_HIP_LIB
 python - "$O" <<'PY'

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG="$1"; VAR="$2"; VALUES="$3"; shift 3
 O="gpurun_out/$TAG"; mkdir -p "$O"
 for V in $VALUES; do
-  ( export $VAR=$V; timeout 300 python bench.py --no-frontend --no-cpu-baseline --no-other-mode-leg --no-voxblox-leg "$@" 2>&1 | tail -3 ) > "$O/bench_${VAR}_$V.log" 2>&1
+  ( export $VAR=$V; timeout 300 python bench.py --full --no-frontend --no-cpu-baseline --no-other-mode-leg --no-voxblox-leg "$@" 2>&1 | tail -3 ) > "$O/bench_${VAR}_$V.log" 2>&1
 done
 python - "$O" <<'PY'
 import json, sys, glob, os

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG="$1"; VAR="$2"; VALUES="$3"
 O="gpurun_out/$TAG"; mkdir -p "$O"
 for V in $VALUES; do
-  ( export $VAR=$V; timeout 300 python bench.py --no-frontend --no-cpu-baseline --no-realistic-legs --no-parity-check --steps 20 --warmup 5 2>&1 | grep "^{" | tail -1 ) > "$O/bench_${VAR}_$V.json" 2>&1
+  ( export $VAR=$V; timeout 300 python bench.py --full --no-frontend --no-cpu-baseline --no-realistic-legs --no-parity-check --steps 20 --warmup 5 2>&1 | grep "^{" | tail -1 ) > "$O/bench_${VAR}_$V.json" 2>&1
 done
 python - "$O" <<'PY'
 import json, sys, glob, os

@@ -1,4 +1,5 @@
-"""Binary PGM (P5, 8-bit) reader for the grey test frames under tests/golden/."""
+"""Binary PGM (P5, 8-bit) reader for the grey test frames under tests/golden/ (plain, or xz-compressed: *.pgm.xz)."""
+import lzma
 import os
 
 import numpy as np
@@ -9,6 +10,8 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def read_pgm(path):
     with open(path, "rb") as f:
         data = f.read()
+    if path.endswith(".xz"):
+        data = lzma.decompress(data)
     parts = data.split(None, 4)
     if parts[0] != b"P5" or int(parts[3]) != 255:
         raise ValueError(f"{path}: not an 8-bit binary PGM")

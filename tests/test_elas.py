@@ -155,14 +155,13 @@ def test_oracle_descriptor_equals_the_reference_source(oracle, half, size):
         assert np.array_equal(oracle.elas_descriptor(right, half), calls[0]["I2_desc"])
 
 
-TREE_INPUT = "/root/reference/Thirdparty/libelas-gpu/input"
+TREE_INPUT = os.path.join(GOLDEN, "libelas")      # the reference tree's input/*.pgm, xz-compressed
 
 
 @needs_ref
-@pytest.mark.skipif(not os.path.isdir(TREE_INPUT), reason="the reference tree's other stereo pairs are not committed (1 MB images)")
 @pytest.mark.parametrize("name,subsampling", [("cones", False), ("cones", True), ("aloe", True), ("urban3", False)])
 def test_every_oracle_stage_on_the_trees_other_pairs(oracle, name, subsampling):
-    """Dev-container test: the reference tree's own input pairs beyond urban1 (cones 900 x 750, aloe 1282 x 1110,
+    """The reference tree's own input pairs beyond urban1 (tests/golden/libelas/; cones 900 x 750, aloe 1282 x 1110,
     urban3 1344 x 391 — other textures, disparity ranges up to the 255 limit, widths that are not multiples of 16).  The
     descriptors against libelas::Descriptor; then the pipeline with the oracle's candidate grid, computeDisparity,
     left/right check, speckle removal, gap interpolation and adaptive mean in place of the reference's methods: the very
@@ -170,7 +169,8 @@ def test_every_oracle_stage_on_the_trees_other_pairs(oracle, name, subsampling):
     import ctypes
 
     def pgm(path):       # (binary P5 with comment lines, which GIMP writes into some of the tree's files)
-        data = open(path, "rb").read()
+        import lzma
+        data = lzma.decompress(open(path, "rb").read())
         tokens, pos = [], 0
         while len(tokens) < 4:
             while data[pos:pos + 1].isspace():
@@ -186,7 +186,7 @@ def test_every_oracle_stage_on_the_trees_other_pairs(oracle, name, subsampling):
         assert tokens[0] == b"P5" and int(tokens[3]) == 255
         w_, h_ = int(tokens[1]), int(tokens[2])
         return np.frombuffer(data, np.uint8, w_ * h_, pos + 1).reshape(h_, w_).copy()
-    left, right = pgm(f"{TREE_INPUT}/{name}_left.pgm"), pgm(f"{TREE_INPUT}/{name}_right.pgm")
+    left, right = pgm(f"{TREE_INPUT}/{name}_left.pgm.xz"), pgm(f"{TREE_INPUT}/{name}_right.pgm.xz")
     lib = ctypes.CDLL(elas_ref.REF)
     lib.ref_elas_descriptor.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     h, w = left.shape
