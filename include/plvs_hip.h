@@ -854,9 +854,10 @@ int plvs_hip_tsdf_chisel_halo_clear(plvs_tsdf_chisel* h);
  * libelas::ElasInterface::process -> Elas::process, elas.cpp:36-159) — and, beyond that build, the other stages a pair
  * goes through (entry points further down): the descriptor images (plvs_hip_elas_set_images), the candidate loop of
  * computeSupportMatches (_support_candidates), leftRightConsistencyCheck (_left_right_check), removeSmallSegments
- * (_remove_small_segments) and gapInterpolation (_gap_interpolation).  The support filters, the Delaunay triangulation,
- * the planes and the grid stay the caller's host code.  All pointers are HOST pointers (the reference's call sites hand
- * over host memory); results are bit-identical to the CPU methods — of a reference whose uninitialised reads see zeros
+ * (_remove_small_segments) and gapInterpolation (_gap_interpolation), the support filters (_support_points), the
+ * Delaunay triangulation (_triangulate, host code), the planes (_disparity_planes) and the grid (_create_grid), and all of
+ * Elas::process in one call (_process).  All pointers are HOST pointers (the reference's call sites hand over host
+ * memory); results are bit-identical to the CPU methods — of a reference whose uninitialised reads see zeros
  * (oracle/ref/elas_zero_malloc.h: its sources read allocated memory they never wrote; parity is pinned through that
  * hook).  Preconditions the post-processing stages share with the reference: invalid pixels hold -10;
  * speckle_sim_threshold < 10.
@@ -933,6 +934,42 @@ int plvs_hip_elas_postprocess(plvs_elas* e, int width, int height, int postproce
  * into d_depth (DEVICE, width x height floats: what plvs_hip_cloudgen_generate_dev reads): bf / d, with subsampling only
  * at rows step * m1 and pixels step * n1, step * n1 + 1 (zero elsewhere); step = PointCloudMapping::skDownsampleStep. */
 int plvs_hip_elas_depth_dev(plvs_elas* e, float bf, int step, float* d_depth, int width, int height, void* stream);
+/* Elas::computeDelaunayTriangulation (elas.cpp:492-556): the Delaunay triangulation of the support points as the
+ * reference's Triangle computes it (triangulate("zQB"), Thirdparty/libelas-gpu/CPU/triangle.cpp) — the same triangles,
+ * in the same order, each with its corners in the same order (computeDisparity rasterises them in that order, and on
+ * the 5-px support grid the triangulation is not unique).  Host code: no handle, no device; callable without a GPU.
+ * support: n_support x {u, v, d}; the vertices are (u, v), or (u - d, v) with right_image.  Of equal vertices the one
+ * the reference keeps is used (its input index).  tri: room for cap 36-byte records {c1, c2, c3, t1a .. t2c}; the
+ * corners are filled, the planes are 0.  *n_tri: the number of triangles (0 when all points are collinear), also when
+ * it exceeds cap (PLVS_ERR_CAPACITY).  Fewer than 3 points: PLVS_ERR_EMPTY (the reference's triangulate exits there;
+ * Elas::process never calls it with fewer).  Coordinates must stay below 2^24 in magnitude. */
+int plvs_hip_elas_triangulate(const int32_t* support, int n_support, int right_image, void* tri, int cap, int* n_tri);
+/* Elas::process (elas.cpp:36-157) in ONE call on the handle's stream: descriptors, candidates, the support filters and
+ * list (+ corners with add_corners) on the device, one download of the list, the two triangulations on two host threads
+ * while the device builds both grids, one upload of the triangles, the planes, computeDisparity x 2 and the
+ * post-processing chain of plvs_hip_elas_postprocess.  dims: {width, height, bytes per line}.  D1 / D2: host destinations
+ * (width x height, half of it with subsampling), either may be NULL; the maps stay in HBM (plvs_hip_elas_depth_dev).
+ * Fewer than 3 support points: PLVS_ERR_EMPTY, D1 / D2 untouched (the reference prints and returns).  The MIDDLEBURY
+ * median filter is not built.  Bit-identical to the reference's Elas::process. */
+int plvs_hip_elas_process(plvs_elas* e, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int postprocess_only_left,
+                          int filter_adaptive_mean, float* D1, float* D2);
+/* computeSupportMatches after its candidate loop (elas.cpp:459-486) on the device: removeInconsistentSupportPoints (window 5,
+ * threshold 5, minimum support 5: Elas' incon_* in both settings), removeRedundantSupportPoints vertical then horizontal
+ * (5, 1), each the reference's in-place scan, the list in its column-major order and, with add_corners,
+ * addCornerSupportPoints.  D_can: the candidate grid (ceil(width / step) x ceil(height / step) int16), NULL = the one the
+ * last plvs_hip_elas_support_candidates left in HBM.  support: n x {u, v, d}; more than cap: PLVS_ERR_CAPACITY with
+ * *n_support = the size needed. */
+int plvs_hip_elas_support_points(plvs_elas* e, const int16_t* D_can, int width, int height, int32_t* support, int cap,
+                                 int* n_support);
+/* computeDisparityPlanes (elas.cpp:561-633) on the device: both planes of every triangle (t1* from (u, v, 1), t2* from
+ * (u - d, v, 1)), Matrix::solve's Gauss-Jordan in fp64 (matrix.cpp:416-500), zeros for a singular system; tri in place. */
+int plvs_hip_elas_disparity_planes(plvs_elas* e, const int32_t* support, int n_support, void* tri, int n_tri);
+/* createGrid (elas.cpp:635-715) on the device: grid_dims = {disp_max + 2, ceil(width / grid_size), ceil(height /
+ * grid_size)} of the IMAGE size; disparity_grid: grid_dims[0] * [1] * [2] ints, every cell its count, its disparities
+ * ascending, zeros.  The 3 x 3 dilation walks the flat array as the reference does.  A grid of fewer than
+ * 2 * grid_width + 2 cells: PLVS_ERR_INVALID_ARG (the reference's walk has no end there). */
+int plvs_hip_elas_create_grid(plvs_elas* e, const int32_t* support, int n_support, int width, int height, int right_image,
+                              int32_t* disparity_grid, int32_t* grid_dims);
 
 /* ------------------------------------------------- dense stereo (semi-global matching)
  * Replaces sgm::StereoSGM as PointCloudKeyFrame::ProcessStereoLibsgm uses it

@@ -427,6 +427,27 @@ class ElasGPU {
   void leftRightConsistencyCheck(float* D1, float* D2) { check(plvs_hip_elas_left_right_check(h_, D1, D2, width, height)); }
   void removeSmallSegments(float* D) { check(plvs_hip_elas_remove_small_segments(h_, D, width, height)); }
   void gapInterpolation(float* D) { check(plvs_hip_elas_gap_interpolation(h_, D, width, height)); }
+  // Elas::computeDelaunayTriangulation (elas.cpp:492-556): the reference's triangles in its order, planes 0.  Host code.
+  static std::vector<triangle> computeDelaunayTriangulation(const std::vector<support_pt>& p_support, int32_t right_image) {
+    std::vector<triangle> tri(2 * p_support.size() + 2);
+    int n = 0;
+    check(plvs_hip_elas_triangulate(reinterpret_cast<const int32_t*>(p_support.data()), (int)p_support.size(), right_image,
+                                    tri.data(), (int)tri.size(), &n));
+    tri.resize(n);
+    return tri;
+  }
+  // Elas::process (elas.cpp:36-157) with its signature, in one call: a replacement of ElasInterface::process is one line.
+  // postprocess_only_left / filter_adaptive_mean as Elas::Parameters holds them (PLVS: both true).
+  bool postprocess_only_left = true, filter_adaptive_mean = true;
+  void process(uint8_t* I1, uint8_t* I2, float* D1, float* D2, const int32_t* dims) {
+    width = dims[0];
+    height = dims[1];
+    check(plvs_hip_elas_process(h_, I1, I2, dims, postprocess_only_left ? 1 : 0, filter_adaptive_mean ? 1 : 0, D1, D2));
+    staged_1_ = staged_2_ = nullptr;
+    staged_w_ = width;
+    staged_h_ = height;
+    staged_by_support_ = false;
+  }
   // libelas::Descriptor of both images on the device; supportCandidates / computeDisparity then take nullptr descriptors
   void setImages(const uint8_t* I1, const uint8_t* I2, int32_t stride) {
     check(plvs_hip_elas_set_images(h_, I1, I2, width, height, stride));

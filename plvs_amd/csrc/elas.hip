@@ -4,9 +4,9 @@
 // the other virtual stages between the descriptors and the result: the candidate loop of computeSupportMatches (:434-456
 // with computeMatchingDisparity :296-410), leftRightConsistencyCheck (:971-1040), removeSmallSegments (:1043-1160),
 // gapInterpolation (:1163-1347).  All reached from PointCloudKeyFrame::ProcessStereoLibelas (src/PointCloudKeyFrame.cc:335-432)
-// through libelas::ElasInterface::process -> Elas::process (elas.cpp:36-159).  Descriptors, the support filters, the Delaunay
-// triangulation, planes and grid stay the caller's host code.  Every entry point takes the host pointers of the method it
-// replaces and returns results bit-identical to it.
+// through libelas::ElasInterface::process -> Elas::process (elas.cpp:36-159).  The Delaunay triangulation of the support
+// points is host code here (plvs_hip_elas_triangulate, elas_delaunay.hpp); the support filters, planes and grid stay the
+// caller's.  Every entry point takes the host pointers of the method it replaces and returns results bit-identical to it.
 //
 // computeDisparity rasterises the triangles one after the other and lets later ones overwrite earlier ones on shared
 // pixels; whether a pixel is written at all depends on the pixel alone (its column and texture), the value on the plane
@@ -17,9 +17,11 @@
 // a fixed window per output pixel: a thread per pixel, the window's values summed in the order the reference's
 // four-lane registers impose (slot = pixel index mod 4 / 8).  The other stages are described at their kernels.
 #include <cmath>
+#include <thread>
 #include <vector>
 
 #include "common.hpp"
+#include "elas_delaunay.hpp"
 
 namespace {
 
@@ -579,6 +581,14 @@ struct plvs_elas {
   // the maps of the last computeDisparity calls, kept in HBM for plvs_hip_elas_postprocess ([0] left, [1] right)
   plvs::DevBuf<float> res[2];
   int res_w[2] = {0, 0}, res_h[2] = {0, 0};
+  // the host stages on the device: filter scratch, the support list and its count, both triangle lists and grids
+  plvs::DevBuf<int16_t> can_a, can_b;
+  plvs::DevBuf<Support> sp;
+  plvs::DevBuf<int32_t> sp_n;
+  plvs::DevBuf<Triangle> ptri[2];
+  plvs::DevBuf<int32_t> pgrid[2];
+  plvs::DevBuf<uint8_t> gmark[2];
+  int can_w = 0, can_h = 0, can_step = 0, can_width = 0, can_height = 0;   // the candidate grid in D_can (0: none)
 };
 
 namespace {
@@ -670,6 +680,392 @@ __global__ __launch_bounds__(256) void depth_from_disparity(const float* __restr
   }
   depth[(size_t)v * W + u] = out;
 }
+// ---- the host stages of Elas::process on the device: support filters and list, planes, grid
+// removeInconsistentSupportPoints / removeRedundantSupportPoints (elas.cpp:162-257) are in-place scans, u_can outer and
+// v_can inner: a point sees its earlier neighbours filtered and its later ones as they were.  One workgroup iterates
+// x[p] = f(x of earlier points, original of later points) over all points until an iteration changes nothing: a point
+// depends only on earlier ones, so the fixed point is unique and is the sequential result.
+constexpr int kInconRadius = 5, kInconThreshold = 5, kInconMinSupport = 5;   // Elas::Parameters incon_* (both settings)
+constexpr int kRedunDist = 5, kRedunThreshold = 1;                           // elas.cpp:465-466
+constexpr int kFilterThreads = 1024;
+
+__device__ __forceinline__ int16_t filter_value(int pass, const int16_t* orig, const int16_t* x, int u, int v, int cw, int ch) {
+  const int d = orig[v * cw + u];
+  if (d < 0) return (int16_t)d;
+  auto at = [&](int u2, int v2) -> int { return (u2 < u || (u2 == u && v2 < v)) ? x[v2 * cw + u2] : orig[v2 * cw + u2]; };
+  if (pass == 0) {
+    int support = 0;
+    for (int u2 = u - kInconRadius; u2 <= u + kInconRadius; ++u2)
+      for (int v2 = v - kInconRadius; v2 <= v + kInconRadius; ++v2)
+        if (u2 >= 0 && v2 >= 0 && u2 < cw && v2 < ch) {
+          const int d2 = at(u2, v2);
+          if (d2 >= 0 && abs(d - d2) <= kInconThreshold) ++support;
+        }
+    return support < kInconMinSupport ? (int16_t)-1 : (int16_t)d;
+  }
+  const int du = pass == 2 ? 1 : 0, dv = pass == 1 ? 1 : 0;   // pass 1: vertical, pass 2: horizontal
+  for (int side = -1; side <= 1; side += 2) {
+    bool support = false;
+    for (int j = 1; j <= kRedunDist; ++j) {
+      const int u2 = u + side * du * j, v2 = v + side * dv * j;
+      if (u2 < 0 || v2 < 0 || u2 >= cw || v2 >= ch) break;
+      const int d2 = at(u2, v2);
+      if (d2 >= 0 && abs(d - d2) <= kRedunThreshold) {
+        support = true;
+        break;
+      }
+    }
+    if (!support) return (int16_t)d;
+  }
+  return (int16_t)-1;
+}
+
+struct SupportListParams {
+  int cw, ch, step, width, height, add_corners;
+};
+
+// The three filters in place on `can`, then the list (column-major over u_can, v_can >= 1, elas.cpp:470-475) and, with
+// add_corners, addCornerSupportPoints (:260-294).  out: room for (cw - 1) * (ch - 1) + 6 points; *n_out: the count.
+__global__ __launch_bounds__(kFilterThreads) void elas_support_points(SupportListParams P, int16_t* __restrict__ can,
+                                                                      int16_t* __restrict__ xa, int16_t* __restrict__ xb,
+                                                                      Support* __restrict__ out, int32_t* __restrict__ n_out) {
+  __shared__ int changed;
+  __shared__ int wave_sums[kFilterThreads / 64];
+  __shared__ unsigned long long best[4];
+  const int tid = threadIdx.x, n = P.cw * P.ch;
+  for (int pass = 0; pass < 3; ++pass) {
+    for (int i = tid; i < n; i += kFilterThreads) xa[i] = can[i];
+    int16_t* x = xa;
+    int16_t* y = xb;
+    for (;;) {
+      if (tid == 0) changed = 0;
+      __threadfence();
+      __syncthreads();
+      int mine = 0;
+      for (int i = tid; i < n; i += kFilterThreads) {
+        const int16_t nv = filter_value(pass, can, x, i % P.cw, i / P.cw, P.cw, P.ch);
+        mine |= nv != x[i];
+        y[i] = nv;
+      }
+      if (mine) atomicOr(&changed, 1);
+      __threadfence();
+      __syncthreads();
+      int16_t* t = x;
+      x = y;
+      y = t;
+      const int again = changed;
+      __syncthreads();
+      if (!again) break;
+    }
+    for (int i = tid; i < n; i += kFilterThreads) can[i] = x[i];
+    __threadfence();
+    __syncthreads();
+  }
+  // the list: a block-wide exclusive scan per chunk of 1024 points in list order
+  const int rows = P.ch - 1, total = (P.cw - 1) * rows, lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int c0 = 0; c0 < total; c0 += kFilterThreads) {
+    const int k = c0 + tid;
+    int u = 0, v = 0, d = -1;
+    if (k < total) {
+      u = 1 + k / rows;
+      v = 1 + k % rows;
+      d = can[v * P.cw + u];
+    }
+    const bool valid = d >= 0;
+    const unsigned long long mask = __ballot(valid);
+    if (lane == 0) wave_sums[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, chunk = 0;
+    for (int w = 0; w < kFilterThreads / 64; ++w) {
+      before += w < wave ? wave_sums[w] : 0;
+      chunk += wave_sums[w];
+    }
+    if (valid) {
+      const int at = base + before + __popcll(mask & ((1ull << lane) - 1ull));
+      out[at] = Support{u * P.step, v * P.step, d};
+    }
+    base += chunk;
+    __syncthreads();
+  }
+  int count = base;
+  if (P.add_corners) {
+    // nearest support point by squared pixel distance, the first of equals (`<`), best_dist starting at 10^7
+    __threadfence();
+    if (tid < 4) best[tid] = ~0ull;
+    __syncthreads();
+    const int cu[4] = {0, 0, P.width - 1, P.width - 1}, cv[4] = {0, P.height - 1, 0, P.height - 1};
+    for (int j = tid; j < count; j += kFilterThreads) {
+      const Support s = out[j];
+      for (int c = 0; c < 4; ++c) {
+        const int du = cu[c] - s.u, dv = cv[c] - s.v, dist = du * du + dv * dv;
+        if (dist < 10000000) atomicMin(&best[c], ((unsigned long long)(unsigned)dist << 32) | (unsigned)j);
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int cd[4];
+      for (int c = 0; c < 4; ++c) cd[c] = best[c] == ~0ull ? 0 : out[(int)(best[c] & 0xffffffffu)].d;
+      for (int c = 0; c < 4; ++c) out[count + c] = Support{cu[c], cv[c], cd[c]};
+      out[count + 4] = Support{cu[2] + cd[2], cv[2], cd[2]};
+      out[count + 5] = Support{cu[3] + cd[3], cv[3], cd[3]};
+    }
+    count += 6;
+  }
+  if (tid == 0) *n_out = count;
+}
+
+// computeDisparityPlanes (elas.cpp:561-633): Matrix::solve (matrix.cpp:416-500) — Gauss-Jordan with a full pivot search
+// (the last maximum wins, `>=`), eps = 1e-20 — in fp64, no contraction; a singular system leaves zeros.
+__device__ bool gauss_jordan3(double a[3][3], double b[3]) {
+  int ipiv[3] = {0, 0, 0};
+  for (int i = 0; i < 3; ++i) {
+    double big = 0.0;
+    int irow = 0, icol = 0;
+    for (int j = 0; j < 3; ++j)
+      if (ipiv[j] != 1)
+        for (int k = 0; k < 3; ++k)
+          if (ipiv[k] == 0 && fabs(a[j][k]) >= big) {
+            big = fabs(a[j][k]);
+            irow = j;
+            icol = k;
+          }
+    ++ipiv[icol];
+    if (irow != icol) {
+      for (int l = 0; l < 3; ++l) {
+        const double t = a[irow][l];
+        a[irow][l] = a[icol][l];
+        a[icol][l] = t;
+      }
+      const double t = b[irow];
+      b[irow] = b[icol];
+      b[icol] = t;
+    }
+    if (fabs(a[icol][icol]) < 1e-20) return false;
+    const double pivinv = 1.0 / a[icol][icol];
+    a[icol][icol] = 1.0;
+    for (int l = 0; l < 3; ++l) a[icol][l] *= pivinv;
+    b[icol] *= pivinv;
+    for (int ll = 0; ll < 3; ++ll)
+      if (ll != icol) {
+        const double dum = a[ll][icol];
+        a[ll][icol] = 0.0;
+        for (int l = 0; l < 3; ++l) a[ll][l] -= a[icol][l] * dum;
+        b[ll] -= b[icol] * dum;
+      }
+  }
+  return true;   // (the column unscrambling of Matrix::solve touches A only)
+}
+
+__global__ __launch_bounds__(256) void elas_planes(const Support* __restrict__ sp, Triangle* __restrict__ tri, int n_tri) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_tri) return;
+  Triangle t = tri[i];
+  const Support c[3] = {sp[t.c1], sp[t.c2], sp[t.c3]};
+  float out[6];
+  for (int side = 0; side < 2; ++side) {
+    double a[3][3], b[3];
+    for (int r = 0; r < 3; ++r) {
+      a[r][0] = (double)(side ? c[r].u - c[r].d : c[r].u);
+      a[r][1] = (double)c[r].v;
+      a[r][2] = 1.0;
+      b[r] = (double)c[r].d;
+    }
+    const bool ok = gauss_jordan3(a, b);
+    for (int r = 0; r < 3; ++r) out[3 * side + r] = ok ? (float)b[r] : 0.0f;
+  }
+  t.t1a = out[0]; t.t1b = out[1]; t.t1c = out[2];
+  t.t2a = out[3]; t.t2b = out[4]; t.t2c = out[5];
+  tri[i] = t;
+}
+
+// createGrid (elas.cpp:635-715): temp1 marks (x, y, d) for d in [d - 1, d + 1] of every support point; temp2 is the
+// 3 x 3 dilation as the reference walks it — over the FLAT array, wrapping across row ends, written from cell
+// (1, 1) on for gw * gh - 2 gw - 2 cells' worth of entries, zero elsewhere; then per cell the count and the disparities.
+__global__ __launch_bounds__(256) void elas_grid_mark(const Support* __restrict__ sp, int n, int right_image, int grid_size,
+                                                      int disp_max, int gw, int gh, uint8_t* __restrict__ temp1) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Support s = sp[i];
+  const int d_min = max(s.d - 1, 0), d_max = min(s.d + 1, disp_max);
+  for (int d = d_min; d <= d_max; ++d) {
+    const int x = right_image ? (int)floorf((float)(s.u - s.d) / (float)grid_size) : (int)floorf((float)(s.u / grid_size));
+    const int y = (int)floorf((float)s.v / (float)grid_size);
+    if (x >= 0 && x < gw && y >= 0 && y < gh) temp1[((size_t)y * gw + x) * (disp_max + 1) + d] = 1;
+  }
+}
+
+// a wave per cell: lane l looks at disparities l, l + 64, ...; the ballot compacts them in ascending order (in LDS, then
+// every entry of the cell is written: count, disparities, zeros)
+__global__ __launch_bounds__(64) void elas_grid_cells(const uint8_t* __restrict__ temp1, int disp_max, int gw, int gh,
+                                                      int32_t* __restrict__ grid) {
+  extern __shared__ int32_t list[];   // disp_max + 1 entries
+  const int cell = blockIdx.x, lane = threadIdx.x, D1 = disp_max + 1;
+  // temp2 is written on [first, last): the walk's last read is temp1's last entry
+  const long long first = (long long)(gw + 1) * D1, last = first + ((long long)gw * gh - 2LL * gw - 2) * D1;
+  const long long offs[9] = {0, D1, 2LL * D1, (long long)gw * D1, (long long)(gw + 1) * D1, (long long)(gw + 2) * D1,
+                             2LL * gw * D1, (2LL * gw + 1) * D1, (2LL * gw + 2) * D1};
+  for (int s = lane; s < D1; s += 64) list[s] = 0;
+  __syncthreads();
+  int count = 0;
+  for (int d0 = 0; d0 < D1; d0 += 64) {
+    const int d = d0 + lane;
+    bool on = false;
+    const long long j = (long long)cell * D1 + d;
+    if (d < D1 && j >= first && j < last)
+      for (int o = 0; o < 9; ++o) on |= temp1[j - first + offs[o]] != 0;
+    const unsigned long long mask = __ballot(on);
+    if (on) list[count + __popcll(mask & ((1ull << lane) - 1ull))] = d;
+    count += __popcll(mask);
+  }
+  __syncthreads();
+  int32_t* g = grid + (size_t)cell * (D1 + 1);
+  for (int s = lane; s < D1; s += 64) g[1 + s] = list[s];
+  if (lane == 0) g[0] = count;
+}
+}  // namespace
+
+namespace {
+// the grid dimensions Elas::process computes (elas.cpp:96-98): IMAGE sizes, also with subsampling
+void grid_dims_of(const plvs_elas* h, int width, int height, int32_t gd[3]) {
+  gd[0] = h->prm.disp_max + 2;
+  gd[1] = (int32_t)std::ceil((float)width / (float)h->prm.grid_size);
+  gd[2] = (int32_t)std::ceil((float)height / (float)h->prm.grid_size);
+}
+
+// the candidate loop into h->D_can (asynchronous; the descriptor pair must be staged)
+int candidates_core(plvs_elas* h, int width, int height) {
+  PLVS_REQUIRE(h->prm.candidate_stepsize > 0 && h->prm.disp_max >= h->prm.disp_min && h->prm.disp_max < 32767, "support parameters");
+  hipStream_t s = h->stream;
+  SupportParams sp;
+  sp.width = width; sp.height = height;
+  sp.step = h->prm.candidate_stepsize + (h->prm.subsampling ? h->prm.candidate_stepsize % 2 : 0);   // elas.cpp:420-422
+  sp.can_w = (width + sp.step - 1) / sp.step;
+  sp.can_h = (height + sp.step - 1) / sp.step;
+  sp.disp_min = h->prm.disp_min; sp.disp_max = h->prm.disp_max; sp.support_texture = h->prm.support_texture;
+  sp.lr_threshold = h->prm.lr_threshold; sp.support_threshold = h->prm.support_threshold;
+  const size_t ncan = (size_t)sp.can_w * sp.can_h;
+  PLVS_HIP_TRY(h->D_can.reserve(ncan));
+  PLVS_HIP_TRY(hipMemsetAsync(h->D_can.p, 0, ncan * sizeof(int16_t), s));   // (row 0 / column 0: calloc's zeros, elas.cpp:429)
+  if (sp.can_w > 1 && sp.can_h > 1) {
+    hipLaunchKernelGGL(elas_support_candidates, dim3((unsigned)(sp.can_w - 1), (unsigned)(sp.can_h - 1)), dim3(64), 0, s, sp,
+                       reinterpret_cast<const uint4*>(h->desc1.p), reinterpret_cast<const uint4*>(h->desc2.p), h->D_can.p);
+    PLVS_KERNEL_CHECK();
+  }
+  h->can_w = sp.can_w; h->can_h = sp.can_h; h->can_step = sp.step; h->can_width = width; h->can_height = height;
+  return PLVS_OK;
+}
+
+// the filters, the list and the corners of the grid in h->D_can -> h->sp, count in h->sp_n (asynchronous)
+int support_core(plvs_elas* h) {
+  PLVS_REQUIRE(h->can_w >= 1 && h->can_h >= 1, "no candidate grid in HBM");
+  hipStream_t s = h->stream;
+  const size_t ncan = (size_t)h->can_w * h->can_h, cap = (size_t)(h->can_w - 1) * (h->can_h - 1) + 6;
+  PLVS_HIP_TRY(h->can_a.reserve(ncan));
+  PLVS_HIP_TRY(h->can_b.reserve(ncan));
+  PLVS_HIP_TRY(h->sp.reserve(cap));
+  PLVS_HIP_TRY(h->sp_n.reserve(1));
+  const SupportListParams P{h->can_w, h->can_h, h->can_step, h->can_width, h->can_height, h->prm.add_corners ? 1 : 0};
+  hipLaunchKernelGGL(elas_support_points, dim3(1), dim3(kFilterThreads), 0, s, P, h->D_can.p, h->can_a.p, h->can_b.p, h->sp.p,
+                     h->sp_n.p);
+  PLVS_KERNEL_CHECK();
+  return PLVS_OK;
+}
+
+// createGrid of the n device support points into grid (device, gd[0] * gd[1] * gd[2] ints), asynchronous
+int grid_core(plvs_elas* h, const Support* sp, int n, int right_image, const int32_t gd[3], int32_t* grid, plvs::DevBuf<uint8_t>& mark) {
+  const int gw = gd[1], gh = gd[2], D1 = gd[0] - 1;
+  PLVS_REQUIRE((int64_t)gw * gh >= 2 * (int64_t)gw + 2,
+               "disparity grid of fewer than 2 * grid_width + 2 cells (the reference's dilation walk has no end there)");
+  PLVS_REQUIRE(D1 >= 1 && D1 <= 16384, "disp_max");
+  hipStream_t s = h->stream;
+  const size_t nmark = (size_t)gw * gh * D1;
+  PLVS_HIP_TRY(mark.reserve(nmark));
+  PLVS_HIP_TRY(hipMemsetAsync(mark.p, 0, nmark, s));
+  if (n > 0)
+    hipLaunchKernelGGL(elas_grid_mark, dim3(ceil_div((size_t)n, 256)), dim3(256), 0, s, sp, n, right_image ? 1 : 0,
+                       h->prm.grid_size, h->prm.disp_max, gw, gh, mark.p);
+  hipLaunchKernelGGL(elas_grid_cells, dim3((unsigned)(gw * gh)), dim3(64), (size_t)D1 * sizeof(int32_t), s, mark.p,
+                     h->prm.disp_max, gw, gh, grid);
+  PLVS_KERNEL_CHECK();
+  return PLVS_OK;
+}
+
+int planes_core(plvs_elas* h, const Support* sp, Triangle* tri, int n_tri) {
+  if (n_tri > 0) {
+    hipLaunchKernelGGL(elas_planes, dim3(ceil_div((size_t)n_tri, 256)), dim3(256), 0, h->stream, sp, tri, n_tri);
+    PLVS_KERNEL_CHECK();
+  }
+  return PLVS_OK;
+}
+
+// computeDisparity on device-resident support points, triangles and grid; the map stays in HBM (res[side]) and is
+// downloaded to D if given.  Synchronises the stream.
+int disparity_core(plvs_elas* h, const Support* sp, const Triangle* tri, int n_tri, const int32_t* grid, const int32_t* grid_dims,
+                   int width, int height, int right_image, float* D) {
+  hipStream_t s = h->stream;
+  const bool sub = h->prm.subsampling != 0;
+  const int ow = sub ? width / 2 : width, oh = sub ? height / 2 : height;
+  const size_t npix = (size_t)ow * oh;
+  const int disp_num = grid_dims[0] - 1;
+  // the prior table and the plane radius on the host, in the reference's float arithmetic (elas.cpp:861-865: exp / log /
+  // ceil of floats under `using namespace std`)
+  std::vector<int32_t> P((size_t)disp_num);
+  const float two_sigma_squared = 2 * h->prm.sigma * h->prm.sigma;
+  for (int32_t delta_d = 0; delta_d < disp_num; ++delta_d)
+    P[(size_t)delta_d] = (int32_t)((-std::log(h->prm.gamma + std::exp((float)(-delta_d * delta_d) / two_sigma_squared)) +
+                                    std::log(h->prm.gamma)) / h->prm.beta);
+  MatchParams mp;
+  mp.width = width; mp.height = height; mp.subsampling = sub; mp.right_image = right_image != 0;
+  mp.grid_size = h->prm.grid_size; mp.match_texture = h->prm.match_texture;
+  mp.plane_radius = (int32_t)std::max(std::ceil(h->prm.sigma * h->prm.sradius), 2.0f);
+  mp.disp_num = disp_num; mp.grid_w = grid_dims[1]; mp.grid_stride = grid_dims[0];
+  PLVS_HIP_TRY(h->prior.reserve((size_t)disp_num));
+  PLVS_HIP_TRY(h->owner.reserve(npix));
+  PLVS_HIP_TRY(h->D.reserve(npix));
+  PLVS_HIP_TRY(hipMemcpyAsync(h->prior.p, P.data(), (size_t)disp_num * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  PLVS_HIP_TRY(hipMemsetAsync(h->owner.p, 0, npix * sizeof(uint32_t), s));
+  if (n_tri) {
+    hipLaunchKernelGGL(elas_owner, dim3((unsigned)n_tri), dim3(64), 0, s, mp, tri, n_tri, sp, h->owner.p);
+    PLVS_KERNEL_CHECK();
+  }
+  hipLaunchKernelGGL(elas_match, dim3(ceil_div((size_t)ow, 256), (unsigned)oh), dim3(256), 0, s, mp, tri, sp, h->owner.p, grid,
+                     h->prior.p, reinterpret_cast<const uint4*>(h->desc1.p), reinterpret_cast<const uint4*>(h->desc2.p), h->D.p);
+  PLVS_KERNEL_CHECK();
+  {   // the map stays in HBM as well (the post-processing chain reads it there)
+    const int side = right_image ? 1 : 0;
+    PLVS_HIP_TRY(h->res[side].reserve(npix));
+    PLVS_HIP_TRY(hipMemcpyAsync(h->res[side].p, h->D.p, npix * sizeof(float), hipMemcpyDeviceToDevice, s));
+    h->res_w[side] = ow;
+    h->res_h[side] = oh;
+  }
+  if (D) PLVS_HIP_TRY(hipMemcpyAsync(D, h->D.p, npix * sizeof(float), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  return PLVS_OK;
+}
+
+// joins a helper thread when the scope ends, however it ends
+struct JoinOnExit {
+  std::thread& t;
+  ~JoinOnExit() {
+    if (t.joinable()) t.join();
+  }
+};
+
+int triangulate_into(const Support* sp, int n, int right_image, std::vector<Triangle>& out) {
+  std::vector<int32_t> xs(n), ys(n), corners;
+  for (int i = 0; i < n; ++i) {
+    xs[i] = right_image ? sp[i].u - sp[i].d : sp[i].u;
+    ys[i] = sp[i].v;
+    PLVS_REQUIRE(xs[i] > -(1 << 24) && xs[i] < (1 << 24) && ys[i] > -(1 << 24) && ys[i] < (1 << 24),
+                 "support coordinates beyond 2^24 (the reference's float vertices)");
+  }
+  plvs::elas_dt::Triangulator().run(xs.data(), ys.data(), n, corners);
+  out.resize(corners.size() / 3);
+  for (size_t i = 0; i < out.size(); ++i)
+    out[i] = Triangle{corners[3 * i], corners[3 * i + 1], corners[3 * i + 2], 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return PLVS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -695,6 +1091,8 @@ int plvs_hip_elas_destroy(plvs_elas* h) {
   h->desc1.release(); h->desc2.release(); h->support.release(); h->tri.release(); h->grid.release(); h->prior.release();
   h->owner.release(); h->D.release(); h->D_copy.release(); h->D_tmp.release(); h->D_can.release(); h->seg_parent.release(); h->seg_size.release(); h->seg_run.release(); h->img.release(); h->sob_u.release(); h->sob_v.release();
   h->res[0].release(); h->res[1].release();
+  h->can_a.release(); h->can_b.release(); h->sp.release(); h->sp_n.release();
+  for (int k = 0; k < 2; ++k) { h->ptri[k].release(); h->pgrid[k].release(); h->gmark[k].release(); }
   delete h;
   return PLVS_OK;
 }
@@ -773,6 +1171,7 @@ int plvs_hip_elas_support_candidates(plvs_elas* h, const uint8_t* I1_desc, const
   }
   PLVS_HIP_TRY(hipMemcpyAsync(D_can, h->D_can.p, ncan * sizeof(int16_t), hipMemcpyDeviceToHost, s));
   PLVS_HIP_TRY(hipStreamSynchronize(s));
+  h->can_w = sp.can_w; h->can_h = sp.can_h; h->can_step = sp.step; h->can_width = width; h->can_height = height;
   h->desc_width = width;     // (the pair stays staged for the compute_disparity calls that follow)
   h->desc_height = height;
   return PLVS_OK;
@@ -802,30 +1201,11 @@ int plvs_hip_elas_compute_disparity(plvs_elas* h, const int32_t* support, int n_
     PLVS_REQUIRE(ht[i].c1 >= 0 && ht[i].c1 < n_support && ht[i].c2 >= 0 && ht[i].c2 < n_support && ht[i].c3 >= 0 &&
                      ht[i].c3 < n_support, "triangle corner outside the support points");
   hipStream_t s = h->stream;
-  const bool sub = h->prm.subsampling != 0;
-  const int ow = sub ? width / 2 : width, oh = sub ? height / 2 : height;
-  const size_t npix = (size_t)ow * oh, desc_bytes = (size_t)16 * width * height;
+  const size_t desc_bytes = (size_t)16 * width * height;
   const size_t ngrid = (size_t)grid_dims[0] * grid_dims[1] * grid_dims[2];
-  const int disp_num = grid_dims[0] - 1;
-  // the prior table and the plane radius on the host, in the reference's float arithmetic (elas.cpp:861-865: exp / log /
-  // ceil of floats under `using namespace std`)
-  std::vector<int32_t> P((size_t)disp_num);
-  const float two_sigma_squared = 2 * h->prm.sigma * h->prm.sigma;
-  for (int32_t delta_d = 0; delta_d < disp_num; ++delta_d)
-    P[(size_t)delta_d] = (int32_t)((-std::log(h->prm.gamma + std::exp((float)(-delta_d * delta_d) / two_sigma_squared)) +
-                                    std::log(h->prm.gamma)) / h->prm.beta);
-  MatchParams mp;
-  mp.width = width; mp.height = height; mp.subsampling = sub; mp.right_image = right_image != 0;
-  mp.grid_size = h->prm.grid_size; mp.match_texture = h->prm.match_texture;
-  mp.plane_radius = (int32_t)std::max(std::ceil(h->prm.sigma * h->prm.sradius), 2.0f);
-  mp.disp_num = disp_num; mp.grid_w = grid_dims[1]; mp.grid_stride = grid_dims[0];
-
   PLVS_HIP_TRY(h->support.reserve((size_t)std::max(n_support, 1)));
   PLVS_HIP_TRY(h->tri.reserve((size_t)std::max(n_tri, 1)));
   PLVS_HIP_TRY(h->grid.reserve(ngrid));
-  PLVS_HIP_TRY(h->prior.reserve((size_t)disp_num));
-  PLVS_HIP_TRY(h->owner.reserve(npix));
-  PLVS_HIP_TRY(h->D.reserve(npix));
   if (I1_desc != nullptr) {
     PLVS_HIP_TRY(h->desc1.reserve(desc_bytes));
     PLVS_HIP_TRY(h->desc2.reserve(desc_bytes));
@@ -836,25 +1216,8 @@ int plvs_hip_elas_compute_disparity(plvs_elas* h, const int32_t* support, int n_
   if (n_support) PLVS_HIP_TRY(hipMemcpyAsync(h->support.p, hs, (size_t)n_support * sizeof(Support), hipMemcpyHostToDevice, s));
   if (n_tri) PLVS_HIP_TRY(hipMemcpyAsync(h->tri.p, ht, (size_t)n_tri * sizeof(Triangle), hipMemcpyHostToDevice, s));
   PLVS_HIP_TRY(hipMemcpyAsync(h->grid.p, disparity_grid, ngrid * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  PLVS_HIP_TRY(hipMemcpyAsync(h->prior.p, P.data(), (size_t)disp_num * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  PLVS_HIP_TRY(hipMemsetAsync(h->owner.p, 0, npix * sizeof(uint32_t), s));
-  if (n_tri) {
-    hipLaunchKernelGGL(elas_owner, dim3((unsigned)n_tri), dim3(64), 0, s, mp, h->tri.p, n_tri, h->support.p, h->owner.p);
-    PLVS_KERNEL_CHECK();
-  }
-  hipLaunchKernelGGL(elas_match, dim3(ceil_div((size_t)ow, 256), (unsigned)oh), dim3(256), 0, s, mp, h->tri.p, h->support.p,
-                     h->owner.p, h->grid.p, h->prior.p, reinterpret_cast<const uint4*>(h->desc1.p),
-                     reinterpret_cast<const uint4*>(h->desc2.p), h->D.p);
-  PLVS_KERNEL_CHECK();
-  {   // the map stays in HBM as well (the post-processing chain reads it there)
-    const int side = right_image ? 1 : 0;
-    PLVS_HIP_TRY(h->res[side].reserve(npix));
-    PLVS_HIP_TRY(hipMemcpyAsync(h->res[side].p, h->D.p, npix * sizeof(float), hipMemcpyDeviceToDevice, s));
-    h->res_w[side] = ow;
-    h->res_h[side] = oh;
-  }
-  if (D) PLVS_HIP_TRY(hipMemcpyAsync(D, h->D.p, npix * sizeof(float), hipMemcpyDeviceToHost, s));
-  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  const int rc = disparity_core(h, h->support.p, h->tri.p, n_tri, h->grid.p, grid_dims, width, height, right_image, D);
+  if (rc != PLVS_OK) return rc;
   if (I1_desc != nullptr) {
     h->desc_width = width;
     h->desc_height = height;
@@ -974,5 +1337,165 @@ int plvs_hip_elas_depth_dev(plvs_elas* h, float bf, int step, float* d_depth, in
   return PLVS_OK;
 }
 #undef ELAS_STAGE_SIZES
+
+// Elas::computeDelaunayTriangulation (elas.cpp:492-556): host code, no handle, no device (elas_delaunay.hpp)
+int plvs_hip_elas_triangulate(const int32_t* support, int n_support, int right_image, void* tri, int cap, int* n_tri) {
+  PLVS_REQUIRE(support && n_tri && n_support >= 0 && cap >= 0 && (tri || cap == 0), "null argument / negative count");
+  *n_tri = 0;
+  if (n_support < 3) {
+    plvs::set_error("triangulate: %d support points, the reference needs 3", n_support);
+    return PLVS_ERR_EMPTY;
+  }
+  const Support* sp = reinterpret_cast<const Support*>(support);
+  std::vector<int32_t> xs(n_support), ys(n_support), corners;
+  for (int i = 0; i < n_support; ++i) {
+    xs[i] = right_image ? sp[i].u - sp[i].d : sp[i].u;
+    ys[i] = sp[i].v;
+    PLVS_REQUIRE(xs[i] > -(1 << 24) && xs[i] < (1 << 24) && ys[i] > -(1 << 24) && ys[i] < (1 << 24),
+                 "support coordinates beyond 2^24 (the reference's float vertices)");
+  }
+  plvs::elas_dt::Triangulator().run(xs.data(), ys.data(), n_support, corners);
+  const int nt = (int)(corners.size() / 3);
+  *n_tri = nt;
+  if (nt > cap) {
+    plvs::set_error("triangulate: %d triangles, room for %d", nt, cap);
+    return PLVS_ERR_CAPACITY;
+  }
+  Triangle* out = static_cast<Triangle*>(tri);
+  for (int i = 0; i < nt; ++i) out[i] = Triangle{corners[3 * i], corners[3 * i + 1], corners[3 * i + 2], 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return PLVS_OK;
+}
+
+// computeSupportMatches after its candidate loop (elas.cpp:459-486): filters, list, corners on the device
+int plvs_hip_elas_support_points(plvs_elas* h, const int16_t* D_can, int width, int height, int32_t* support, int cap,
+                                 int* n_support) {
+  PLVS_REQUIRE(h && n_support && cap >= 0 && (support || cap == 0), "null argument");
+  PLVS_REQUIRE(width >= 16 && height >= 16, "image size");
+  hipStream_t s = h->stream;
+  if (D_can) {
+    const int step = h->prm.candidate_stepsize + (h->prm.subsampling ? h->prm.candidate_stepsize % 2 : 0);
+    PLVS_REQUIRE(step > 0, "candidate_stepsize");
+    const int cw = (width + step - 1) / step, ch = (height + step - 1) / step;
+    PLVS_HIP_TRY(h->D_can.reserve((size_t)cw * ch));
+    PLVS_HIP_TRY(hipMemcpyAsync(h->D_can.p, D_can, (size_t)cw * ch * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    h->can_w = cw; h->can_h = ch; h->can_step = step; h->can_width = width; h->can_height = height;
+  } else {
+    PLVS_REQUIRE(h->can_w > 0 && h->can_width == width && h->can_height == height,
+                 "no candidate grid of this image size in HBM (plvs_hip_elas_support_candidates first, or pass D_can)");
+  }
+  int rc = support_core(h);
+  if (rc != PLVS_OK) return rc;
+  int32_t n = 0;
+  PLVS_HIP_TRY(hipMemcpyAsync(&n, h->sp_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  *n_support = n;
+  h->can_w = 0;   // (the filters ran in place: the grid in HBM is no longer the candidate loop's)
+  if (n > cap) {
+    plvs::set_error("support_points: %d points, room for %d", n, cap);
+    return PLVS_ERR_CAPACITY;
+  }
+  if (n) {
+    PLVS_HIP_TRY(hipMemcpyAsync(support, h->sp.p, (size_t)n * sizeof(Support), hipMemcpyDeviceToHost, s));
+    PLVS_HIP_TRY(hipStreamSynchronize(s));
+  }
+  return PLVS_OK;
+}
+
+// computeDisparityPlanes (elas.cpp:561-633), both planes of every triangle, on the device
+int plvs_hip_elas_disparity_planes(plvs_elas* h, const int32_t* support, int n_support, void* tri, int n_tri) {
+  PLVS_REQUIRE(h && n_support >= 0 && n_tri >= 0 && (n_tri == 0 || (support && tri)), "null argument");
+  Triangle* ht = static_cast<Triangle*>(tri);
+  for (int i = 0; i < n_tri; ++i)
+    PLVS_REQUIRE(ht[i].c1 >= 0 && ht[i].c1 < n_support && ht[i].c2 >= 0 && ht[i].c2 < n_support && ht[i].c3 >= 0 &&
+                     ht[i].c3 < n_support, "triangle corner outside the support points");
+  if (n_tri == 0) return PLVS_OK;
+  hipStream_t s = h->stream;
+  PLVS_HIP_TRY(h->sp.reserve((size_t)n_support));
+  PLVS_HIP_TRY(h->ptri[0].reserve((size_t)n_tri));
+  PLVS_HIP_TRY(hipMemcpyAsync(h->sp.p, support, (size_t)n_support * sizeof(Support), hipMemcpyHostToDevice, s));
+  PLVS_HIP_TRY(hipMemcpyAsync(h->ptri[0].p, ht, (size_t)n_tri * sizeof(Triangle), hipMemcpyHostToDevice, s));
+  int rc = planes_core(h, h->sp.p, h->ptri[0].p, n_tri);
+  if (rc != PLVS_OK) return rc;
+  PLVS_HIP_TRY(hipMemcpyAsync(ht, h->ptri[0].p, (size_t)n_tri * sizeof(Triangle), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  return PLVS_OK;
+}
+
+// createGrid (elas.cpp:635-715) on the device; grid_dims out = {disp_max + 2, ceil(w / grid_size), ceil(h / grid_size)}
+int plvs_hip_elas_create_grid(plvs_elas* h, const int32_t* support, int n_support, int width, int height, int right_image,
+                              int32_t* disparity_grid, int32_t* grid_dims) {
+  PLVS_REQUIRE(h && disparity_grid && grid_dims && n_support >= 0 && (n_support == 0 || support), "null argument");
+  PLVS_REQUIRE(width >= 1 && height >= 1, "image size");
+  int32_t gd[3];
+  grid_dims_of(h, width, height, gd);
+  hipStream_t s = h->stream;
+  const size_t ngrid = (size_t)gd[0] * gd[1] * gd[2];
+  PLVS_HIP_TRY(h->sp.reserve((size_t)std::max(n_support, 1)));
+  PLVS_HIP_TRY(h->pgrid[0].reserve(ngrid));
+  if (n_support)
+    PLVS_HIP_TRY(hipMemcpyAsync(h->sp.p, support, (size_t)n_support * sizeof(Support), hipMemcpyHostToDevice, s));
+  int rc = grid_core(h, h->sp.p, n_support, right_image, gd, h->pgrid[0].p, h->gmark[0]);
+  if (rc != PLVS_OK) return rc;
+  PLVS_HIP_TRY(hipMemcpyAsync(disparity_grid, h->pgrid[0].p, ngrid * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < 3; ++k) grid_dims[k] = gd[k];
+  return PLVS_OK;
+}
+
+// Elas::process (elas.cpp:36-157) in one call
+int plvs_hip_elas_process(plvs_elas* h, const uint8_t* I1, const uint8_t* I2, const int32_t* dims, int postprocess_only_left,
+                          int filter_adaptive_mean, float* D1, float* D2) {
+  PLVS_REQUIRE(h && I1 && I2 && dims, "null argument");
+  const int width = dims[0], height = dims[1], stride = dims[2];
+  PLVS_REQUIRE(width >= 16 && height >= 16 && stride >= width, "image size / bytes per line");
+  int32_t gd[3];
+  grid_dims_of(h, width, height, gd);
+  PLVS_REQUIRE((int64_t)gd[1] * gd[2] >= 2 * (int64_t)gd[1] + 2,
+               "disparity grid of fewer than 2 * grid_width + 2 cells (the reference's dilation walk has no end there)");
+  int rc = plvs_hip_elas_set_images(h, I1, I2, width, height, stride);
+  if (rc == PLVS_OK) rc = candidates_core(h, width, height);
+  if (rc == PLVS_OK) rc = support_core(h);
+  if (rc != PLVS_OK) return rc;
+  hipStream_t s = h->stream;
+  h->can_w = 0;   // (filtered in place)
+  int32_t n = 0;
+  PLVS_HIP_TRY(hipMemcpyAsync(&n, h->sp_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  if (n < 3) {
+    plvs::set_error("process: %d support points, the reference needs 3 (elas.cpp:72-77)", n);
+    return PLVS_ERR_EMPTY;
+  }
+  std::vector<Support> sup((size_t)n);
+  PLVS_HIP_TRY(hipMemcpyAsync(sup.data(), h->sp.p, (size_t)n * sizeof(Support), hipMemcpyDeviceToHost, s));
+  PLVS_HIP_TRY(hipStreamSynchronize(s));
+  // both grids on the device while the host triangulates the left and the right image
+  const size_t ngrid = (size_t)gd[0] * gd[1] * gd[2];
+  for (int k = 0; k < 2 && rc == PLVS_OK; ++k) {
+    PLVS_HIP_TRY(h->pgrid[k].reserve(ngrid));
+    rc = grid_core(h, h->sp.p, n, k, gd, h->pgrid[k].p, h->gmark[k]);
+  }
+  if (rc != PLVS_OK) return rc;
+  std::vector<Triangle> tri[2];
+  int trc[2] = {PLVS_OK, PLVS_OK};
+  {
+    std::thread right([&]() { trc[1] = triangulate_into(sup.data(), n, 1, tri[1]); });
+    JoinOnExit join{right};
+    trc[0] = triangulate_into(sup.data(), n, 0, tri[0]);
+  }
+  if (trc[0] != PLVS_OK) return trc[0];
+  if (trc[1] != PLVS_OK) return trc[1];
+  for (int k = 0; k < 2; ++k) {
+    const int nt = (int)tri[k].size();
+    PLVS_HIP_TRY(h->ptri[k].reserve((size_t)std::max(nt, 1)));
+    if (nt) PLVS_HIP_TRY(hipMemcpyAsync(h->ptri[k].p, tri[k].data(), (size_t)nt * sizeof(Triangle), hipMemcpyHostToDevice, s));
+    rc = planes_core(h, h->sp.p, h->ptri[k].p, nt);
+    if (rc != PLVS_OK) return rc;
+  }
+  for (int k = 0; k < 2; ++k) {
+    rc = disparity_core(h, h->sp.p, h->ptri[k].p, (int)tri[k].size(), h->pgrid[k].p, gd, width, height, k, nullptr);
+    if (rc != PLVS_OK) return rc;
+  }
+  return plvs_hip_elas_postprocess(h, width, height, postprocess_only_left, filter_adaptive_mean, D1, D2);
+}
 
 }  // extern "C"

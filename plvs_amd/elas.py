@@ -1,11 +1,12 @@
 """Host-side mirror of libelas::ElasGPU (Thirdparty/libelas-gpu/GPU/elas_gpu.h:29-47): the two methods of libelas::Elas the
 reference's accelerated build overrides — computeDisparity and adaptiveMean — as PointCloudKeyFrame::ProcessStereoLibelas
-reaches them (src/PointCloudKeyFrame.cc:335-432) — and the other device stages of a pair: setImages (the descriptor
-images), supportCandidates (the candidate loop of computeSupportMatches), leftRightConsistencyCheck, removeSmallSegments,
-gapInterpolation.  Same argument meaning as the reference's methods; the support filters, the triangulation, the planes
-and the grid of Elas::process are the caller's.  Preconditions shared with the reference: invalid pixels hold -10,
-speckle_sim_threshold < 10; parity is against a reference whose uninitialised reads see zeros (DESIGN §3:
-the zero-filling malloc the test build of the reference is compiled with).  The arithmetic runs in libplvs_hip.so; there is no CPU fallback."""
+reaches them (src/PointCloudKeyFrame.cc:335-432) — and the other stages of a pair: setImages (the descriptor images),
+supportCandidates (the candidate loop of computeSupportMatches), supportPoints (its filters, list and corners),
+triangulate (the Delaunay triangulation, host code), computeDisparityPlanes, createGrid, leftRightConsistencyCheck,
+removeSmallSegments, gapInterpolation — and all of Elas::process in one call (process).  Same argument meaning as the
+reference's methods.  Preconditions shared with the reference: invalid pixels hold -10, speckle_sim_threshold < 10; parity
+is against a reference whose uninitialised reads see zeros (the zero-filling malloc the test build of the
+reference is compiled with).  The arithmetic runs in libplvs_hip.so; there is no CPU fallback."""
 import ctypes
 
 import numpy as np
@@ -39,6 +40,11 @@ L.plvs_hip_elas_set_images.argtypes = [_vp, _vp, _vp, _i, _i, _i]
 L.plvs_hip_elas_download_descriptors.argtypes = [_vp, _vp, _vp]
 L.plvs_hip_elas_remove_small_segments.argtypes = [_vp, _vp, _i, _i]
 L.plvs_hip_elas_gap_interpolation.argtypes = [_vp, _vp, _i, _i]
+L.plvs_hip_elas_triangulate.argtypes = [_vp, _i, _i, _vp, _i, ctypes.POINTER(_i)]
+L.plvs_hip_elas_process.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]
+L.plvs_hip_elas_support_points.argtypes = [_vp, _vp, _i, _i, _vp, _i, ctypes.POINTER(_i)]
+L.plvs_hip_elas_disparity_planes.argtypes = [_vp, _vp, _i, _vp, _i]
+L.plvs_hip_elas_create_grid.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp]
 
 
 class ElasGPU:
@@ -168,6 +174,73 @@ class ElasGPU:
                                                       None if d2 is None else _lib.np_ptr(d2), int(width), int(height),
                                                       _lib.np_ptr(D_can)))
         return D_can
+
+    def process(self, I1, I2, postprocess_only_left=True, filter_adaptive_mean=True, download=True):
+        """Elas::process (elas.cpp:36-157) in one call on two u8 images [height, width] -> (D1, D2) float32 (half size with
+        subsampling); download=False: the maps stay in HBM only (depthDev next), None is returned.  Fewer than 3 support
+        points raise PlvsHipError(PLVS_ERR_EMPTY).  No median filter (MIDDLEBURY's filter_median is not built)."""
+        I1, I2 = np.ascontiguousarray(I1, dtype=np.uint8), np.ascontiguousarray(I2, dtype=np.uint8)
+        if I1.ndim != 2 or I1.shape != I2.shape:
+            raise ValueError("two u8 images of one size")
+        h, w = I1.shape
+        self._img_shape = I1.shape
+        dims = np.array([w, h, w], np.int32)
+        D1 = np.empty(self._out_shape(w, h), np.float32) if download else None
+        D2 = np.empty(self._out_shape(w, h), np.float32) if download else None
+        _lib.check(L.plvs_hip_elas_process(self._h, _lib.np_ptr(I1), _lib.np_ptr(I2), _lib.np_ptr(dims),
+                                           int(bool(postprocess_only_left)), int(bool(filter_adaptive_mean)), _lib.np_ptr(D1),
+                                           _lib.np_ptr(D2)))
+        return (D1, D2) if download else None
+
+    def supportPoints(self, D_can, width, height, cap=None):
+        """The filters, list and corners of computeSupportMatches (elas.cpp:459-486) on the candidate grid D_can (int16
+        [D_can_height, D_can_width]; None = the grid the last supportCandidates left in HBM) -> SUPPORT_PT records."""
+        can = None if D_can is None else np.ascontiguousarray(D_can, dtype=np.int16)
+        cw, ch, _ = self.candidateGrid(width, height)
+        if can is not None and can.size != cw * ch:
+            raise ValueError("D_can does not have the size of the candidate grid")
+        cap = (cw - 1) * (ch - 1) + 6 if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), SUPPORT_PT)
+        n = _i()
+        _lib.check(L.plvs_hip_elas_support_points(self._h, _lib.np_ptr(can), int(width), int(height), _lib.np_ptr(out), cap,
+                                                  ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def computeDisparityPlanes(self, p_support, tri):
+        """Elas::computeDisparityPlanes (elas.cpp:561-633) -> a copy of tri with both planes of every triangle filled."""
+        sup = np.ascontiguousarray(p_support, dtype=SUPPORT_PT).reshape(-1)
+        tri = np.ascontiguousarray(tri, dtype=TRIANGLE).reshape(-1).copy()
+        _lib.check(L.plvs_hip_elas_disparity_planes(self._h, _lib.np_ptr(sup), len(sup), _lib.np_ptr(tri), len(tri)))
+        return tri
+
+    def gridDims(self, width, height):
+        """{disp_max + 2, ceil(width / grid_size), ceil(height / grid_size)} as Elas::process computes it (elas.cpp:96-98)."""
+        gs = np.float32(self.param.grid_size)
+        return np.array([self.param.disp_max + 2, int(np.ceil(np.float32(width) / gs)), int(np.ceil(np.float32(height) / gs))],
+                        np.int32)
+
+    def createGrid(self, p_support, width, height, right_image):
+        """Elas::createGrid (elas.cpp:635-715) -> (disparity_grid int32 [grid_dims product], grid_dims int32 [3])."""
+        sup = np.ascontiguousarray(p_support, dtype=SUPPORT_PT).reshape(-1)
+        gd = self.gridDims(width, height)
+        grid = np.empty(int(np.prod(gd.astype(np.int64))), np.int32)
+        out_dims = np.zeros(3, np.int32)
+        _lib.check(L.plvs_hip_elas_create_grid(self._h, _lib.np_ptr(sup), len(sup), int(width), int(height),
+                                               int(bool(right_image)), _lib.np_ptr(grid), _lib.np_ptr(out_dims)))
+        return grid, out_dims
+
+    @staticmethod
+    def triangulate(p_support, right_image):
+        """Elas::computeDelaunayTriangulation (elas.cpp:492-556): the reference's Triangle triangulation of the support
+        points (u, v), or (u - d, v) with right_image -> TRIANGLE records in its order, corners (c1, c2, c3) in its order,
+        planes 0.  Host code; needs no GPU.  Fewer than 3 points raise (the reference never triangulates those)."""
+        sup = np.ascontiguousarray(p_support, dtype=SUPPORT_PT).reshape(-1)
+        cap = 2 * len(sup) + 2              # a planar triangulation of n points has at most 2n - 5 triangles
+        tri = np.zeros(cap, TRIANGLE)
+        n = _i()
+        _lib.check(L.plvs_hip_elas_triangulate(_lib.np_ptr(sup), len(sup), int(bool(right_image)), _lib.np_ptr(tri), cap,
+                                               ctypes.byref(n)))
+        return tri[:n.value].copy()
 
     def _map(self, D, width, height):
         D = np.ascontiguousarray(D, dtype=np.float32).copy()
