@@ -1239,6 +1239,46 @@ int plvs_hip_tsdf_voxblox_halo_clear(plvs_tsdf_voxblox* h);
 int plvs_hip_tsdf_voxblox_halo_gather(plvs_tsdf_voxblox* h, void* rccl_comm, const int32_t* block_ids_xyz, int nblocks,
                                       int* fetched, void* stream);
 
+/* ------------------------------------------- chisel: projective depth + colour scan integrate
+ * The third input kind of PointCloudMapChisel::InsertData, kColorAndDepthImages:
+ *   PointCloudMapChisel::InsertDepthScanColor                  src/PointCloudMapChisel.cc:134-189
+ *   -> ChiselServer::IntegrateLastDepthImage                   Thirdparty/chisel_server/src/ChiselServer.cpp:632-647
+ *   -> Chisel::IntegrateDepthScanColorWithOneCameraModelBGR    open_chisel/include/open_chisel/Chisel.h:198-258
+ *   -> ProjectionIntegrator::IntegrateColorWithOneCameraModelBGR   .../ProjectionIntegrator.h:189-269
+ * Every voxel centre of every chunk on the depth camera's frustum list (ChunkManager.cpp:241-271, the list of the
+ * carving entry above; near / far plane = PointCloudMapping's minDepthDistance / maxDepthDistance) is projected into
+ * the depth image.  Within truncation(depth) + 2 sqrt(3) res of the measured surface the voxel takes the pixel's colour
+ * (ColorVoxel::IntegrateSimple, only while its colour weight is below 5) and DistVoxel::Integrate(depth - z,
+ * weight / (2 truncation)); kfid is not written.  With use_carving, a known voxel more than truncation + carving_dist
+ * in front of the surface with sdf < 1e-5 is Reset().  NaN depth = no measurement; a depth of 0 is a measurement, as in
+ * the reference.  Listed chunks the map lacks exist afterwards only if a voxel of theirs was integrated (the reference
+ * creates all of them and collects the rest, Chisel.cpp:67-77): the others never take a slot of max_chunks.  Another
+ * integrator than the ray walk of plvs_hip_tsdf_chisel_integrate — it builds a different map — and bit-identical to
+ * the reference's (tests/test_chisel_scan_reference.py).  Not available on order_free or sharded handles
+ * (PLVS_ERR_INVALID_ARG).  plvs_tsdf_stats afterwards: visits = voxels integrated + voxels reset, points = 0;
+ * plvs_hip_tsdf_chisel_updated_chunk_ids[_dev] lists the chunks the call updated (meshesToUpdate takes their 27
+ * neighbourhoods). */
+typedef struct plvs_scan_camera {
+  float fx, fy, cx, cy;          /* the depth camera (the colour image is registered to it) */
+  int width, height;
+  float near_plane, far_plane;
+} plvs_scan_camera;
+/* One scan, host pointers, synchronous.  depth: height rows of width floats, depth_pitch_bytes apart; bgr: height rows
+ * of width pixels of `channels` (3 or 4) bytes, blue first, bgr_pitch_bytes apart; NULL is refused
+ * (PLVS_ERR_INVALID_ARG: the depth-only IntegrateDepthScan is not provided).  Twc: 3x4 row-major, host. */
+int plvs_hip_tsdf_chisel_integrate_scan(plvs_tsdf_chisel* h, const float* depth, int depth_pitch_bytes,
+                                        const uint8_t* bgr, int bgr_pitch_bytes, int channels,
+                                        const plvs_scan_camera* camera, const float* Twc, int use_carving,
+                                        float carving_dist);
+/* nscans scans resident in device memory, dense: d_depth [nscans][height][width] f32, d_bgr
+ * [nscans][height][width][channels] u8, d_Twc [nscans][12] f32.  The same map as nscans single calls in that order,
+ * bit for bit, in the same few kernel launches whatever nscans is: every voxel is read and written once per call.  The
+ * updated-chunk list and the stats cover the whole call.  A map with deform enabled takes one scan per call.
+ * Asynchronous on `stream` except for reading the poses and the call's counters. */
+int plvs_hip_tsdf_chisel_integrate_scans_dev(plvs_tsdf_chisel* h, const float* d_depth, const uint8_t* d_bgr,
+                                             int channels, const plvs_scan_camera* camera, const float* d_Twc,
+                                             int nscans, int use_carving, float carving_dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

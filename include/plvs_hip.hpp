@@ -22,6 +22,8 @@
 // CPU fallback anywhere.
 #pragma once
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <set>
@@ -589,6 +591,59 @@ class PointCloudMapChisel {
     }
     InsertCloud(cloud_camera, Twc, max_range);
   }
+  // SetDepthCameraModel (src/PointCloudMapChisel.cc:63-67): the camera InsertDepthScanColor projects through
+  void SetDepthCameraModel(float fx, float fy, float cx, float cy, int width, int height) {
+    depthCam_.fx = fx; depthCam_.fy = fy; depthCam_.cx = cx; depthCam_.cy = cy;
+    depthCam_.width = width; depthCam_.height = height;
+    depthCam_.near_plane = near_; depthCam_.far_plane = far_;
+  }
+  // InsertDepthScanColor (src/PointCloudMapChisel.cc:134-189): the depth image and the BGR / BGRA image registered to
+  // it through the projective integrator (Chisel::IntegrateDepthScanColorWithOneCameraModelBGR, Chisel.h:198-258);
+  // carving follows useCarving.  colorChannels: cv::Mat::channels() of the colour image (3 or 4).
+  void InsertDepthScanColor(const Image32F& depthImage, const Image8U& colorImage, const SE3f& Twc, uint64_t /*timestamp*/ = 0,
+                            int colorChannels = 3) {
+    if (depthImage.data != nullptr && depthImage.rows > 0 && depthImage.cols > 0 && !colorImage.empty()) {
+      if (depthCam_.width != depthImage.cols || depthCam_.height != depthImage.rows || colorImage.cols != depthImage.cols ||
+          colorImage.rows != depthImage.rows)
+        throw std::invalid_argument("InsertDepthScanColor: SetDepthCameraModel first, with the size of the (registered) images");
+      Flush();   // (the scan reads and changes the map: what is waiting goes in first)
+      check(plvs_hip_tsdf_chisel_integrate_scan(h_, depthImage.data, (int)depthImage.step, colorImage.data, (int)colorImage.step,
+                                                colorChannels, &depthCam_, Twc.m, useCarving_ ? 1 : 0, carvingDist_));
+      MarkUpdated();   // the 27 neighbours of every updated chunk (Chisel.h:233-245)
+    } else {
+      std::fprintf(stderr, "PointCloudMapChisel::InsertDepthScanColor() - ERROR: depth and/or color images are emtpy \n");
+    }
+  }
+  // InsertData (src/PointCloudMapChisel.cc:192-225): the dispatch on the input kind; an unknown kind ends the process
+  // there (quick_exit), and here.
+  struct Input {
+    enum Type { kPointCloud, kColorAndDepthImages, kPointCloudAndDepthImage } type = kPointCloud;
+    const std::vector<PointSurfelSegment>* pCloudCamera = nullptr;
+    Image32F imgDepth;
+    Image8U imgColor;
+    int colorChannels = 3;
+    SE3f Twc{};
+    uint64_t timestamp = 0;
+    double maxRange = 0;
+  };
+  void InsertData(const Input& d) {
+    static const std::vector<PointSurfelSegment> none;
+    switch (d.type) {
+      case Input::kPointCloud:
+        InsertCloud(d.pCloudCamera ? *d.pCloudCamera : none, d.Twc, d.maxRange);
+        break;
+      case Input::kColorAndDepthImages:
+        InsertDepthScanColor(d.imgDepth, d.imgColor, d.Twc, d.timestamp, d.colorChannels);
+        break;
+      case Input::kPointCloudAndDepthImage:
+        InsertCloudWithDepth(d.pCloudCamera ? *d.pCloudCamera : none, d.Twc, d.imgDepth, depthCam_.fx, depthCam_.fy, depthCam_.cx,
+                             depthCam_.cy, d.maxRange);
+        break;
+      default:
+        std::fprintf(stderr, "PointCloudMapChisel<PointT>::InsertData() - ERROR - unknown data mode\n");
+        std::quick_exit(-1);
+    }
+  }
   // UpdateMap: UpdateMesh (meshes of the 27-neighbourhood of every chunk updated since the last call,
   // Chisel.cpp:553-568) + GetPointCloud (ChiselServer.cpp:971-1068).  Returns the cloud size.
   int UpdateMap() {
@@ -711,6 +766,7 @@ class PointCloudMapChisel {
   bool useCarving_;
   float carvingDist_, near_, far_;
   bool resetOnChange_ = true, deformOnChange_ = false, queue_ = true;
+  plvs_scan_camera depthCam_{};
   std::vector<float> xyz_;
   std::vector<uint8_t> rgb_;
   std::vector<uint32_t> kfid_;

@@ -3541,3 +3541,4 @@ int plvs_hip_tsdf_chisel_shard_note_saturated(plvs_tsdf_chisel* h, const int32_t
 }  // extern "C"
 
 #include "tsdf_chisel_deform.hpp"
+#include "tsdf_chisel_scan.hpp"

@@ -6,6 +6,10 @@
              (Thirdparty/chisel_server/src/ChiselServer.cpp:561, 664)
           -> chisel::Chisel::IntegratePointCloudWidthDepth
              (Thirdparty/open_chisel/src/Chisel.cpp:442-585)
+  PointCloudMapChisel.InsertDepthScanColor(depth, color, Twc, timestamp)
+      <-> PLVS2::PointCloudMapChisel<PointT>::InsertDepthScanColor  (src/PointCloudMapChisel.cc:134-189)
+          -> ChiselServer::IntegrateLastDepthImage (ChiselServer.cpp:632-647)
+          -> chisel::Chisel::IntegrateDepthScanColorWithOneCameraModelBGR (include/open_chisel/Chisel.h:198-258)
   Clear() <-> PointCloudMap::Clear ; GetChunk/ChunkIds give the map back.
 
 All compute happens in libplvs_hip.so; this file only marshals arguments.
@@ -26,6 +30,17 @@ class DepthBatch(ctypes.Structure):
                 ("width", ctypes.c_int), ("height", ctypes.c_int), ("step", ctypes.c_int),
                 ("d_grid_points", ctypes.c_void_p), ("min_depth", ctypes.c_double), ("max_depth", ctypes.c_double),
                 ("d_kfid", ctypes.c_void_p)]
+
+
+class ScanCamera(ctypes.Structure):
+    """plvs_scan_camera (include/plvs_hip.h)."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("width", ctypes.c_int), ("height", ctypes.c_int), ("near_plane", ctypes.c_float), ("far_plane", ctypes.c_float)]
+
+    @classmethod
+    def of(cls, cam, near, far):
+        """cam: dict with fx, fy, cx, cy, width, height."""
+        return cls(cam["fx"], cam["fy"], cam["cx"], cam["cy"], int(cam["width"]), int(cam["height"]), near, far)
 
 
 class TsdfChisel:
@@ -103,6 +118,42 @@ class TsdfChisel:
         _lib.check(f(self._h, _lib.np_ptr(depth), depth.shape[1], depth.shape[0], fx, fy, cx, cy, near, far,
                      _lib.np_ptr(Twc), carving_dist, ctypes.byref(n)))
         return n.value
+
+    def integrate_scan(self, depth, bgr, cam, Twc, near=0.1, far=5.0, use_carving=False, carving_dist=0.05):
+        """Projective depth + colour scan (Chisel::IntegrateDepthScanColorWithOneCameraModelBGR, Chisel.h:198-258): depth
+        [h, w] f32 (NaN = no measurement; rows may be strided), bgr [h, w, 3 or 4] u8 registered to it, cam: dict with fx,
+        fy, cx, cy, width, height (the depth camera), near / far: the frustum's planes (PointCloudMapping's min / max depth
+        distance).  Host arrays; synchronous."""
+        depth = np.asarray(depth)
+        if depth.dtype != np.float32 or depth.ndim != 2 or depth.strides[1] != 4 or depth.strides[0] < depth.shape[1] * 4:
+            depth = np.ascontiguousarray(depth, dtype=np.float32)
+        bgr = np.asarray(bgr)
+        ch = bgr.shape[2] if bgr.ndim == 3 else 0
+        if bgr.dtype != np.uint8 or bgr.strides[2] != 1 or bgr.strides[1] != ch or bgr.strides[0] < bgr.shape[1] * ch:
+            bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+        assert depth.shape == (cam["height"], cam["width"]) and bgr.shape[:2] == depth.shape
+        Twc = np.ascontiguousarray(np.asarray(Twc, dtype=np.float32)[:3, :4])
+        c = ScanCamera.of(cam, near, far)
+        f = _lib.lib.plvs_hip_tsdf_chisel_integrate_scan
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                      ctypes.POINTER(ScanCamera), ctypes.c_void_p, ctypes.c_int, ctypes.c_float]
+        _lib.check(f(self._h, ctypes.c_void_p(depth.ctypes.data), depth.strides[0], ctypes.c_void_p(bgr.ctypes.data), bgr.strides[0], ch, ctypes.byref(c),
+                     _lib.np_ptr(Twc), int(bool(use_carving)), carving_dist))
+
+    def integrate_scans_dev(self, d_depth, d_bgr, cam, d_Twc, near=0.1, far=5.0, use_carving=False, carving_dist=0.05):
+        """K scans resident in HBM in one call (plvs_hip_tsdf_chisel_integrate_scans_dev): d_depth [k, h, w] f32, d_bgr
+        [k, h, w, 3 or 4] u8, d_Twc [k, 3, 4] f32, contiguous torch tensors.  The same map as k integrate_scan calls."""
+        k, hgt, wid = d_depth.shape
+        assert d_depth.dtype == torch.float32 and d_depth.is_contiguous()
+        assert d_bgr.dtype == torch.uint8 and d_bgr.is_contiguous() and tuple(d_bgr.shape[:3]) == (k, hgt, wid)
+        assert d_Twc.dtype == torch.float32 and d_Twc.is_contiguous() and d_Twc.numel() == 12 * k
+        assert (hgt, wid) == (cam["height"], cam["width"])
+        c = ScanCamera.of(cam, near, far)
+        f = _lib.lib.plvs_hip_tsdf_chisel_integrate_scans_dev
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ScanCamera),
+                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
+        _lib.check(f(self._h, _lib.t_ptr(d_depth), _lib.t_ptr(d_bgr), int(d_bgr.shape[3]), ctypes.byref(c), _lib.t_ptr(d_Twc),
+                     k, int(bool(use_carving)), carving_dist, _lib.current_stream_ptr()))
 
     def mesh_chunks(self, chunk_ids, halo_ok=False):
         """ChunkManager::RecomputeMesh for every chunk id of the list ([n,3] ints, e.g. the 27-neighbourhood of
@@ -838,6 +889,7 @@ class PointCloudMapChisel:
         self._meshes_to_update = set()       # Chisel::meshesToUpdate
         self.all_meshes = {}                 # chunk id -> dict(vertices, normals, colors, kfids)
         self._pending = False                # clouds queued since the last _flush (their chunks are not yet marked)
+        self._depth_cam = None               # SetDepthCameraModel
 
     def InsertCloud(self, cloud_camera, Twc, max_range=None):
         """cloud_camera: dict/obj with xyz [n,3] f32, rgb [n,3] u8 (r,g,b members of
@@ -936,10 +988,34 @@ class PointCloudMapChisel:
                         self._meshes_to_update.add((int(c[0]) + dx, int(c[1]) + dy, int(c[2]) + dz))
         return self.UpdateMap()
 
+    def SetDepthCameraModel(self, fx, fy, cx, cy, width, height):
+        """src/PointCloudMapChisel.cc:63-67 (ChiselServer::SetDepthCameraInfo): the camera of InsertDepthScanColor."""
+        self._depth_cam = dict(fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy), width=int(width), height=int(height))
+
+    def InsertDepthScanColor(self, depthImage, colorImage, Twc, timestamp=0):
+        """src/PointCloudMapChisel.cc:134-189: the depth image and the BGR(A) image registered to it go through the
+        projective integrator (TsdfChisel.integrate_scan); the frustum's planes are min_depth / max_depth (:54-55), carving
+        follows use_carving.  The 27 neighbours of every updated chunk are marked for meshing (Chisel.h:233-245)."""
+        print("PointCloudMapChisel<PointT>::InsertDepthScanColor()")
+        if depthImage is None or colorImage is None or np.size(depthImage) == 0 or np.size(colorImage) == 0:
+            print("PointCloudMapChisel::InsertDepthScanColor() - ERROR: depth and/or color images are emtpy ")
+        else:
+            if self._depth_cam is None:
+                raise ValueError("SetDepthCameraModel first: the scan integrate projects through the depth camera")
+            self._flush()      # (the scan reads and changes the map: what is waiting goes in first)
+            self._tsdf.integrate_scan(depthImage, colorImage, self._depth_cam, Twc, near=self.min_depth, far=self.max_depth,
+                                      use_carving=self.use_carving, carving_dist=self.carving_dist)
+            self._mark_updated()
+        if self.use_carving:
+            print("using carving")
+
     def InsertData(self, pData):
-        """PointCloudMapInput dispatch (src/PointCloudMapChisel.cc:192-225): only the
-        point-cloud input type is handled; anything else terminates the reference."""
+        """PointCloudMapInput dispatch (src/PointCloudMapChisel.cc:192-225): point clouds and colour + depth images;
+        anything else terminates the reference."""
         t = pData.get("type", "kPointCloud")
+        if t == "kColorAndDepthImages":
+            self.InsertDepthScanColor(pData.get("imgDepth"), pData.get("imgColor"), pData["Twc"], pData.get("timestamp", 0))
+            return
         if t != "kPointCloud":
             raise SystemExit(-1)
         self.InsertCloud(pData["pPointCloud"], pData["Twc"], pData.get("maxRange", self.max_depth))
