@@ -41,6 +41,7 @@
 #include "tsdf_chisel_view.hpp"
 #include "tsdf_tiles.hpp"
 #include "tsdf_walk.hpp"
+#include "tsdf_walk_plan.hpp"
 #include "tsdf_shard.hpp"
 
 using namespace plvs;
@@ -919,8 +920,7 @@ struct plvs_tsdf_chisel {
   DevBuf<uint32_t> pa_last, pa_cnt, pa_done;
   uint32_t multi_cap = 0;
   uint32_t part_segs = kPartSegs, part_min = kPartMin;   // (plvs_hip_tsdf_chisel_set_apply_parts)
-  bool third_pass = false;                                // a 4096-entry pass behind the 1024- and the 2048-entry one (the call before needed it)
-  bool walk_small = false, walk_small_used = false;      // first-pass table of the order-free walk: 1024 entries instead of 2048
+  plvs::tsdf::WalkHistory walk;   // what the next order-free call's plan takes from the call before (tsdf_walk_plan.hpp)
   DevBuf<uint32_t> w_runkey, w_run_cnt, w_run_off, w_val0, w_val1;   // runs: per-tile regions of 2^run_r1_log2 slots
   int32_t* h_offsets = nullptr;      // pinned copy of the call's cloud offsets
   size_t h_offsets_cap = 0;
@@ -951,8 +951,6 @@ struct plvs_tsdf_chisel {
   plvs_tsdf_stats sh_stats{};
   hipStream_t side = nullptr;   // second stream for the colour chain
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool small_runs_known = false;   // the runs of the last small call (integrate_walk_acc launches the next one's colour chain on them)
-  uint32_t small_runs_last = 0, small_tiles_last = 1;
   // optional per-stage timing (HIP events on the caller's stream)
   bool profiling = false;
   hipEvent_t ev[kNumStages + 1] = {};
@@ -1039,10 +1037,10 @@ constexpr unsigned kDeferGrid = 1024;   // workgroups of the general walk over t
 // kRecStride records (the larger table's limit) in the record buffer.
 constexpr int kFastEntriesSmall = 1024, kFastEntries = 2048, kFastEntriesBig = 4096;
 constexpr uint32_t kRecStride = kFastEntriesBig * 7 / 8;
-constexpr uint32_t kSmallCallTiles = 320;
-constexpr uint32_t kPredictTiles = 4096;   // calls up to this size (~25 key frames) launch their colour chain on the previous call's sizes
-constexpr unsigned kListGrid = 512;      // workgroups of the large-table pass over the first list (it loops)
 static_assert(kRecStride == (uint32_t)kWalkLimit, "a tile's record region holds a flush of the largest table");
+static_assert(kSortSmallRuns == kSmallRuns && kSortMediumRuns <= kMediumRuns && kCollectPartRuns == kCollectPart &&
+                  kRowsPerChunk == (uint32_t)kSlabs && kTileSegments == (uint32_t)kWalkChunks && kSegmentBlock == (uint32_t)kSegSpan,
+              "tsdf_walk_plan.hpp plans for the kernels' sizes");
 const char* const kWalkStageNames[kWalkStages] = {"walk_tiles", "sort_segments", "apply_chunks", "fold_colours"};
 
 // The host's wait for a publish_counters launch that carried sequence number `seq` on stream q: it polls the word for up to
@@ -1119,11 +1117,11 @@ static int wait_published(plvs_tsdf_chisel* h, uint32_t seq, hipStream_t q, int 
   return PLVS_OK;
 }
 
-static int read_walk_counters(plvs_tsdf_chisel* h, hipStream_t s, int size_class = 0) {
+static int read_walk_counters(plvs_tsdf_chisel* h, hipStream_t s, int size_class = 0, int kind = 0) {
   const uint32_t seq = ++h->seq_next;
   hipLaunchKernelGGL(publish_counters, dim3(1), dim3(64), 0, s, h->d_wctr, h->d_ctr, h->h_wctr, h->h_ctr, h->h_seq, seq);
   PLVS_KERNEL_CHECK();
-  return wait_published(h, seq, s, 0, size_class);
+  return wait_published(h, seq, s, kind, size_class);
 }
 
 static int walk_fail(plvs_tsdf_chisel* h, uint32_t err) {
@@ -1156,14 +1154,11 @@ static int sort_runs(plvs_tsdf_chisel* h, uint32_t D, uint32_t ntiles, int num_c
   RunGuard g = guard ? *guard : RunGuard{0xFFFFFFFFu, nullptr, nullptr, 0, nullptr, nullptr, 0u, nullptr, 0u};
   g.zero = zero_words ? h->scratch.p : nullptr;
   g.zero_words = (uint32_t)zero_words;
-  hipLaunchKernelGGL(compact_runs, dim3(ceil_div(ntiles, 4) + (guard ? (guard->pad ? std::min<unsigned>(64u, ceil_div((size_t)D, 1024)) : 1u) : 0u)),
+  hipLaunchKernelGGL(compact_runs, dim3(ceil_div(ntiles, 4) + (guard ? std::min<unsigned>(64u, ceil_div((size_t)D, 1024)) : 0u)),
                      dim3(256), 0, s, h->w_runkey.p, h->w_run_cnt.p, h->w_run_off.p, ntiles, h->run_r1_log2, h->dkey0.p,
                      h->w_val0.p, g);
   bool second = false;
-  if (guard && !guard->pad)   // the bound is loose: the sort takes the number of pairs from the device
-    PLVS_HIP_TRY(radix_sort_pairs_bound(h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, D, guard->total, 0, key_bits,
-                                        h->scratch.p, s, &second));
-  else if (zero_words)
+  if (zero_words)
     PLVS_HIP_TRY(radix_sort_pairs_zeroed(h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, D, 0, key_bits, h->scratch.p, s,
                                          &second));
   else
@@ -1194,533 +1189,326 @@ static int ensure_part_acc(plvs_tsdf_chisel* h, uint32_t chunks) {
   return PLVS_OK;
 }
 
-// Order-free mode: walk_tiles -> segment sort -> apply_chunks (+ the colour fold when the call met voxels
-// whose colour weight is below 254).
-// gsrc (plvs_hip_tsdf_chisel_integrate_depth_batch_dev): the clouds are depth images — tiles are 32 x 16 blocks of grid
-// pixels (GridSrc, tsdf_walk.hpp), d_xyz is null, d_rgb = the colour images, d_kfid = one id per image, offsets =
-// nclouds + 1 zeros (nothing reads them).
-static int integrate_walk_acc(plvs_tsdf_chisel* h, const float* d_xyz, const uint8_t* d_rgb, const uint32_t* d_kfid,
-                              int n, int nclouds, const int32_t* offsets, const float* d_Twc, hipStream_t s,
-                              const GridSrc* gsrc = nullptr) {
-  const int max_chunks = h->prm.max_chunks;
-  const GridSrc grid = gsrc ? *gsrc : GridSrc{};
-  // tiles: 512 consecutive points of one cloud (tsdf_directory.hpp)
+// The walk's scratch (integrate_walk_acc, shard_walk): every tile owns kRecStride records, kWalkChunks segments and
+// 2^run_r1_log2 run slots; what a tile has beyond its own goes to a spill area behind the tiles' regions.  A walk that runs
+// out of any of them sets kErrScratch and leaves the map untouched: the regions grow and the call is repeated.
+struct WalkScratch {
+  size_t rec_own, seg_own, rec_spill, seg_spill;
+};
+static WalkScratch walk_scratch(const plvs_tsdf_chisel* h, uint32_t ntiles) {
+  WalkScratch w;
+  w.rec_own = (size_t)ntiles * kRecStride;
+  w.seg_own = (size_t)ntiles * kWalkChunks;
+  w.rec_spill = std::max<size_t>(h->w_rec.cap > w.rec_own ? h->w_rec.cap - w.rec_own : 0, (size_t)1 << 16);
+  w.seg_spill = std::max<size_t>(h->w_seg.cap / 2 > w.seg_own ? h->w_seg.cap / 2 - w.seg_own : 0, (size_t)1 << 12);
+  return w;
+}
+static int reserve_walk_scratch(plvs_tsdf_chisel* h, uint32_t ntiles, const WalkScratch& w) {
+  // (sized by the call's tiles, and the largest buffers of the handle — 64 B of masks per run slot, hundreds of MB: a
+  // hipFree + hipMalloc of that size costs milliseconds, and a stream of calls of varying length would pay it whenever a
+  // call is a little longer than any before; they grow to TWICE what a call needs instead)
+  if (h->w_rec.cap < w.rec_own + w.rec_spill) PLVS_HIP_TRY(h->w_rec.reserve(2 * w.rec_own + w.rec_spill));
+  if (h->w_seg.cap < 2 * (w.seg_own + w.seg_spill)) PLVS_HIP_TRY(h->w_seg.reserve(2 * (2 * w.seg_own + w.seg_spill)));
+  PLVS_HIP_TRY(h->w_sorted_seg.reserve(h->w_seg.cap));
+  const size_t run_slots = (size_t)ntiles << h->run_r1_log2;
+  if (h->w_runkey.cap < run_slots) {
+    PLVS_HIP_TRY(h->w_runkey.reserve(2 * run_slots));
+    PLVS_HIP_TRY(h->w_masks.reserve(2 * run_slots * kMaskWords));
+  }
+  PLVS_HIP_TRY(h->w_masks.reserve(run_slots * kMaskWords));
+  return PLVS_OK;
+}
+static AccOut walk_out(const plvs_tsdf_chisel* h, const WalkScratch& w, uint32_t* chunk_nseg) {
+  return AccOut{h->w_rec.p, (uint32_t)std::min<size_t>(w.rec_own + w.rec_spill, 0xFFFFFFFFu), h->w_seg.p,
+                (uint32_t)std::min<size_t>(w.seg_own + w.seg_spill, 0xFFFFFFFFu), h->w_seg_cnt.p, h->w_tile_visits.p, chunk_nseg};
+}
+// kErrScratch: room for twice what the walk asked for (h_wctr).  false: the tiles' run slots would leave the index range.
+static bool grow_walk_scratch(plvs_tsdf_chisel* h, uint32_t ntiles, WalkScratch& w) {
+  w.rec_spill = std::max<size_t>(w.rec_spill, (size_t)h->h_wctr->rec_top * 2);
+  w.seg_spill = std::max<size_t>(w.seg_spill, (size_t)h->h_wctr->seg_top * 2);
+  while ((1u << h->run_r1_log2) < h->h_wctr->run_need) ++h->run_r1_log2;
+  return ((size_t)ntiles << h->run_r1_log2) < 0xFFFFFFFFull;
+}
+
+// ---- Order-free mode: walk_tiles -> segment sort -> apply_chunks (+ the colour fold when the call met voxels whose colour
+// weight is below 254).  The policy — which passes, which colour chain, which stream — is plan_walk_call's
+// (tsdf_walk_plan.hpp); the functions below launch what a plan says.
+
+// One attempt of a call: the caller's inputs and what its stages share.
+struct WalkCall {
+  const float* d_xyz;
+  const uint8_t* d_rgb;
+  const uint32_t* d_kfid;
+  int n, nclouds;
+  uint32_t ntiles;
+  int max_chunks;
+  const GridSrc* gsrc;     // depth-image entry: the host's copy of the grid description (null: point clouds) ...
+  const GridSrc* d_grid;   //   ... and the device's, behind the offsets
+  size_t seg_slots;        // the tiles' segment slots and the spill area behind them
+  AccOut out;
+  RunOut runs;
+  const uint32_t* last_count;   // (device) tiles the last lean pass left to walk_tiles
+  uint32_t collect_seq;         // kChainCollected: the sequence number rows_place publishes the walk's counters under
+};
+
+static hipError_t stage_mark(plvs_tsdf_chisel* h, int i, hipStream_t q) {
+  return h->profiling ? hipEventRecord(h->ev[i], q) : hipSuccess;
+}
+
+template <int E>
+static void launch_walk_fast(plvs_tsdf_chisel* h, const WalkCall& c, const WalkPass& pass, hipStream_t s) {
+  uint32_t* const counts[3] = {&h->d_wctr->ndeferred, &h->d_wctr->ndeferred2, &h->d_wctr->ndeferred3};
+  const uint32_t* const list = pass.src < 0 ? nullptr : h->w_deferred.p + (size_t)pass.src * c.ntiles;
+  const uint32_t* const nlist = pass.src < 0 ? nullptr : counts[pass.src];
+  const auto kernel = c.d_grid ? walk_fast<E, true> : walk_fast<E, false>;
+  hipLaunchKernelGGL(kernel, dim3(pass.grid), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, c.d_xyz, c.n, h->offsets.p,
+                     c.nclouds, h->poses.p, h->dir, &h->d_ctr->num_chunks, h->d_wctr, h->rgbw, (const uint32_t*)nullptr, c.out,
+                     c.runs, TileMap{1u, 0u, 1u}, kRecStride, list, nlist, h->w_deferred.p + (size_t)pass.dst * c.ntiles,
+                     counts[pass.dst], c.d_grid);
+}
+
+// The common case of a tile alone in a lean kernel; what the passes defer (tiles over several clouds, table overflows) is
+// walked by the general kernel from the last pass's list.
+static void launch_walk_passes(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkCall& c, hipStream_t s) {
+  for (int i = 0; i < plan.npasses; ++i) {
+    const WalkPass& pass = plan.pass[i];
+    if (pass.entries == kFastEntriesSmall) launch_walk_fast<kFastEntriesSmall>(h, c, pass, s);
+    else if (pass.entries == kFastEntries) launch_walk_fast<kFastEntries>(h, c, pass, s);
+    else launch_walk_fast<kFastEntriesBig>(h, c, pass, s);
+  }
+  hipLaunchKernelGGL((walk_tiles<true, true>), dim3(kDeferGrid), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, c.d_xyz,
+                     c.n, h->offsets.p, c.nclouds, h->poses.p, h->dir, &h->d_ctr->num_chunks, h->d_wctr, h->rgbw,
+                     (const uint32_t*)nullptr, c.out, c.runs, TileMap{1u, 0u, 1u}, c.ntiles,
+                     (const uint32_t*)(h->w_deferred.p + (size_t)plan.last_list * c.ntiles), c.last_count, kRecStride,
+                     plan.pieces, c.d_grid);
+}
+
+// Segment sort and apply stage on stream q; in front of them, for a call whose runs may be collected chunk by chunk, the
+// colour side's counting stages: short kernels that would otherwise start beside the apply stage's first thousand
+// workgroups and wait for their slots (40 us each, measured).
+static int segments_and_apply(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkCall& c, hipStream_t q) {
+  hipLaunchKernelGGL(seg_scan, dim3(1), dim3(1024), 0, q, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p,
+                     h->updated.p, h->w_active_off.p, h->d_wctr, &h->d_ctr->num_chunks, c.max_chunks,
+                     h->w_tile_visits.p, h->w_run_cnt.p, c.ntiles, h->w_part_off.p, h->w_multi_idx.p, h->multi_cap,
+                     h->part_segs, h->part_min, plan.collect_ready ? h->w_active_idx.p : (uint32_t*)nullptr);
+  if (plan.collect_ready) {
+    const bool queued = plan.chain == kChainCollected;   // (rows_place then publishes the walk's counters for the host)
+    PLVS_HIP_TRY(hipStreamWaitEvent(q, h->ev_zero, 0));
+    hipLaunchKernelGGL(runs_count, dim3(plan.collect_blocks), dim3(kSegSpan), 0, q, h->w_seg.p, h->w_rseg.p, c.ntiles, h->w_seg_cnt.p,
+                       h->w_active_idx.p, plan.collect_rows, plan.collect_blocks, h->w_run_matrix.p, h->w_rpre.p, h->d_wctr, c.last_count);
+    hipLaunchKernelGGL(runs_rowscan, dim3(std::min<uint32_t>(ceil_div(plan.collect_rows, 4), 1024u)), dim3(256), 0, q,
+                       h->w_run_matrix.p, plan.collect_rows, plan.collect_blocks, h->d_wctr, h->w_item_cnt.p);
+    hipLaunchKernelGGL(rows_place, dim3(1), dim3(1024), 0, q, h->w_item_cnt.p, plan.collect_rows, plan.collect_bound,
+                       (uint32_t)std::min<size_t>(plan.parts_cap, 0xFFFFFFFFu), h->d_wctr,
+                       h->w_item_base.p, h->w_item_part0.p, h->w_part_item.p, reinterpret_cast<const uint32_t*>(h->d_ctr),
+                       reinterpret_cast<uint32_t*>(h->h_wctr), reinterpret_cast<uint32_t*>(h->h_ctr),
+                       (uint32_t)(sizeof(Counters) / sizeof(uint32_t)), queued ? h->h_seq : (uint32_t*)nullptr,
+                       queued ? c.collect_seq : 0u);
+    PLVS_HIP_TRY(hipEventRecord(h->ev_seg, q));
+  }
+  // (a long call: 4096 descriptor slots — 64 tiles — per workgroup instead of 1024: a quarter of the workgroups, and what
+  // the kernel waits for is their atomics on the counters of a hundred-odd chunks)
+  if (plan.size_class == 2)
+    hipLaunchKernelGGL((seg_pass<true, kSegSpanLong>), dim3(ceil_div(c.seg_slots, kSegSpanLong)), dim3(256), 0, q, h->w_seg.p,
+                       c.out.seg_cap, c.ntiles, h->w_seg_cnt.p, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p,
+                       h->w_sorted_seg.p, h->d_wctr);
+  else
+    hipLaunchKernelGGL(seg_pass<true>, dim3(ceil_div(c.seg_slots, kSegSpan)), dim3(256), 0, q, h->w_seg.p, c.out.seg_cap,
+                       c.ntiles, h->w_seg_cnt.p, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p, h->w_sorted_seg.p,
+                       h->d_wctr);
+  PLVS_HIP_TRY(stage_mark(h, 2, q));
+  hipLaunchKernelGGL((apply_chunks<false, false>), dim3(4096), dim3(kApplyThreads), 0, q, h->w_sorted_seg.p, h->updated.p,
+                     h->w_active_off.p, h->w_part_off.p, h->w_multi_idx.p, h->part_segs,
+                     PartAcc{h->pa_wuu.p, h->pa_w.p, h->pa_last.p, h->pa_cnt.p, h->pa_done.p}, h->w_rec.p,
+                     1.0 / (double)h->scale_u, 1.0 / (double)h->scale_w, c.d_kfid, h->sdf, h->weight, h->kfid, h->d_wctr,
+                     EmitOut{}, c.gsrc ? c.gsrc->key_bits : 0u);
+  PLVS_KERNEL_CHECK();
+  PLVS_HIP_TRY(stage_mark(h, 3, q));
+  return PLVS_OK;
+}
+
+// The colour fold: the truncating u8 mean is order dependent -> through the sorted runs of the voxels whose colour weight
+// is below 254 (D of them, or a bound: `skip` then says whether the chain in front held).
+static int launch_fold(plvs_tsdf_chisel* h, const WalkCall& c, uint32_t D, const uint32_t* skeys, const uint32_t* sval,
+                       const uint32_t* skip, hipStream_t q) {
+  const RunSrc rsrc{h->w_masks.p, (uint32_t)kMaskWords, h->run_r1_log2, TileMap{1u, 0u}, h->offsets.p, c.nclouds,
+                    reinterpret_cast<const uint32_t*>(h->offsets.p) + 2 * ((size_t)c.nclouds + 1)};
+  const auto kernel = c.gsrc ? fold_colours_masks<true> : fold_colours_masks<false>;
+  hipLaunchKernelGGL(kernel, dim3(std::min<size_t>(ceil_div(D, kFoldWaves), 8192)), dim3(64 * kFoldWaves), 0, q, skeys, sval,
+                     &h->d_wctr[1].num_desc, rsrc, h->heads.p, c.d_rgb, h->rgbw, &h->d_wctr[1].num_heads, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr, skip, c.gsrc ? *c.gsrc : GridSrc{});
+  PLVS_KERNEL_CHECK();
+  return PLVS_OK;
+}
+
+// One workgroup, one launch: the runs listed, sorted and their voxels' first runs found.
+template <int BITS>
+static void launch_sort_medium(plvs_tsdf_chisel* h, uint32_t ntiles, int passes, const RunGuard* guard, hipStream_t q) {
+  hipLaunchKernelGGL(sort_runs_medium<BITS>, dim3(1), dim3(1024), 0, q, h->w_runkey.p, h->w_run_cnt.p, ntiles, h->run_r1_log2,
+                     h->d_wctr + 1, h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, h->w_run_off.p, h->heads.p, passes,
+                     guard ? guard->limit : 0xFFFFFFFFu, &h->d_ctr->num_chunks, guard ? guard->chunk_limit : 0,
+                     guard ? guard->skip : (uint32_t*)nullptr);
+}
+
+// The sorting colour chain for D runs in a map of `chunks` chunks — or bounds on both (guard) — on stream q.  Where
+// sort_needs_scan(D, ntiles), the caller has queued the scan of the run counts in front of it.
+static int colour_chain(plvs_tsdf_chisel* h, const WalkCall& c, uint32_t D, int chunks, const RunGuard* guard, hipStream_t q) {
+  const uint32_t* skeys = h->dkey0.p;
+  const uint32_t* sval = h->w_val0.p;
+  switch (sort_kind(D, c.ntiles)) {
+    case kSortSmall:
+      hipLaunchKernelGGL(sort_runs_small, dim3(1), dim3(1024), 0, q, h->w_runkey.p, h->w_run_cnt.p, c.ntiles,
+                         h->run_r1_log2, h->d_wctr + 1, h->dkey0.p, h->w_val0.p, h->heads.p, guard ? guard->skip : (uint32_t*)nullptr);
+      break;
+    case kSortMedium: {
+      PLVS_HIP_TRY(h->dkey0.reserve(D));
+      PLVS_HIP_TRY(h->dkey1.reserve(D));
+      PLVS_HIP_TRY(h->w_val0.reserve(D));
+      PLVS_HIP_TRY(h->w_val1.reserve(D));
+      PLVS_HIP_TRY(h->heads.reserve(D));
+      int key_bits = 12;
+      while ((1ll << (key_bits - 12)) < (long long)chunks) ++key_bits;
+      const bool ten = key_bits <= 20;   // (two passes of ten bits instead of three of eight)
+      const int passes = ten ? 2 : (key_bits + 7) / 8;
+      if (ten) launch_sort_medium<10>(h, c.ntiles, passes, guard, q);
+      else launch_sort_medium<8>(h, c.ntiles, passes, guard, q);
+      skeys = (passes & 1) ? h->dkey1.p : h->dkey0.p;
+      sval = (passes & 1) ? h->w_val1.p : h->w_val0.p;
+      break;
+    }
+    case kSortGeneral: {
+      int rc = sort_runs(h, D, c.ntiles, chunks, q, &skeys, &sval, guard);
+      if (rc != PLVS_OK) return rc;
+      PLVS_HIP_TRY(h->heads.reserve(D));
+      PLVS_HIP_TRY(h->w_dummy.reserve((size_t)c.max_chunks + 1));
+      hipLaunchKernelGGL(voxel_heads, dim3(ceil_div(D, 256 * kHeadTiles)), dim3(256), 0, q, skeys, D, h->heads.p, h->w_dummy.p,
+                         h->d_wctr + 1, guard ? (const uint32_t*)&h->d_wctr[1].num_desc : (const uint32_t*)nullptr);
+      break;
+    }
+  }
+  return launch_fold(h, c, D, skeys, sval, guard ? (const uint32_t*)guard->skip : (const uint32_t*)nullptr, q);
+}
+
+// The runs of a long call whose tiles all went through walk_fast, chunk by chunk (runs_count ... parts_place): behind the
+// list of the updated chunks (ev_seg), no pass that sorts all runs.  What it cannot take sets `skip` — the fold then
+// leaves at once and the sorting chain runs once the call's counters are read (as for a predicted chain whose bounds
+// did not hold).
+static int collect_chain(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkCall& c, uint32_t D, hipStream_t q) {
+  const uint32_t rows = plan.collect_rows, blocks = plan.collect_blocks;
+  PLVS_HIP_TRY(hipStreamWaitEvent(q, h->ev_seg, 0));
+  hipLaunchKernelGGL(runs_scatter, dim3(blocks * (kSegSpan / 256)), dim3(256), 0, q, h->w_seg.p, h->w_rseg.p, c.ntiles, h->w_seg_cnt.p,
+                     h->w_active_idx.p, rows, blocks, h->w_run_matrix.p, h->w_rpre.p, h->w_item_base.p, h->d_wctr, h->w_val0.p);
+  const unsigned part_grid = (unsigned)std::min<size_t>(plan.parts_cap, 4096);
+  hipLaunchKernelGGL(parts_count, dim3(part_grid), dim3(256), 0, q, h->w_part_item.p, h->w_item_part0.p, h->w_item_base.p,
+                     h->w_item_cnt.p, h->w_runkey.p, h->d_wctr, h->w_val0.p, h->dkey0.p, h->w_phist.p);
+  hipLaunchKernelGGL(rows_heads, dim3(std::min<uint32_t>(ceil_div(rows, 4), 1024u)), dim3(256), 0, q, h->w_item_part0.p,
+                     h->w_item_cnt.p, h->w_phist.p, h->d_wctr, rows, h->w_row_heads.p, h->w_row_tot.p);
+  hipLaunchKernelGGL(parts_place, dim3(part_grid), dim3(512), 0, q, h->w_part_item.p, h->w_item_part0.p, h->w_item_base.p,
+                     h->w_item_cnt.p, h->w_phist.p, h->d_wctr, h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, h->heads.p,
+                     h->w_row_heads.p, rows, h->w_row_tot.p);
+  return launch_fold(h, c, D, h->dkey1.p, h->w_val1.p, &h->d_wctr[1].skip, q);
+}
+
+// The collected chain's buffers, and its run matrix zeroed on the side stream while the walk runs (runs_count writes the
+// cells that hold runs, and waits for ev_zero: long over by then).
+static int reserve_collect(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkScratch& w, int max_chunks) {
+  const uint32_t rows = plan.collect_rows;
+  PLVS_HIP_TRY(h->w_rseg.reserve(h->w_seg.cap));
+  PLVS_HIP_TRY(h->w_rpre.reserve(w.seg_own));
+  PLVS_HIP_TRY(h->w_active_idx.reserve((size_t)max_chunks));
+  PLVS_HIP_TRY(h->w_run_matrix.reserve((size_t)rows * plan.collect_blocks));
+  PLVS_HIP_TRY(h->w_item_base.reserve(rows));
+  PLVS_HIP_TRY(h->w_item_cnt.reserve(rows));
+  PLVS_HIP_TRY(h->w_item_part0.reserve(rows));
+  PLVS_HIP_TRY(h->w_row_heads.reserve(rows));
+  PLVS_HIP_TRY(h->w_row_tot.reserve((size_t)rows * kSlabVox));
+  PLVS_HIP_TRY(h->dkey0.reserve(plan.collect_bound));
+  PLVS_HIP_TRY(h->dkey1.reserve(plan.collect_bound));
+  PLVS_HIP_TRY(h->w_val0.reserve(plan.collect_bound));
+  PLVS_HIP_TRY(h->w_val1.reserve(plan.collect_bound));
+  PLVS_HIP_TRY(h->heads.reserve(plan.collect_bound));
+  PLVS_HIP_TRY(h->w_part_item.reserve(plan.parts_cap));
+  PLVS_HIP_TRY(h->w_phist.reserve(plan.parts_cap * kSlabVox));
+  PLVS_HIP_TRY(hipMemsetAsync(h->w_run_matrix.p, 0, (size_t)rows * plan.collect_blocks * sizeof(uint32_t), h->side));
+  PLVS_HIP_TRY(hipEventRecord(h->ev_zero, h->side));
+  return PLVS_OK;
+}
+
+// The call's offsets, tile table, first point and cloud of every tile (the colour fold would otherwise search the cloud
+// table once per RUN; the walk's tiles read both instead of searching: tile_span_tables) and, for depth images, the grid
+// description, in pinned memory: walk_prologue copies them to the device.  Tiles: 512 consecutive points of one cloud
+// (tsdf_directory.hpp), or 32 x 16 blocks of grid pixels.
+constexpr size_t kGridWords = (sizeof(GridSrc) + 3) / 4;
+static_assert(sizeof(GridSrc) % 4 == 0 && alignof(GridSrc) <= 8, "GridSrc travels as words behind the offsets");
+static int fill_call_tables(plvs_tsdf_chisel* h, const int32_t* offsets, int nclouds, const GridSrc* gsrc, uint32_t* ntiles_out,
+                            size_t* table_words_out) {
   size_t tiles_of_call = 0;
   for (int c = 0; c < nclouds; ++c) tiles_of_call += ((size_t)(offsets[c + 1] - offsets[c]) + kWalkRays - 1) / kWalkRays;
-  const size_t grid_tiles = gsrc ? (size_t)nclouds * grid.ntx * grid.nty : 0;
+  const size_t grid_tiles = gsrc ? (size_t)nclouds * gsrc->ntx * gsrc->nty : 0;
   if (gsrc) PLVS_REQUIRE(grid_tiles < 0x7FFFFFFFull, "too many images in one call");
-  constexpr size_t kGridWords = (sizeof(GridSrc) + 3) / 4;
-  static_assert(sizeof(GridSrc) % 4 == 0 && alignof(GridSrc) <= 8, "GridSrc travels as words behind the offsets");
   const size_t table_words = 2 * ((size_t)nclouds + 1) + 2 * tiles_of_call + (gsrc ? kGridWords : 0);
-  if (h->h_offsets_cap < table_words) {   // pinned copy of the offsets + tile table + tile starts: the prologue kernel reads it
+  if (h->h_offsets_cap < table_words) {
     if (h->h_offsets) (void)hipHostFree(h->h_offsets);
     h->h_offsets = nullptr;
     h->h_offsets_cap = 0;
     PLVS_HIP_TRY(hipHostMalloc((void**)&h->h_offsets, (2 * table_words + 64) * sizeof(int32_t)));
     h->h_offsets_cap = 2 * table_words + 64;
   }
-  const uint32_t ntiles = gsrc ? (uint32_t)grid_tiles : plvs::tsdf::fill_tile_table(offsets, nclouds, h->h_offsets, kWalkRays);
-  if (gsrc) {   // (zeros: the table is unused; the walk's copy of the grid description travels behind it)
-    plvs::tsdf::fill_tile_table(offsets, nclouds, h->h_offsets, kWalkRays);
-    memcpy(h->h_offsets + 2 * ((size_t)nclouds + 1), &grid, sizeof(GridSrc));
-  }
-  {   // the first point of every tile (the colour fold would otherwise search the cloud table once per RUN)
-    int32_t* tf = h->h_offsets + 2 * ((size_t)nclouds + 1);
-    size_t t = 0;
-    for (int c = 0; c < nclouds; ++c)
-      for (int32_t p = offsets[c]; p < offsets[c + 1]; p += kWalkRays) {
-        tf[ntiles + t] = c;   // (and its cloud: the walk's tiles read both instead of searching: tile_span_tables)
-        tf[t++] = p;
-      }
-  }
+  // (depth images: zeros, the table is unused; the walk's copy of the grid description travels behind it)
+  const uint32_t cloud_tiles = plvs::tsdf::fill_tile_table(offsets, nclouds, h->h_offsets, kWalkRays);
+  const uint32_t ntiles = gsrc ? (uint32_t)grid_tiles : cloud_tiles;
+  int32_t* tf = h->h_offsets + 2 * ((size_t)nclouds + 1);
+  if (gsrc) memcpy(tf, gsrc, sizeof(GridSrc));
+  size_t t = 0;
+  for (int c = 0; c < nclouds; ++c)
+    for (int32_t p = offsets[c]; p < offsets[c + 1]; p += kWalkRays) {
+      tf[ntiles + t] = c;
+      tf[t++] = p;
+    }
+  *ntiles_out = ntiles;
+  *table_words_out = table_words;
+  return PLVS_OK;
+}
+
+// What every attempt of a call of ntiles tiles needs, whatever its plan.
+static int reserve_call(plvs_tsdf_chisel* h, uint32_t ntiles, size_t table_words) {
+  const size_t max_chunks = (size_t)h->prm.max_chunks;
   PLVS_HIP_TRY(h->offsets.reserve(table_words));
   PLVS_HIP_TRY(h->tile_state.reserve((size_t)ntiles + 1));
-  PLVS_HIP_TRY(h->w_chunk_nseg.reserve((size_t)max_chunks));
-  PLVS_HIP_TRY(h->w_chunk_off.reserve((size_t)max_chunks + 1));
-  PLVS_HIP_TRY(h->w_chunk_fill.reserve((size_t)max_chunks));
-  PLVS_HIP_TRY(h->w_active_off.reserve((size_t)max_chunks + 1));
-  PLVS_HIP_TRY(h->updated.reserve((size_t)max_chunks + 1));
+  PLVS_HIP_TRY(h->w_chunk_nseg.reserve(max_chunks));
+  PLVS_HIP_TRY(h->w_chunk_off.reserve(max_chunks + 1));
+  PLVS_HIP_TRY(h->w_chunk_fill.reserve(max_chunks));
+  PLVS_HIP_TRY(h->w_active_off.reserve(max_chunks + 1));
+  PLVS_HIP_TRY(h->updated.reserve(max_chunks + 1));
   PLVS_HIP_TRY(h->w_seg_cnt.reserve(ntiles));
   PLVS_HIP_TRY(h->w_tile_visits.reserve(ntiles));
   PLVS_HIP_TRY(h->w_deferred.reserve(3 * (size_t)ntiles));   // (three lists: one behind each lean pass)
-  // every tile owns kRecStride records / kWalkChunks segments; the spill area behind them grows on demand
-  const size_t rec_own = (size_t)ntiles * kRecStride, seg_own = (size_t)ntiles * kWalkChunks;
-  if (rec_own + (1 << 16) >= 0xFFFFFFFFull) {
-    plvs::set_error("tsdf_chisel integrate: %d points in one call exceed the record index range (split the batch)", n);
-    return PLVS_ERR_CAPACITY;
-  }
-  size_t rec_spill = std::max<size_t>(h->w_rec.cap > rec_own ? h->w_rec.cap - rec_own : 0, (size_t)1 << 16);
-  size_t seg_spill = std::max<size_t>(h->w_seg.cap / 2 > seg_own ? h->w_seg.cap / 2 - seg_own : 0, (size_t)1 << 12);
   PLVS_HIP_TRY(h->w_run_cnt.reserve(ntiles));
-  PLVS_HIP_TRY(h->w_part_off.reserve((size_t)max_chunks + 1));
-  PLVS_HIP_TRY(h->w_multi_idx.reserve((size_t)max_chunks + 1));
-  {
-    int rc = ensure_part_acc(h, std::min<uint32_t>((uint32_t)max_chunks, 64u));
-    if (rc != PLVS_OK) return rc;
-  }
+  PLVS_HIP_TRY(h->w_part_off.reserve(max_chunks + 1));
+  PLVS_HIP_TRY(h->w_multi_idx.reserve(max_chunks + 1));
+  int rc = ensure_part_acc(h, std::min<uint32_t>((uint32_t)max_chunks, 64u));
+  if (rc != PLVS_OK) return rc;
   PLVS_HIP_TRY(h->dkey0.reserve(kSmallRuns));
   PLVS_HIP_TRY(h->w_val0.reserve(kSmallRuns));
   PLVS_HIP_TRY(h->heads.reserve(kSmallRuns));
   PLVS_HIP_TRY(h->w_run_off.reserve((size_t)ntiles + 1));
   PLVS_HIP_TRY(h->scratch.reserve(scan_scratch_words(ntiles)));
-  h->stage_set = 1;
-  const int size_class = ntiles <= kSmallCallTiles ? 0 : (ntiles <= kPredictTiles ? 1 : 2);
-  const int chunks_before = h->num_chunks;
-  timespec trace_t0;   // (developer trace: the call's time on the host's clock)
-  clock_gettime(CLOCK_MONOTONIC, &trace_t0);
-#define STAGE_MARK(i) \
-  do { if (h->profiling) PLVS_HIP_TRY(hipEventRecord(h->ev[i], s)); } while (0)
-  for (int attempt = 0;; ++attempt) {
-    // (the per-tile regions are sized by the call's tiles: a stream of calls of varying length would otherwise re-allocate
-    // these — the largest buffers of the handle, hundreds of MB: a hipFree + hipMalloc of that size costs milliseconds —
-    // every time a call is a little longer than any before; they grow to TWICE what a call needs instead)
-    if (h->w_rec.cap < rec_own + rec_spill) PLVS_HIP_TRY(h->w_rec.reserve(2 * rec_own + rec_spill));
-    if (h->w_seg.cap < 2 * (seg_own + seg_spill)) PLVS_HIP_TRY(h->w_seg.reserve(2 * (2 * seg_own + seg_spill)));
-    PLVS_HIP_TRY(h->w_sorted_seg.reserve(h->w_seg.cap));
-    // (a long call's runs may be collected chunk by chunk instead of sorted: collect_chain, below)
-    static const int collect_mode = plvs::env_int("PLVS_TSDF_COLLECT", 1, 0, 2);   // (developer switch: 0 never, 2 every call — tests)
-    // (the colour chain of this attempt — the reasons are where the chains are queued, below: `predicted` = on the sizes of
-    // the call before, general chain; a long call over new ground: collected)
-    const size_t expect_runs = h->small_runs_known
-        ? (size_t)((double)h->small_runs_last * (double)ntiles / (double)std::max(1u, h->small_tiles_last)) : ~(size_t)0;
-    constexpr size_t kPredictRuns = 200000;
-    constexpr uint32_t kCollectMinRuns = 65536;
-    static const bool predict_long = plvs::env_int("PLVS_TSDF_PREDICT_LONG", 0, 0, 1) != 0;   // (developer switch)
-    const bool predicted = h->small_runs_known && attempt == 0 && collect_mode != 2 &&
-                           (predict_long || ntiles <= kPredictTiles || (expect_runs <= kPredictRuns && collect_mode == 0));
-    // (with the collected chain a long call is never `predicted`: that chain is queued without the call's counts just as
-    // well, and the few runs of a saturated map's rim cost it seven short kernels instead of the sort's ten — steady state
-    // 0.631 -> 0.618 ms)
-    const bool collect_ready = collect_mode != 0 && (ntiles > kPredictTiles || collect_mode == 2) && !predicted;
-    // (rows of the run matrix: twice the chunks the call before updated — more than that and the general chain takes over)
-    // (a power of two: the matrix is re-allocated when a stream's calls update twice the chunks, not a few more each time)
-    size_t collect_row_chunks = 256;
-    while (collect_row_chunks < 2 * (size_t)h->last_updated + 64) collect_row_chunks *= 2;
-    // (developer switch, tests: at most this many chunks' rows — calls that update more repeat their chain, the general one)
-    static const int max_row_chunks = plvs::env_int("PLVS_TSDF_COLLECT_MAX_ROWS", 0, 0, 1 << 20);
-    if (max_row_chunks > 0) collect_row_chunks = std::min<size_t>(collect_row_chunks, (size_t)max_row_chunks);
-    const uint32_t collect_rows = (uint32_t)std::min<size_t>((size_t)max_chunks, collect_row_chunks) * kSlabs;
-    const uint32_t collect_blocks = (uint32_t)ceil_div(seg_own, kSegSpan);
-    // (the most runs its buffers hold: four times the call before scaled to this call's tiles — the stream's counts go 4.5 M,
-    // 1.4 M, 1.6 M, 1.1 M, 2.6 M —, 8 M at least, never more than the tiles' run slots)
-    const uint32_t collect_bound = (uint32_t)std::min<size_t>(
-        (size_t)ntiles << h->run_r1_log2,
-        std::max<size_t>((size_t)8 << 20, h->small_runs_known ? (size_t)(4.0 * (double)h->small_runs_last * (double)ntiles /
-                                                                         (double)std::max(1u, h->small_tiles_last)) : 0));
-    if (collect_ready) {
-      PLVS_HIP_TRY(h->w_rseg.reserve(h->w_seg.cap));
-      PLVS_HIP_TRY(h->w_rpre.reserve(seg_own));
-      PLVS_HIP_TRY(h->w_active_idx.reserve((size_t)max_chunks));
-      PLVS_HIP_TRY(h->w_run_matrix.reserve((size_t)collect_rows * collect_blocks));
-      PLVS_HIP_TRY(h->w_item_base.reserve(collect_rows));
-      PLVS_HIP_TRY(h->w_item_cnt.reserve(collect_rows));
-      PLVS_HIP_TRY(h->w_item_part0.reserve(collect_rows));
-      PLVS_HIP_TRY(h->w_row_heads.reserve(collect_rows));
-      PLVS_HIP_TRY(h->w_row_tot.reserve((size_t)collect_rows * kSlabVox));
-      const size_t parts_cap = (size_t)collect_bound / kCollectPart + collect_rows + 1;
-      PLVS_HIP_TRY(h->dkey0.reserve(collect_bound));
-      PLVS_HIP_TRY(h->dkey1.reserve(collect_bound));
-      PLVS_HIP_TRY(h->w_val0.reserve(collect_bound));
-      PLVS_HIP_TRY(h->w_val1.reserve(collect_bound));
-      PLVS_HIP_TRY(h->heads.reserve(collect_bound));
-      PLVS_HIP_TRY(h->w_part_item.reserve(parts_cap));
-      PLVS_HIP_TRY(h->w_phist.reserve(parts_cap * kSlabVox));
-      // (zero while the walk runs: runs_count writes the cells that hold runs)
-      PLVS_HIP_TRY(hipMemsetAsync(h->w_run_matrix.p, 0, (size_t)collect_rows * collect_blocks * sizeof(uint32_t), h->side));
-      PLVS_HIP_TRY(hipEventRecord(h->ev_zero, h->side));   // (runs_count, on the caller's stream, waits for it: long over by then)
-    }
-    if (h->w_runkey.cap < ((size_t)ntiles << h->run_r1_log2)) {
-      PLVS_HIP_TRY(h->w_runkey.reserve((size_t)2 * ntiles << h->run_r1_log2));
-      PLVS_HIP_TRY(h->w_masks.reserve(((size_t)2 * ntiles << h->run_r1_log2) * kMaskWords));
-    }
-    PLVS_HIP_TRY(h->w_masks.reserve(((size_t)ntiles << h->run_r1_log2) * kMaskWords));
-    hipLaunchKernelGGL(walk_prologue, dim3(ceil_div((size_t)std::max(max_chunks, nclouds + 1), 256)), dim3(256), 0, s, d_Twc,
-                       nclouds, h->poses.p, (const int32_t*)h->h_offsets, h->offsets.p, h->d_wctr, h->d_ctr, h->w_chunk_nseg.p,
-                       max_chunks, gsrc ? (int)kGridWords : (int)(2 * ntiles));
-    STAGE_MARK(0);
-    const GridSrc* const d_grid = gsrc ? reinterpret_cast<const GridSrc*>(h->offsets.p + 2 * ((size_t)nclouds + 1)) : nullptr;
-    static const bool count_in_walk = plvs::env_int("PLVS_SEG_COUNT_IN_WALK", 1, 0, 1) != 0;   // (developer switch)
-    AccOut out{h->w_rec.p, (uint32_t)std::min<size_t>(rec_own + rec_spill, 0xFFFFFFFFu), h->w_seg.p,
-               (uint32_t)std::min<size_t>(seg_own + seg_spill, 0xFFFFFFFFu), h->w_seg_cnt.p, h->w_tile_visits.p,
-               count_in_walk ? h->w_chunk_nseg.p : nullptr};
-    RunOut runs{h->w_runkey.p, h->w_masks.p, h->w_run_cnt.p, h->run_r1_log2, collect_ready ? h->w_rseg.p : nullptr};
-    // the common case of a tile alone in a lean kernel; what it defers (tiles over several clouds, table overflows,
-    // the owner-filtered walk of a sharded handle) is walked by the general kernel from the list
-    uint32_t* const list_a = h->w_deferred.p;
-    uint32_t* const list_b = h->w_deferred.p + ntiles;
-    uint32_t* const list_c = h->w_deferred.p + 2 * (size_t)ntiles;
-    const uint32_t* last_list = list_a;
-    const uint32_t* last_count = &h->d_wctr->ndeferred;
-    bool second_small = false, third_pass = false;
-#define PLVS_LAUNCH_WALK_FAST(E, GRID, TILES, LIST, NLIST, DEFERRED, NDEFERRED)                                              \
-  hipLaunchKernelGGL((walk_fast<E, GRID>), dim3(TILES), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, d_xyz, n,          \
-                     h->offsets.p, nclouds, h->poses.p, h->dir, &h->d_ctr->num_chunks, h->d_wctr, h->rgbw,                     \
-                     (const uint32_t*)nullptr, out, runs, TileMap{1u, 0u, 1u}, kRecStride, (const uint32_t*)(LIST),            \
-                     (const uint32_t*)(NLIST), DEFERRED, NDEFERRED, d_grid)
-#define PLVS_WALK_FAST(E, TILES, LIST, NLIST, DEFERRED, NDEFERRED)                                  \
-  do {                                                                                              \
-    if (gsrc) PLVS_LAUNCH_WALK_FAST(E, true, TILES, LIST, NLIST, DEFERRED, NDEFERRED);              \
-    else PLVS_LAUNCH_WALK_FAST(E, false, TILES, LIST, NLIST, DEFERRED, NDEFERRED);                  \
-  } while (0)
-    if (ntiles <= kSmallCallTiles) {
-      PLVS_WALK_FAST(kFastEntriesBig, ntiles, nullptr, nullptr, list_a, &h->d_wctr->ndeferred);
-    } else {
-      // The table of the first pass follows the scene: tiles of near surfaces (a small room, a desk) hold 300-600 voxels
-      // and a 1024-entry table lets THREE of them share a CU (6 waves per SIMD: 0.49 against 0.65 ms for the 100 key
-      // frames of the saturated room); tiles of walls 3-5 m away hold 800-2000 and would nearly all overflow it.  The
-      // counters of the call before decide (walk_small): the 2048-entry kernel counts the tiles a 1024-entry table would
-      // not have held, the 1024-entry kernel's deferred list says when it stops paying.
-      {   // developer switch: PLVS_WALK_SMALL = 0 / 1 forces the first pass's table
-        static const int force = plvs::env_int("PLVS_WALK_SMALL", -1, -1, 1);
-        if (force >= 0) h->walk_small = force != 0;
-      }
-      h->walk_small_used = h->walk_small;
-      if (h->walk_small) PLVS_WALK_FAST(kFastEntriesSmall, ntiles, nullptr, nullptr, list_a, &h->d_wctr->ndeferred);
-      else PLVS_WALK_FAST(kFastEntries, ntiles, nullptr, nullptr, list_a, &h->d_wctr->ndeferred);
-      // the tiles that overflowed the first pass: a 1024-entry first pass hands them to the 2048-entry kernel (two tiles per CU
-      // instead of one: nearly all of them fit it), a 2048-entry first pass to the 4096-entry one
-      if (h->walk_small) {
-        PLVS_WALK_FAST(kFastEntries, std::min<unsigned>(ntiles, 2 * kListGrid), list_a, &h->d_wctr->ndeferred, list_b,
-                       &h->d_wctr->ndeferred2);
-        // ... and what overflows that one too (a wall 5 m away seen at a slant) to the 4096-entry kernel rather than to
-        // walk_tiles — a call none of whose tiles reaches walk_tiles can have its runs collected chunk by chunk (below) instead
-        // of sorted — when the call before had such tiles: a launch that finds an empty list costs the stream 8 us
-        third_pass = h->third_pass;
-        if (third_pass)
-          PLVS_WALK_FAST(kFastEntriesBig, std::min<unsigned>(ntiles, kListGrid), list_b, &h->d_wctr->ndeferred2, list_c,
-                         &h->d_wctr->ndeferred3);
-      } else
-        PLVS_WALK_FAST(kFastEntriesBig, std::min<unsigned>(ntiles, kListGrid), list_a, &h->d_wctr->ndeferred, list_b,
-                       &h->d_wctr->ndeferred2);
-      second_small = h->walk_small && !third_pass;   // (the last lean pass had 2048 entries)
-#undef PLVS_WALK_FAST
-#undef PLVS_LAUNCH_WALK_FAST
-      last_list = third_pass ? list_c : list_b;
-      last_count = third_pass ? &h->d_wctr->ndeferred3 : &h->d_wctr->ndeferred2;
-    }
-    hipLaunchKernelGGL((walk_tiles<true, true>), dim3(kDeferGrid), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, d_xyz, n,
-                       h->offsets.p, nclouds, h->poses.p, h->dir, &h->d_ctr->num_chunks, h->d_wctr, h->rgbw,
-                       (const uint32_t*)nullptr, out, runs, TileMap{1u, 0u, 1u}, (uint32_t)ntiles, last_list, last_count,
-                       kRecStride, second_small ? 1u : 2u,
-                       d_grid);   // (what is flagged overflowed a 4096-entry table: two pieces at once; a 2048-entry one: it goes whole)
-    // A small call (a few key frames: PointCloudMapping::UpdateMap's batches) launches its colour chain on the sizes of
-    // the small call before it instead of waiting for its own (below), and keeps the chain — a dozen dependent launches,
-    // the longer of the two branches — on the caller's stream: the segment sort and the apply stage go to the side stream
-    // and are long over when the chain ends.  (A branch on another stream starts ~20 us after the event it waits for and is
-    // joined ~20 us after it ends.)
-    // (round 5) ... and so does a LONG call once the map has saturated: the call before left at most a few hundred runs (what
-    // few rays reach at the rim of the map), the chain is then three short launches on a bound of kSmallRuns, and the host's
-    // read of the run count — scan, publish, a wake-up: 0.06 ms behind a 0.09 ms segment sort + apply — was what a steady-state
-    // step ended with.  A long call over new ground (millions of runs, twice or half the call before) keeps its own count.
-    // (expect_runs, predicted: computed at the top of the attempt — what the call reserves depends on them)
-    // (a moderate number — a saturated map's rim: tens of thousands — is sorted on a bound a quarter above the expectation)
-    // (end of round 5, measured and left OFF: PLVS_TSDF_PREDICT_LONG=1) every call whose predecessor left a count could do so:
-    // beyond a moderate number with a LOOSE bound — three times the expectation, a million at least: the stream's counts go
-    // 4.5 M, 1.4 M, 1.6 M, 1.1 M, 2.6 M ... — and a sort that takes the number of pairs from the device
-    // (radix_sort_pairs_bound: launches sized by the bound, surplus tiles leave at once), so that a loose bound costs empty
-    // workgroups, not sorted padding, and the chain is queued behind the walk without a host read.  On the stream: GPU time
-    // per step 0.969 -> 0.965 ms, wall time 1.05 -> 1.07 (a bound that fails costs the chain twice): the chain's length is its
-    // kernels' (fold 0.13, three passes 0.15, compaction, heads), not the host's read.
-    // (a long call over new ground, not the handle's first: its runs are collected chunk by chunk, below; it has nothing for
-    // the side stream before its counting stages are over — ev_seg — and goes without the event behind the walk: an event
-    // between two kernels of a stream costs ~8 us)
-    const bool collect_fast = collect_ready && h->small_runs_known && attempt == 0 && !predicted;
-    if (!collect_fast) PLVS_HIP_TRY(hipEventRecord(h->ev_fork, s));
-    STAGE_MARK(1);
-    // When that bound is the small one (<= kSmallRuns: ONE sorting launch), nothing is worth a second stream: a branch on
-    // another stream starts ~20 us after the event it waits for and is joined ~20 us after it ends — more than the chain
-    // itself.  Segment sort, apply, sort_runs_small, fold follow each other on the caller's stream; seg_scan, which sums the
-    // tiles' run counts anyway, leaves the total where the colour side reads it (no scan of the counts either).
-    const bool serial_small = predicted && expect_runs <= kSmallRuns / 2;
-    const hipStream_t q_apply = (predicted && !serial_small) ? h->side : s, q_colour = predicted ? s : h->side;
-#define STAGE_MARK_ON(i, q) \
-  do { if (h->profiling) PLVS_HIP_TRY(hipEventRecord(h->ev[i], q)); } while (0)
-    uint32_t collect_seq = 0;   // (the sequence number rows_place publishes the walk's counters under)
-    auto segments_and_apply = [&]() -> int {
-    const unsigned seg_blocks = ceil_div(seg_own + seg_spill, kSegSpan);
-    if (!count_in_walk)
-      hipLaunchKernelGGL(seg_pass<false>, dim3(seg_blocks), dim3(256), 0, q_apply, h->w_seg.p, out.seg_cap, ntiles,
-                         h->w_seg_cnt.p, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p, h->w_sorted_seg.p,
-                         h->d_wctr);
-    hipLaunchKernelGGL(seg_scan, dim3(1), dim3(1024), 0, q_apply, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p,
-                       h->updated.p, h->w_active_off.p, h->d_wctr, &h->d_ctr->num_chunks, max_chunks,
-                       h->w_tile_visits.p, h->w_run_cnt.p, ntiles, h->w_part_off.p, h->w_multi_idx.p, h->multi_cap,
-                       h->part_segs, h->part_min, collect_ready ? h->w_active_idx.p : (uint32_t*)nullptr);
-    if (collect_ready) {
-      // the colour side's counting stages here, in front of the segment sort: short kernels that would otherwise start
-      // beside the apply stage's first thousand workgroups and wait for their slots (40 us each, measured)
-      PLVS_HIP_TRY(hipStreamWaitEvent(q_apply, h->ev_zero, 0));
-      hipLaunchKernelGGL(runs_count, dim3(collect_blocks), dim3(kSegSpan), 0, q_apply, h->w_seg.p, h->w_rseg.p, ntiles, h->w_seg_cnt.p,
-                         h->w_active_idx.p, collect_rows, collect_blocks, h->w_run_matrix.p, h->w_rpre.p, h->d_wctr, last_count);
-      hipLaunchKernelGGL(runs_rowscan, dim3(std::min<uint32_t>(ceil_div(collect_rows, 4), 1024u)), dim3(256), 0, q_apply,
-                         h->w_run_matrix.p, collect_rows, collect_blocks, h->d_wctr, h->w_item_cnt.p);
-      hipLaunchKernelGGL(rows_place, dim3(1), dim3(1024), 0, q_apply, h->w_item_cnt.p, collect_rows, collect_bound,
-                         (uint32_t)std::min<size_t>((size_t)collect_bound / kCollectPart + collect_rows + 1, 0xFFFFFFFFu), h->d_wctr,
-                         h->w_item_base.p, h->w_item_part0.p, h->w_part_item.p, reinterpret_cast<const uint32_t*>(h->d_ctr),
-                         reinterpret_cast<uint32_t*>(h->h_wctr), reinterpret_cast<uint32_t*>(h->h_ctr),
-                         (uint32_t)(sizeof(Counters) / sizeof(uint32_t)), collect_fast ? h->h_seq : (uint32_t*)nullptr,
-                         collect_fast ? (collect_seq = ++h->seq_next) : 0u);
-      PLVS_HIP_TRY(hipEventRecord(h->ev_seg, q_apply));
-    }
-    // (a long call: 4096 descriptor slots — 64 tiles — per workgroup instead of 1024: a quarter of the workgroups, and what
-    // the kernel waits for is their atomics on the counters of a hundred-odd chunks)
-    static const bool wide_span = plvs::env_int("PLVS_SEG_SPAN_WIDE", 1, 0, 1) != 0;   // (developer switch)
-    if (wide_span && ntiles > kPredictTiles)
-      hipLaunchKernelGGL((seg_pass<true, kSegSpanLong>), dim3(ceil_div(seg_own + seg_spill, kSegSpanLong)), dim3(256), 0, q_apply, h->w_seg.p,
-                         out.seg_cap, ntiles, h->w_seg_cnt.p, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p,
-                         h->w_sorted_seg.p, h->d_wctr);
-    else
-    hipLaunchKernelGGL(seg_pass<true>, dim3(seg_blocks), dim3(256), 0, q_apply, h->w_seg.p, out.seg_cap, ntiles,
-                       h->w_seg_cnt.p, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p, h->w_sorted_seg.p,
-                       h->d_wctr);
-    STAGE_MARK_ON(2, q_apply);
-    hipLaunchKernelGGL((apply_chunks<false, false>), dim3(4096), dim3(kApplyThreads), 0, q_apply, h->w_sorted_seg.p, h->updated.p,
-                       h->w_active_off.p, h->w_part_off.p, h->w_multi_idx.p, h->part_segs,
-                       PartAcc{h->pa_wuu.p, h->pa_w.p, h->pa_last.p, h->pa_cnt.p, h->pa_done.p}, h->w_rec.p,
-                       1.0 / (double)h->scale_u, 1.0 / (double)h->scale_w, d_kfid, h->sdf, h->weight, h->kfid, h->d_wctr,
-                       EmitOut{}, gsrc ? grid.key_bits : 0u);
-    PLVS_KERNEL_CHECK();
-    STAGE_MARK_ON(3, q_apply);
-    return PLVS_OK;
-    };
-    // (the host issues the critical branch first: a one-key-frame walk is over before a dozen launches have been made)
-    if (!predicted) {
-      int rc = segments_and_apply();
-      if (rc != PLVS_OK) return rc;
-    }
-    // ---- colour fold: the truncating u8 mean is order dependent -> through the sorted runs of the voxels
-    // whose colour weight is below 254.  It only needs the runs the walk left, so it runs on another stream than
-    // the segment sort and the apply stage (both short, latency-bound kernels).
-    uint32_t* const side_ctr = &h->d_wctr[1].num_desc;   // the run count, for the side stream's kernels
-    // the chain behind the scan of the run counts, for D runs (or a bound on them: guard) on stream q
-    // (developer switch: the most runs the one-launch sort takes, 0 = never; one workgroup sorts ~1 000 pairs per microsecond
-    // and pass, the general chain costs ~60 us of launches before it does anything)
-    static const uint32_t medium_max = (uint32_t)plvs::env_int("PLVS_TSDF_MEDIUM_SORT", 16384, 0, (int)kMediumRuns);
-    // (... and of few tiles: its listing of the runs is one workgroup's loop over the tiles — 15 000 tiles with a run each, the rim
-    // of a saturated map in a 100-key-frame call, take it longer than the general chain's launches: steady state 0.62 -> 0.67 ms)
-    const bool medium_sort = medium_max != 0 && ntiles <= 2048u;
-    auto launch_fold = [&](uint32_t D, const uint32_t* skeys, const uint32_t* sval, hipStream_t q, const uint32_t* skip) -> int {
-      const RunSrc rsrc{h->w_masks.p, (uint32_t)kMaskWords, h->run_r1_log2, TileMap{1u, 0u}, h->offsets.p, nclouds,
-                        reinterpret_cast<const uint32_t*>(h->offsets.p) + 2 * ((size_t)nclouds + 1)};
-      if (gsrc)
-        hipLaunchKernelGGL(fold_colours_masks<true>, dim3(std::min<size_t>(ceil_div(D, kFoldWaves), 8192)),
-                           dim3(64 * kFoldWaves), 0, q, skeys, sval, side_ctr, rsrc, h->heads.p, d_rgb,
-                           h->rgbw, &h->d_wctr[1].num_heads, (uint32_t*)nullptr, (uint32_t*)nullptr, skip, grid);
-      else
-        hipLaunchKernelGGL(fold_colours_masks<false>, dim3(std::min<size_t>(ceil_div(D, kFoldWaves), 8192)),
-                           dim3(64 * kFoldWaves), 0, q, skeys, sval, side_ctr, rsrc, h->heads.p, d_rgb,
-                           h->rgbw, &h->d_wctr[1].num_heads, (uint32_t*)nullptr, (uint32_t*)nullptr, skip, grid);
-      PLVS_KERNEL_CHECK();
-      return PLVS_OK;
-    };
-    auto colour_chain = [&](uint32_t D, int chunks, hipStream_t q, const RunGuard* guard) -> int {
-      const uint32_t* skeys = h->dkey0.p;
-      const uint32_t* sval = h->w_val0.p;
-      if (D <= kSmallRuns) {
-        hipLaunchKernelGGL(sort_runs_small, dim3(1), dim3(1024), 0, q, h->w_runkey.p, h->w_run_cnt.p, ntiles,
-                           h->run_r1_log2, h->d_wctr + 1, h->dkey0.p, h->w_val0.p, h->heads.p, guard ? guard->skip : (uint32_t*)nullptr);
-      } else if (medium_sort && D <= medium_max) {
-        // one workgroup, one launch: the runs listed, sorted and their voxels' first runs found (sort_runs_medium)
-        PLVS_HIP_TRY(h->dkey0.reserve(D));
-        PLVS_HIP_TRY(h->dkey1.reserve(D));
-        PLVS_HIP_TRY(h->w_val0.reserve(D));
-        PLVS_HIP_TRY(h->w_val1.reserve(D));
-        PLVS_HIP_TRY(h->heads.reserve(D));
-        int key_bits = 12;
-        while ((1ll << (key_bits - 12)) < (long long)chunks) ++key_bits;
-        const bool ten = key_bits <= 20;   // (two passes of ten bits instead of three of eight)
-        const int passes = ten ? 2 : (key_bits + 7) / 8;
-#define PLVS_SORT_MEDIUM(BITS)                                                                                                    \
-  hipLaunchKernelGGL(sort_runs_medium<BITS>, dim3(1), dim3(1024), 0, q, h->w_runkey.p, h->w_run_cnt.p, ntiles, h->run_r1_log2,   \
-                     h->d_wctr + 1, h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, h->w_run_off.p, h->heads.p, passes,         \
-                     guard ? guard->limit : 0xFFFFFFFFu, &h->d_ctr->num_chunks, guard ? guard->chunk_limit : 0,                   \
-                     guard ? guard->skip : (uint32_t*)nullptr)
-        if (ten) PLVS_SORT_MEDIUM(10);
-        else PLVS_SORT_MEDIUM(8);
-#undef PLVS_SORT_MEDIUM
-        skeys = (passes & 1) ? h->dkey1.p : h->dkey0.p;
-        sval = (passes & 1) ? h->w_val1.p : h->w_val0.p;
-      } else {
-        int rc = sort_runs(h, D, ntiles, chunks, q, &skeys, &sval, guard);
-        if (rc != PLVS_OK) return rc;
-        PLVS_HIP_TRY(h->heads.reserve(D));
-        PLVS_HIP_TRY(h->w_dummy.reserve((size_t)max_chunks + 1));
-        hipLaunchKernelGGL(voxel_heads, dim3(ceil_div(D, 256 * kHeadTiles)), dim3(256), 0, q, skeys, D,
-                           h->heads.p, h->w_dummy.p, h->d_wctr + 1, guard ? (const uint32_t*)side_ctr : (const uint32_t*)nullptr);
-      }
-      return launch_fold(D, skeys, sval, q, guard ? (const uint32_t*)guard->skip : (const uint32_t*)nullptr);
-    };
-    // the runs of a long call whose tiles all went through walk_fast, chunk by chunk (runs_count ... parts_place): behind the
-    // list of the updated chunks (ev_seg), no pass that sorts all runs.  What it cannot take sets `skip` — the fold then
-    // leaves at once and the general chain runs once the call's counters are read (as for a predicted chain whose bounds
-    // did not hold).
-    auto collect_chain = [&](uint32_t D, hipStream_t q) -> int {
-      const size_t parts_cap = (size_t)collect_bound / kCollectPart + collect_rows + 1;
-      PLVS_HIP_TRY(hipStreamWaitEvent(q, h->ev_seg, 0));
-      hipLaunchKernelGGL(runs_scatter, dim3(collect_blocks * (kSegSpan / 256)), dim3(256), 0, q, h->w_seg.p, h->w_rseg.p, ntiles, h->w_seg_cnt.p,
-                         h->w_active_idx.p, collect_rows, collect_blocks, h->w_run_matrix.p, h->w_rpre.p, h->w_item_base.p,
-                         h->d_wctr, h->w_val0.p);
-      const unsigned part_grid = (unsigned)std::min<size_t>(parts_cap, 4096);
-      hipLaunchKernelGGL(parts_count, dim3(part_grid), dim3(256), 0, q, h->w_part_item.p, h->w_item_part0.p, h->w_item_base.p,
-                         h->w_item_cnt.p, h->w_runkey.p, h->d_wctr, h->w_val0.p, h->dkey0.p, h->w_phist.p);
-      hipLaunchKernelGGL(rows_heads, dim3(std::min<uint32_t>(ceil_div(collect_rows, 4), 1024u)), dim3(256), 0, q, h->w_item_part0.p,
-                         h->w_item_cnt.p, h->w_phist.p, h->d_wctr, collect_rows, h->w_row_heads.p, h->w_row_tot.p);
-      hipLaunchKernelGGL(parts_place, dim3(part_grid), dim3(512), 0, q, h->w_part_item.p, h->w_item_part0.p, h->w_item_base.p,
-                         h->w_item_cnt.p, h->w_phist.p, h->d_wctr, h->dkey0.p, h->w_val0.p, h->dkey1.p, h->w_val1.p, h->heads.p,
-                         h->w_row_heads.p, collect_rows, h->w_row_tot.p);
-      return launch_fold(D, h->dkey1.p, h->w_val1.p, q, &h->d_wctr[1].skip);
-    };
-    // (predicted: a bound that does not hold costs the chain a second time — the fold of the first skips itself: compact_runs)
-    uint32_t run_bound = 0;
-    int chunk_bound = 0;
-    bool collected = false, scanned = false;
-    if (serial_small) {
-      int rc = segments_and_apply();
-      if (rc != PLVS_OK) return rc;
-      run_bound = kSmallRuns;
-      chunk_bound = std::min(max_chunks, std::max(2 * chunks_before, chunks_before + 256));
-      const RunGuard guard{run_bound, side_ctr, &h->d_ctr->num_chunks, chunk_bound, &h->d_wctr[0].err, &h->d_wctr[1].skip, 1u, nullptr, 0u};
-      rc = colour_chain(run_bound, chunk_bound, s, &guard);
-      if (rc != PLVS_OK) return rc;
-    } else {
-      if (!predicted && !collect_fast) PLVS_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-      if (predicted) {
-        const size_t slots = (size_t)ntiles << h->run_r1_log2;
-        // (the call before scaled to this call's tiles — calls of one and of five key frames may alternate —, a quarter more)
-        const size_t expect = (size_t)((double)h->small_runs_last * (double)ntiles / (double)std::max(1u, h->small_tiles_last));
-        // (up to kPredictRuns: a tight bound, padded — two or three short launches of the plain sort; beyond: the loose one)
-        const bool loose = predict_long && expect > kPredictRuns;
-        run_bound = expect <= kSmallRuns / 2 ? kSmallRuns
-                    : loose ? (uint32_t)std::min<size_t>(slots, (std::max<size_t>(3 * expect, (size_t)1 << 20) + 4095) / 4096 * 4096)
-                            : (uint32_t)std::min<size_t>(slots, (expect * 5 / 4 + 8191) / 4096 * 4096);
-        // (a moderate expectation: the one-launch sort on its full capacity — a bound that costs nothing; it sums the tiles'
-        // run counts itself, the general chain wants them scanned)
-        if (medium_sort && run_bound > kSmallRuns && expect * 5 / 4 + 1024 <= medium_max) run_bound = medium_max;
-        if (run_bound > medium_max) {
-          scanned = true;
-          PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, q_colour));
-        }
-        chunk_bound = std::min(max_chunks, std::max(2 * chunks_before, chunks_before + 256));
-        const RunGuard guard{run_bound, side_ctr, &h->d_ctr->num_chunks, chunk_bound, &h->d_wctr[0].err, &h->d_wctr[1].skip,
-                             loose ? 0u : 1u, nullptr, 0u};
-        int rc = colour_chain(run_bound, chunk_bound, q_colour, &guard);
-        if (rc != PLVS_OK) return rc;
-        PLVS_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        rc = segments_and_apply();
-        if (rc != PLVS_OK) return rc;
-      } else if (collect_fast) {
-        // a long call over new ground, not the handle's first: the runs chunk by chunk, queued behind the walk without a
-        // read of its counters — the buffers hold four times the call before, the kernels decide themselves whether the
-        // call is theirs (runs_count, rows_place: `skip`)
-        // The walk's counters are published all the same — in front of the chain on the side stream, which waits for the
-        // counting stages anyway — and read while the chain is queued: a tile or two of one call in twenty reach walk_tiles (a
-        // wall seen at a slant: more chunks than a tile's cache holds), the chain's kernels then leave at once (runs_count:
-        // `skip`) and the general chain is queued behind them now, not after the call's last kernel.
-        const uint32_t seq = collect_seq;   // (published by rows_place)
-        collected = true;
-        int rc = collect_chain(collect_bound, h->side);
-        if (rc != PLVS_OK) return rc;
-        {
-          int rcw = wait_published(h, seq, h->side, 1, size_class);
-          if (rcw != PLVS_OK) return rcw;
-        }
-        const uint32_t left_to_walk_tiles =
-            reinterpret_cast<const uint32_t*>(h->h_wctr)[last_count - reinterpret_cast<const uint32_t*>(h->d_wctr)];
-        if (h->h_wctr[0].err == 0 && (left_to_walk_tiles != 0u || h->h_wctr[0].seg_top != 0u)) {
-          collected = false;
-          scanned = true;
-          PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, h->side));
-          // (the run count: what seg_scan leaves is not there yet — the tiles' counts are: summed here)
-          const uint32_t seq2 = ++h->seq_next;
-          hipLaunchKernelGGL(publish_counters, dim3(1), dim3(64), 0, h->side, h->d_wctr, h->d_ctr, h->h_wctr, h->h_ctr, h->h_seq, seq2);
-          int rcw = wait_published(h, seq2, h->side, 2, size_class);   // (kind 2: a short wait of its own expectation)
-          if (rcw != PLVS_OK) return rcw;
-          const uint32_t D = h->h_wctr[1].num_desc;
-          if (D > 0) {
-            rc = colour_chain(D, h->h_ctr->num_chunks, h->side, nullptr);
-            if (rc != PLVS_OK) return rc;
-          }
-        }
-      } else {
-        scanned = true;
-        PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, q_colour));
-        const uint32_t seq = ++h->seq_next;
-        hipLaunchKernelGGL(publish_counters, dim3(1), dim3(64), 0, h->side, h->d_wctr, h->d_ctr, h->h_wctr, h->h_ctr, h->h_seq, seq);
-        {   // the walk is over; segment sort and apply are queued behind it
-          int rcw = wait_published(h, seq, h->side, 1, size_class);
-          if (rcw != PLVS_OK) return rcw;
-        }
-        const uint32_t D = h->h_wctr[1].num_desc;
-        // (collected: no tile was left to walk_tiles — its runs are not grouped by chunk — and enough runs to pay two launches)
-        const uint32_t left_to_walk_tiles =
-            reinterpret_cast<const uint32_t*>(h->h_wctr)[last_count - reinterpret_cast<const uint32_t*>(h->d_wctr)];
-        collected = collect_ready && left_to_walk_tiles == 0u && h->h_wctr[0].seg_top == 0u &&
-                    (D > kCollectMinRuns || collect_mode == 2);
-        if (h->h_wctr[0].err == 0 && D > 0) {
-          int rc = collected ? collect_chain(D, h->side) : colour_chain(D, h->h_ctr->num_chunks, h->side, nullptr);
-          if (rc != PLVS_OK) return rc;
-        }
-      }
-      PLVS_HIP_TRY(hipEventRecord(h->ev_join, h->side));
-      PLVS_HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
-    }
-#undef STAGE_MARK_ON
-    STAGE_MARK(4);
-    int rc = read_walk_counters(h, s, size_class);
-    if (rc != PLVS_OK) return rc;
-    const uint32_t err = h->h_wctr->err;
-    if (err & ~kErrScratch) return walk_fail(h, err);
-    if (err & kErrScratch) {   // the map is untouched (apply_chunks left at once, no colours folded): grow and repeat
-      if (attempt >= 8) return walk_fail(h, err);
-      rec_spill = std::max<size_t>(rec_spill, (size_t)h->h_wctr->rec_top * 2);
-      seg_spill = std::max<size_t>(seg_spill, (size_t)h->h_wctr->seg_top * 2);
-      while ((1u << h->run_r1_log2) < h->h_wctr->run_need) ++h->run_r1_log2;
-      if (((size_t)ntiles << h->run_r1_log2) >= 0xFFFFFFFFull) return walk_fail(h, err);
-      continue;
-    }
-    h->last_chain = collected ? 2 : (predicted ? 1 : 0);
-    h->last_chain_skipped = (predicted || collected) && h->h_wctr[1].skip != 0u;
-    if ((predicted || collected) && h->h_wctr[1].skip != 0u) {   // the bounds did not hold: the chain once more, with the call's numbers
-      const uint32_t D = h->h_wctr[1].num_desc;
-      if (!scanned)   // (its chain had no use for the offsets of the tiles' runs: the compaction of the long form has)
-        PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, s));
-      PLVS_HIP_TRY(hipMemsetAsync(&h->d_wctr[1].num_heads, 0, sizeof(uint32_t), s));
-      PLVS_HIP_TRY(hipMemsetAsync(&h->d_wctr[1].num_updated, 0, sizeof(uint32_t), s));
-      int rc2 = colour_chain(D, h->h_ctr->num_chunks, s, nullptr);
-      if (rc2 != PLVS_OK) return rc2;
-      rc2 = read_walk_counters(h, s, size_class);
-      if (rc2 != PLVS_OK) return rc2;
-    }
-    h->small_runs_known = true;      // (the runs of the last call, whatever its length)
-    h->small_runs_last = h->h_wctr[1].num_desc;
-    h->small_tiles_last = ntiles;
-    break;
-  }
+  return PLVS_OK;
+}
+
+// The finished call: what the next call's plan takes from it, the developer trace, the stats, the stage times.
+static int finish_call(plvs_tsdf_chisel* h, uint32_t ntiles, int chunks_before, const timespec& t0, bool trace) {
   const WalkCounters& c = *h->h_wctr;
   h->num_chunks = h->h_ctr->num_chunks;
-  if (ntiles > kSmallCallTiles) {   // the first pass's table for the next call of this size class
-    // (round 5: what overflows the small table goes to the 2048-entry kernel at two tiles per CU — a fifth of the tiles there
-    // still costs less than a 2048-entry first pass for all of them: 0.51 + 0.1 against 0.8 ms on the office stream, where
-    // the 6 % / 2 % thresholds of round 4 had every other step fall back to the large table)
-    if (h->walk_small_used) {
-      h->third_pass = c.ndeferred2 != 0u;   // (tiles overflowed the 2048-entry table too: the next call has a 4096-entry pass)
-      if ((size_t)c.ndeferred * 4 > ntiles) h->walk_small = false;    // more than a quarter of the tiles overflowed the small table
-    } else if ((size_t)c.over_small * 6 <= ntiles) {
-      h->walk_small = true;                                             // at most a sixth would
-    }
-  }
-  {   // developer trace of the call's counters (PLVS_HIP_TSDF_TRACE=1)
-    static const bool trace = plvs::env_int("PLVS_HIP_TSDF_TRACE", 0, 0, 1) != 0;
-    if (trace) {
-      timespec t1;
-      clock_gettime(CLOCK_MONOTONIC, &t1);
-      fprintf(stderr, "[tsdf_chisel] %.0f us ", (double)(t1.tv_sec - trace_t0.tv_sec) * 1e6 + (double)(t1.tv_nsec - trace_t0.tv_nsec) * 1e-3);
-    }
-    if (trace)
-      fprintf(stderr, "[tsdf_chisel] tiles %u deferred %u split %u visits %llu runs %u updated %u parts %u multi %u "
-              "rec_top %u seg_top %u voxels %u max_run %u chunks %d chain %d%s\n", ntiles, c.ndeferred * 1000u + c.ndeferred2 + c.ndeferred3 * 1000000u, c.split_tiles,
-              (unsigned long long)c.total_visits, h->h_wctr[1].num_desc, c.num_updated, c.num_parts, c.num_multi, c.rec_top,
-              c.seg_top, c.num_heads, c.max_run, h->num_chunks, h->last_chain, h->last_chain_skipped ? " REPEATED" : "");
+  adapt_after_call(h->walk, WalkOutcome{h->h_wctr[1].num_desc, c.ndeferred, c.ndeferred2, c.over_small}, ntiles);
+  if (trace) {
+    timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    fprintf(stderr, "[tsdf_chisel] %.0f us ", (double)(t1.tv_sec - t0.tv_sec) * 1e6 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-3);
+    fprintf(stderr, "[tsdf_chisel] tiles %u deferred %u split %u visits %llu runs %u updated %u parts %u multi %u "
+            "rec_top %u seg_top %u voxels %u max_run %u chunks %d chain %d%s\n", ntiles, c.ndeferred * 1000u + c.ndeferred2 + c.ndeferred3 * 1000000u, c.split_tiles,
+            (unsigned long long)c.total_visits, h->h_wctr[1].num_desc, c.num_updated, c.num_parts, c.num_multi, c.rec_top,
+            c.seg_top, c.num_heads, c.max_run, h->num_chunks, h->last_chain, h->last_chain_skipped ? " REPEATED" : "");
   }
   h->stats.visits = (int64_t)c.total_visits;
   h->stats.new_chunks = h->num_chunks - chunks_before;
@@ -1731,22 +1519,141 @@ static int integrate_walk_acc(plvs_tsdf_chisel* h, const float* d_xyz, const uin
   // Part accumulators for the next call: a chunk beyond them is applied in ONE part — never wrong, but on a stream of new
   // views the busy chunks of a call are not those of the call before, and a single 1 500-segment item then is the
   // whole stage (0.4 ms).  Room for twice the chunks this call updated (98 KB each), grown geometrically.
-  {
-    const uint32_t want = std::min<uint32_t>((uint32_t)max_chunks, std::max(c.num_multi + c.num_multi / 2, 2u * c.num_updated));
-    if (want > h->multi_cap) {
-      int rc = ensure_part_acc(h, std::min<uint32_t>((uint32_t)max_chunks, std::max(want, 2u * h->multi_cap)));
-      if (rc != PLVS_OK) return rc;
-    }
+  const uint32_t max_chunks = (uint32_t)h->prm.max_chunks;
+  const uint32_t want = std::min<uint32_t>(max_chunks, std::max(c.num_multi + c.num_multi / 2, 2u * c.num_updated));
+  if (want > h->multi_cap) {
+    int rc = ensure_part_acc(h, std::min<uint32_t>(max_chunks, std::max(want, 2u * h->multi_cap)));
+    if (rc != PLVS_OK) return rc;
   }
-  float ms[4] = {0.f, 0.f, 0.f, 0.f};   // the last one: what the colour fold adds behind the apply stage
-  if (h->profiling)
-    for (int i = 0; i < 4; ++i) PLVS_HIP_TRY(stage_elapsed(&ms[i], h->ev[i], h->ev[i + 1]));
-#undef STAGE_MARK
   if (h->profiling) {
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};   // the last one: what the colour fold adds behind the apply stage
+    for (int i = 0; i < 4; ++i) PLVS_HIP_TRY(stage_elapsed(&ms[i], h->ev[i], h->ev[i + 1]));
     for (int i = 0; i < 4; ++i) h->stage_ms[i] += ms[i];
     h->prof_calls++;
   }
   return PLVS_OK;
+}
+
+// gsrc (plvs_hip_tsdf_chisel_integrate_depth_batch_dev): the clouds are depth images — tiles are 32 x 16 blocks of grid
+// pixels (GridSrc, tsdf_walk.hpp), d_xyz is null, d_rgb = the colour images, d_kfid = one id per image, offsets =
+// nclouds + 1 zeros (nothing reads them).
+static int integrate_walk_acc(plvs_tsdf_chisel* h, const float* d_xyz, const uint8_t* d_rgb, const uint32_t* d_kfid,
+                              int n, int nclouds, const int32_t* offsets, const float* d_Twc, hipStream_t s,
+                              const GridSrc* gsrc = nullptr) {
+  // developer switches, read once per process: the collected chain (0 never, 1 long calls, 2 every call — tests); at most
+  // this many chunks' rows in its run matrix (tests: calls that update more repeat their chain); a line per call on stderr
+  static const int collect_mode = plvs::env_int("PLVS_TSDF_COLLECT", 1, 0, 2);
+  static const int max_row_chunks = plvs::env_int("PLVS_TSDF_COLLECT_MAX_ROWS", 0, 0, 1 << 20);
+  static const bool trace = plvs::env_int("PLVS_HIP_TSDF_TRACE", 0, 0, 1) != 0;
+  const int max_chunks = h->prm.max_chunks;
+  uint32_t ntiles = 0;
+  size_t table_words = 0;
+  int rc = fill_call_tables(h, offsets, nclouds, gsrc, &ntiles, &table_words);
+  if (rc != PLVS_OK) return rc;
+  if ((size_t)ntiles * kRecStride + (1 << 16) >= 0xFFFFFFFFull) {
+    plvs::set_error("tsdf_chisel integrate: %d points in one call exceed the record index range (split the batch)", n);
+    return PLVS_ERR_CAPACITY;
+  }
+  if ((rc = reserve_call(h, ntiles, table_words)) != PLVS_OK) return rc;
+  WalkScratch scratch = walk_scratch(h, ntiles);
+  h->stage_set = 1;
+  const int chunks_before = h->num_chunks;
+  timespec trace_t0;   // (developer trace: the call's time on the host's clock)
+  clock_gettime(CLOCK_MONOTONIC, &trace_t0);
+  uint32_t* const counts[3] = {&h->d_wctr->ndeferred, &h->d_wctr->ndeferred2, &h->d_wctr->ndeferred3};
+  uint32_t* const side_ctr = &h->d_wctr[1].num_desc;   // the run count: the scan of the tiles' run counts leaves it there
+  for (int attempt = 0;; ++attempt) {
+    if ((rc = reserve_walk_scratch(h, ntiles, scratch)) != PLVS_OK) return rc;
+    const WalkPlan plan = plan_walk_call(WalkPlanInput{ntiles, attempt, max_chunks, chunks_before, h->run_r1_log2, h->walk,
+                                                       h->last_updated, collect_mode, max_row_chunks});
+    if (plan.collect_ready && (rc = reserve_collect(h, plan, scratch, max_chunks)) != PLVS_OK) return rc;
+    hipLaunchKernelGGL(walk_prologue, dim3(ceil_div((size_t)std::max(max_chunks, nclouds + 1), 256)), dim3(256), 0, s, d_Twc,
+                       nclouds, h->poses.p, (const int32_t*)h->h_offsets, h->offsets.p, h->d_wctr, h->d_ctr, h->w_chunk_nseg.p,
+                       max_chunks, gsrc ? (int)kGridWords : (int)(2 * ntiles));
+    PLVS_HIP_TRY(stage_mark(h, 0, s));
+    const WalkCall call{d_xyz, d_rgb, d_kfid, n, nclouds, ntiles, max_chunks, gsrc,
+                        gsrc ? reinterpret_cast<const GridSrc*>(h->offsets.p + 2 * ((size_t)nclouds + 1)) : nullptr,
+                        scratch.seg_own + scratch.seg_spill, walk_out(h, scratch, h->w_chunk_nseg.p),
+                        RunOut{h->w_runkey.p, h->w_masks.p, h->w_run_cnt.p, h->run_r1_log2, plan.collect_ready ? h->w_rseg.p : nullptr},
+                        counts[plan.last_list], plan.chain == kChainCollected ? ++h->seq_next : 0u};
+    launch_walk_passes(h, plan, call, s);
+    if (plan.record_fork) PLVS_HIP_TRY(hipEventRecord(h->ev_fork, s));   // (an event between two kernels of a stream costs ~8 us)
+    PLVS_HIP_TRY(stage_mark(h, 1, s));
+    // ---- segment sort + apply, and the colour chain the plan names.  (The host issues the critical branch first: a
+    // one-key-frame walk is over before a dozen launches have been made.)
+    bool collected = false, scanned = false;   // collected: the chain that folded; scanned: w_run_off holds this call's offsets
+    if (plan.chain == kChainPredicted) {
+      // On the sizes of the call before; a bound that does not hold costs the chain a second time (the fold of the first
+      // skips itself).  The chain — a dozen dependent launches, the longer branch — stays on the caller's stream; segment
+      // sort and apply go to the side stream and are long over when it ends, or, under the small bound, in front of it.
+      if (plan.serial_small && (rc = segments_and_apply(h, plan, call, s)) != PLVS_OK) return rc;
+      if ((scanned = plan.scan_first))
+        PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, s));
+      const RunGuard guard{plan.run_bound, side_ctr, &h->d_ctr->num_chunks, plan.chunk_bound, &h->d_wctr[0].err,
+                           &h->d_wctr[1].skip, 1u, nullptr, 0u};
+      if ((rc = colour_chain(h, call, plan.run_bound, plan.chunk_bound, &guard, s)) != PLVS_OK) return rc;
+      if (plan.apply_on_side) {
+        PLVS_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+        if ((rc = segments_and_apply(h, plan, call, h->side)) != PLVS_OK) return rc;
+      }
+    } else {
+      if ((rc = segments_and_apply(h, plan, call, s)) != PLVS_OK) return rc;
+      const size_t last_count_word = call.last_count - reinterpret_cast<const uint32_t*>(h->d_wctr);   // (in h_wctr once read)
+      if (plan.chain == kChainCollected) {
+        // A long call over new ground, not the handle's first: the runs chunk by chunk, queued behind the walk without a
+        // read of its counters — the kernels decide themselves whether the call is theirs (runs_count, rows_place: `skip`).
+        // The walk's counters are published all the same (rows_place) and read while the chain is queued: when a tile
+        // reached walk_tiles or a segment spilled, the chain's kernels leave at once and the sorting chain is queued
+        // behind them now, not after the call's last kernel.
+        if ((rc = collect_chain(h, plan, call, plan.collect_bound, h->side)) != PLVS_OK) return rc;
+        if ((rc = wait_published(h, call.collect_seq, h->side, 1, plan.size_class)) != PLVS_OK) return rc;
+        const uint32_t left_to_walk_tiles = reinterpret_cast<const uint32_t*>(h->h_wctr)[last_count_word];
+        collected = !(h->h_wctr[0].err == 0 && (left_to_walk_tiles != 0u || h->h_wctr[0].seg_top != 0u));
+        if (!collected) {
+          scanned = true;
+          PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, h->side));
+          if ((rc = read_walk_counters(h, h->side, plan.size_class, 2)) != PLVS_OK) return rc;   // (kind 2: a short wait of its own expectation)
+          const uint32_t D = h->h_wctr[1].num_desc;
+          if (D > 0 && (rc = colour_chain(h, call, D, h->h_ctr->num_chunks, nullptr, h->side)) != PLVS_OK) return rc;
+        }
+      } else {
+        // On the call's own counts: the walk is over when they arrive; segment sort and apply are queued behind it.
+        PLVS_HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+        scanned = true;
+        PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, h->side));
+        if ((rc = read_walk_counters(h, h->side, plan.size_class, 1)) != PLVS_OK) return rc;
+        const uint32_t D = h->h_wctr[1].num_desc;
+        collected = collect_on_own_counts(plan, reinterpret_cast<const uint32_t*>(h->h_wctr)[last_count_word], h->h_wctr[0].seg_top, D);
+        if (h->h_wctr[0].err == 0 && D > 0) {
+          rc = collected ? collect_chain(h, plan, call, D, h->side) : colour_chain(h, call, D, h->h_ctr->num_chunks, nullptr, h->side);
+          if (rc != PLVS_OK) return rc;
+        }
+      }
+    }
+    if (!plan.serial_small) {   // (the side stream had a branch)
+      PLVS_HIP_TRY(hipEventRecord(h->ev_join, h->side));
+      PLVS_HIP_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
+    }
+    PLVS_HIP_TRY(stage_mark(h, 4, s));
+    if ((rc = read_walk_counters(h, s, plan.size_class)) != PLVS_OK) return rc;
+    const uint32_t err = h->h_wctr->err;
+    if (err & ~kErrScratch) return walk_fail(h, err);
+    if (err & kErrScratch) {   // the map is untouched (apply_chunks left at once, no colours folded): grow and repeat
+      if (attempt >= 8 || !grow_walk_scratch(h, ntiles, scratch)) return walk_fail(h, err);
+      continue;
+    }
+    h->last_chain = collected ? kChainCollected : plan.chain == kChainPredicted ? kChainPredicted : kChainOwn;
+    h->last_chain_skipped = h->last_chain != kChainOwn && h->h_wctr[1].skip != 0u;
+    if (h->last_chain_skipped) {   // the bounds did not hold: the chain once more, with the call's numbers
+      if (!scanned) PLVS_HIP_TRY(exclusive_scan_u32(h->w_run_cnt.p, h->w_run_off.p, ntiles, side_ctr, h->scratch.p, s));
+      PLVS_HIP_TRY(hipMemsetAsync(&h->d_wctr[1].num_heads, 0, sizeof(uint32_t), s));
+      PLVS_HIP_TRY(hipMemsetAsync(&h->d_wctr[1].num_updated, 0, sizeof(uint32_t), s));
+      if ((rc = colour_chain(h, call, h->h_wctr[1].num_desc, h->h_ctr->num_chunks, nullptr, s)) != PLVS_OK) return rc;
+      if ((rc = read_walk_counters(h, s, plan.size_class)) != PLVS_OK) return rc;
+    }
+    break;
+  }
+  return finish_call(h, ntiles, chunks_before, trace_t0, trace);
 }
 
 extern "C" {
@@ -1903,14 +1810,10 @@ int plvs_hip_tsdf_chisel_create(const plvs_tsdf_chisel_params* p, plvs_tsdf_chis
   {
     // The side stream carries a long call's colour chain — the longer of the two branches behind the walk, a row of short
     // kernels — beside the apply stage's thousands of workgroups on the caller's stream: at the highest priority its
-    // workgroups are dispatched ahead of the apply stage's queue instead of behind it.  (developer switch)
+    // workgroups are dispatched ahead of the apply stage's queue instead of behind it.
     int least = 0, greatest = 0;
     CREATE_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const bool prio = plvs::env_int("PLVS_TSDF_SIDE_PRIORITY", 1, 0, 1) != 0;
-    CREATE_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio ? greatest : least));
-    // (developer switches: the apply stage's parts, as plvs_hip_tsdf_chisel_set_apply_parts sets them)
-    h->part_segs = (uint32_t)plvs::env_int("PLVS_APPLY_PART_SEGS", (int)kPartSegs, 1, 1 << 20);
-    h->part_min = (uint32_t)plvs::env_int("PLVS_APPLY_PART_MIN", (int)kPartMin, 1, 1 << 20);
+    CREATE_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, greatest));
   }
   CREATE_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   CREATE_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
@@ -2016,7 +1919,7 @@ int plvs_hip_tsdf_chisel_clear(plvs_tsdf_chisel* h) {
   PLVS_KERNEL_CHECK();
   PLVS_HIP_TRY(hipDeviceSynchronize());
   h->num_chunks = 0;
-  h->small_runs_known = false;   // (the first small call on the empty map reads its own run count)
+  h->walk.small_runs_known = false;   // (the first call on the empty map reads its own run count)
   h->poisoned = false;
   h->stats = plvs_tsdf_stats{};
   h->last_updated = 0;
@@ -3171,23 +3074,17 @@ int plvs_hip_tsdf_chisel_shard_walk(plvs_tsdf_chisel* h, const float* d_xyz, con
     int rc2 = ensure_part_acc(h, (uint32_t)std::min<size_t>(xmax, 64));
     if (rc2 != PLVS_OK) return rc2;
   }
-  const size_t rec_own = (size_t)nt * kWalkLimit, seg_own = (size_t)nt * kWalkChunks;
-  size_t rec_spill = std::max<size_t>(h->w_rec.cap > rec_own ? h->w_rec.cap - rec_own : 0, (size_t)1 << 16);
-  size_t seg_spill = std::max<size_t>(h->w_seg.cap / 2 > seg_own ? h->w_seg.cap / 2 - seg_own : 0, (size_t)1 << 12);
+  WalkScratch scratch = walk_scratch(h, nt);
   Params Pw = h->P;       // this rank walks its tiles through every chunk they cross
   Pw.shard_count = 1;
   Pw.shard_rank = 0;
   const TileMap tmap{(uint32_t)N, (uint32_t)rank};
   for (int attempt = 0;; ++attempt) {
-    // (sized by the call's tiles, and the largest buffers of the handle — 64 B of masks per run slot, gigabytes: a stream of
-    // calls of varying length would re-allocate them whenever a call is a little longer than any before, so they grow to
-    // TWICE what a call needs, as in integrate_walk_acc)
-    if (h->w_rec.cap < rec_own + rec_spill) PLVS_HIP_TRY(h->w_rec.reserve(2 * rec_own + rec_spill));
-    if (h->w_seg.cap < 2 * (seg_own + seg_spill)) PLVS_HIP_TRY(h->w_seg.reserve(2 * (2 * seg_own + seg_spill)));
-    PLVS_HIP_TRY(h->w_sorted_seg.reserve(h->w_seg.cap));
-    const size_t run_slots = (size_t)nt << h->run_r1_log2;
-    if (h->w_runkey.cap < run_slots) PLVS_HIP_TRY(h->w_runkey.reserve(2 * run_slots));
-    if (h->w_masks.cap < run_slots * kMaskWords) PLVS_HIP_TRY(h->w_masks.reserve(2 * run_slots * kMaskWords));
+    {
+      int rcs = reserve_walk_scratch(h, nt, scratch);
+      if (rcs != PLVS_OK) return rcs;
+    }
+    const size_t run_slots = (size_t)nt << h->run_r1_log2;   // (what follows grows to twice a call's need as well)
     if (h->dkey0.cap < run_slots) PLVS_HIP_TRY(h->dkey0.reserve(2 * run_slots));   // (all a call's runs, whatever their number)
     if (h->sh_run_first.cap < run_slots) PLVS_HIP_TRY(h->sh_run_first.reserve(2 * run_slots));   // (first wire record per run)
     if (h->w_val0.cap < run_slots) PLVS_HIP_TRY(h->w_val0.reserve(2 * run_slots));
@@ -3195,8 +3092,7 @@ int plvs_hip_tsdf_chisel_shard_walk(plvs_tsdf_chisel* h, const float* d_xyz, con
     PLVS_HIP_TRY(hipMemsetAsync(h->d_wctr, 0, 2 * sizeof(WalkCounters), s));
     PLVS_HIP_TRY(hipMemsetAsync(h->w_chunk_nseg.p, 0, xmax * sizeof(uint32_t), s));
     PLVS_HIP_TRY(hipMemsetAsync(h->sh_run_ctr.p, 0, 3 * 64 * sizeof(uint32_t), s));
-    AccOut out{h->w_rec.p, (uint32_t)std::min<size_t>(rec_own + rec_spill, 0xFFFFFFFFu), h->w_seg.p,
-               (uint32_t)std::min<size_t>(seg_own + seg_spill, 0xFFFFFFFFu), h->w_seg_cnt.p, h->w_tile_visits.p, nullptr};
+    const AccOut out = walk_out(h, scratch, nullptr);   // (nullptr: seg_pass<false> counts the chunks' segments)
     RunOut runs{h->w_runkey.p, h->w_masks.p, h->w_run_cnt.p, h->run_r1_log2};
     // (a chunk entered by an attempt that has to be repeated stays in the walk directory: harmless)
     hipLaunchKernelGGL(walk_fast<kFastEntries>, dim3(nt), dim3(kWalkRays), 0, s, Pw, h->scale_u, h->scale_w, d_xyz, n,
@@ -3208,7 +3104,7 @@ int plvs_hip_tsdf_chisel_shard_walk(plvs_tsdf_chisel* h, const float* d_xyz, con
                        (const uint32_t*)h->x_sat, out, runs, tmap, (uint32_t)nt, (const uint32_t*)h->w_deferred.p,
                        (const uint32_t*)&h->d_wctr->ndeferred, (uint32_t)kWalkLimit,
                        1u, (const GridSrc*)nullptr);   // (flagged = overflowed 2048 entries: this kernel's table takes 3584, the tile goes whole)
-    const unsigned seg_blocks = ceil_div(seg_own + seg_spill, kSegSpan);
+    const unsigned seg_blocks = ceil_div(scratch.seg_own + scratch.seg_spill, kSegSpan);
     hipLaunchKernelGGL(seg_pass<false>, dim3(seg_blocks), dim3(256), 0, s, h->w_seg.p, out.seg_cap, nt, h->w_seg_cnt.p,
                        h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p, h->w_sorted_seg.p, h->d_wctr);
     hipLaunchKernelGGL(seg_scan, dim3(1), dim3(1024), 0, s, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p,
@@ -3244,14 +3140,7 @@ int plvs_hip_tsdf_chisel_shard_walk(plvs_tsdf_chisel* h, const float* d_xyz, con
     }
     if (err & ~kErrScratch) return walk_fail(h, err);
     if (err & kErrScratch) {
-      if (attempt >= 8) return walk_fail(h, err);
-      if (getenv("PLVS_DEBUG_SHARD"))   // (a repeated walk doubles the step: which scratch region was short)
-        fprintf(stderr, "shard_walk repeats: %u tiles, records %u of %zu spill, segments %u of %zu spill, runs per tile %u of %u\n",
-                nt, h->h_wctr->rec_top, rec_spill, h->h_wctr->seg_top, seg_spill, h->h_wctr->run_need, 1u << h->run_r1_log2);
-      rec_spill = std::max<size_t>(rec_spill, (size_t)h->h_wctr->rec_top * 2);
-      seg_spill = std::max<size_t>(seg_spill, (size_t)h->h_wctr->seg_top * 2);
-      while ((1u << h->run_r1_log2) < h->h_wctr->run_need) ++h->run_r1_log2;
-      if (((size_t)nt << h->run_r1_log2) >= 0xFFFFFFFFull) return walk_fail(h, err);
+      if (attempt >= 8 || !grow_walk_scratch(h, nt, scratch)) return walk_fail(h, err);
       continue;
     }
     // ---- this rank's own aggregation: one sum per touched voxel into the owner's send region

@@ -70,15 +70,6 @@ constexpr uint32_t kErrScratch = 8u;            // record / segment / run buffer
 
 // Phase clocks of walk_tiles (a developer build: make PROF=1 -> libplvs_hip_prof.so; thread 0 of a tile adds the shader
 // cycles between the tile's barriers to g_walk_prof[phase]).  Compiled out of the product library.
-#ifndef PLVS_WALK_SORT
-#define PLVS_WALK_SORT 0    // walk_fast: 1 = the rays of a tile dealt to the waves by depth — parity holds, measured SLOWER
-                            // (walk 0.857 -> 0.880 ms on the stream, 0.512 -> 0.550 in the room: three barriers, scattered point
-                            // loads and neighbouring lanes no longer sharing table buckets cost more than the 14-19 % of loop
-                            // iterations the homogeneous waves save); kept as a switch
-#endif
-#ifndef PLVS_WALK_EXP
-#define PLVS_WALK_EXP 0     // timing experiments (developer builds; results are wrong with any bit set)
-#endif
 #ifdef PLVS_WALK_PROF
 __device__ unsigned long long g_walk_prof[16];
 __device__ unsigned long long g_apply_items[8192][4];   // per item of the LAST apply launch: cycles, segments << 32 | records of thread 0's group
@@ -310,9 +301,6 @@ __device__ __forceinline__ float signed_dist_fast(const Pose& pose, float depth,
   xform(pose.Ri, pose.ti, c0, c1, c2, cc);
   const float n2 = sqnorm3(cc[0], cc[1], cc[2]);
   const bool plain = !(n2 >= 0x1p-80f && n2 <= 0x1p80f) || !(fabsf(cc[2]) >= 0x1p-40f && fabsf(cc[2]) <= 0x1p40f);
-#if (PLVS_WALK_EXP & 4)   // (timing experiment: raw v_sqrt / v_rcp, no correction steps)
-  return __builtin_amdgcn_sqrtf(n2) * (depth * __builtin_amdgcn_rcpf(cc[2]) - 1);
-#endif
   if (__builtin_expect(plain, 0)) return sqrtf(n2) * (depth / cc[2] - 1);
   return sqrt_rn_normal(n2) * (div_rn_normal(depth, cc[2]) - 1);
 }
@@ -837,7 +825,7 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
     uint32_t nv = 0;
     // the lean walk: whole rays of a sub-tile of several rays on an unsharded map (everything but the re-walks
     // of a ray that did not fit the table and the owner-filtered walk of a sharded handle)
-    const bool lean = !lone && st.vlo == 0u && st.vhi == 0xFFFFFFFFu && P.shard_count <= 1 && !(PLVS_WALK_EXP & 512);
+    const bool lean = !lone && st.vlo == 0u && st.vhi == 0xFFFFFFFFu && P.shard_count <= 1;
     if (lean) {
       // ---- the chunks the ray starts and ends in -> chunk cache, their directory entries requested (DirPeek) ...
       bool fits = false, won_s = false, won_e = false;
@@ -874,14 +862,14 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
       }
       WALK_PROF(0);   // sub-tile set-up: table reset, ray of the point, key origin
       // ---- ... the walk (its set-up arithmetic hides the directory's latency; the slots land before the loop)
-      if (fits && !(PLVS_WALK_EXP & 32)) {
+      if (fits) {
         RayCursor cur;
         ray_begin(ray, &cur);   // (walk_lean's own ray_begin is this one: common subexpression)
         if (won_s && dir_peek_slot(peek_s) >= 0) S.cslot[ci_s] = dir_peek_slot(peek_s);
         if (won_e && dir_peek_slot(peek_e) >= 0) S.cslot[ci_e] = dir_peek_slot(peek_e);
         nv = walk_lean<kAcc, kRuns>(P, pose, ray, S, ox, oy, oz, tid, wu_scaled, q_w, e_wuu, e_wc, e_last, vlog, (uint32_t)tid);
       }
-    } else if (walks && !(PLVS_WALK_EXP & 32)) {   // (bit 32, timing experiment: set-up and flush only)
+    } else if (walks) {
       WALK_PROF(0);
       nv = walk_one(P, pose, ray, st.vlo, st.vhi, [&](uint32_t k, int vx, int vy, int vz, float u) {
         if (!org_set) {   // (one lane only)
@@ -906,9 +894,6 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
       });
     }
     WALK_PROF(1);   // thread 0's own walk
-#if (PLVS_WALK_EXP & 2048)
-    __builtin_amdgcn_s_setprio(3);   // the flush: short dependent phases between barriers — ahead of the other tiles' walks
-#endif
     __syncthreads();
     WALK_PROF(2);   // ... and the wait for the tile's longest ray
     uint32_t ekey[kPer];
@@ -934,10 +919,6 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
     }
     const uint32_t nmine = nv > st.vlo ? nv - st.vlo : 0u;   // this ray's visits in the (sub-)tile
     my_visits += nmine;
-#if (PLVS_WALK_EXP & 16)   // (timing experiment: no flush)
-    ++flushes;
-    continue;
-#endif
 
     // ---- entries -> chunks -> pool slots
     const int fox = S.org[0], foy = S.org[1], foz = S.org[2];   // (a lone ray set them during its walk)
@@ -995,11 +976,7 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
       }
       if (slot_of[k] >= 0) {
         vkey[k] = (uint32_t)slot_of[k] * (uint32_t)kChunkVox + vid;
-#if (PLVS_WALK_EXP & 128)   // (timing experiment: no colour-weight loads)
-        const bool cold = false;
-#else
         const bool cold = sat ? ((sat[vkey[k] >> 5] >> (vkey[k] & 31u)) & 1u) == 0u : (rgbw[vkey[k]] >> 24) < 254u;
-#endif
         if (kRuns && cold) {   // its colour still depends on the order of the visits
           need |= 1u << k;
           ++nneed;
@@ -1092,7 +1069,7 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
 
     ++flushes;
     WALK_PROF(6);   // records
-    if (!kRuns || (PLVS_WALK_EXP & 64)) {   // (bit 64, timing experiment: no runs)
+    if (!kRuns) {
       if (single && !was_split) break;
       continue;
     }
@@ -1281,32 +1258,6 @@ __device__ __forceinline__ void walk_fast_tile(
       S.vis_total = 0;
       S.any_cold = 0;
     }
-#if PLVS_WALK_SORT
-    {
-      // Rays of like length into the same wave: a wave runs its voxel loop as long as its longest ray, and the rays of a
-      // tile (a strip of the image) differ by the depths they end at — the truncation band grows with the square of it.
-      // Counting sort of the tile's rays by depth bucket (12.5 cm), in the visit log's memory (free until the walk); a
-      // thread then walks ray `rid`, and everything that names a ray — the last visitor of an entry, the bits of the
-      // ray masks, the point it reads — names it by rid, so the tile's outputs do not depend on the assignment.
-      uint32_t* const bins = reinterpret_cast<uint32_t*>(vlog) + 256;   // 64 words behind the 512 u16 of the permutation
-      if (tid < 64) bins[tid] = 0u;
-      __syncthreads();
-      int b = 63;
-      uint32_t r = 0;
-      if ((uint32_t)tid < nrays) {
-        const float z = grid ? 0.0f : xyz[3 * (size_t)(first + (uint32_t)tid) + 2];   // (the switch is a cloud-mode experiment)
-        b = z < 0.01f ? 63 : min(62, (int)(z * 8.0f));
-        r = atomicAdd(&bins[b], 1u);
-      }
-      __syncthreads();
-      const uint32_t c = bins[lane];
-      const uint32_t excl = wave_scan_incl(c) - c;   // (every wave scans the 64 bins for itself)
-      const uint32_t start = (uint32_t)__shfl((int)excl, b);
-      if ((uint32_t)tid < nrays) vlog[start + r] = (uint16_t)tid;   // (the permutation lies in front of the bins)
-      __syncthreads();
-      if ((uint32_t)tid < nrays) rid = (uint32_t)vlog[tid];          // (a thread's first log entry is this very slot)
-    }
-#endif
     const Pose& pose = poses[cloud];   // (uniform address: scalar loads where it is used)
     Ray ray;
     walks = (uint32_t)tid < nrays && tile_ray_src(P, xyz, grid, gt, pose, first, rid, &ray, &ctr->err);
@@ -1348,16 +1299,10 @@ __device__ __forceinline__ void walk_fast_tile(
       if (!fits) S.overflow = 1u;   // the rays of the tile are too far apart
     }
     if (fits) {
-#if !(PLVS_WALK_EXP & 32)   // (bit 32, timing experiment: no voxel loop)
       nv = walk_lean<true, true>(P, pose, ray, S, ox, oy, oz, tid, wu * scale_u, (uint32_t)__float2int_rn(wu * scale_w), e_wuu,
                                  e_wc, e_last, vlog, rid);
-#endif
     }
   }
-#if (PLVS_WALK_EXP & 16)   // (bit 16, timing experiment: no flush)
-  if (tid == 0) { out.seg_cnt[tile] = 0; runs.run_cnt[tile] = 0; out.tile_visits[tile] = nv; }
-  return;
-#endif
   uint32_t ekey[kPer];
   WALK_PROF(2);     // the voxel loop of this wave
   if (!defer) {   // entries in use (nobody counts them during the walk)

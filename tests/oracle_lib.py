@@ -744,6 +744,22 @@ def load_hostorb():
     return lib
 
 
+def load_hostplan():
+    """Host (g++) build of plvs_amd/csrc/tsdf_walk_plan.hpp (the order-free integrate's policy)."""
+    src = os.path.join(HOSTCORE_DIR, "walk_plan_host.cpp")
+    hdr = os.path.join(ROOT, "plvs_amd", "csrc", "tsdf_walk_plan.hpp")
+    lib = ctypes.CDLL(_host_build("libhostplan", src, [hdr]))
+    u32 = ctypes.c_uint32
+    lib.hostplan_plan.argtypes = [_vp, _vp]
+    lib.hostplan_plan.restype = None
+    lib.hostplan_sort_kind.argtypes = [u32, u32]
+    lib.hostplan_sort_needs_scan.argtypes = [u32, u32]
+    lib.hostplan_collect_on_own_counts.argtypes = [_vp, u32, u32, u32]
+    lib.hostplan_adapt.argtypes = [_vp, _vp, u32]
+    lib.hostplan_adapt.restype = None
+    return lib
+
+
 def load_hostlines():
     """Host (g++) build of plvs_amd/csrc/lines_host.hpp (the product's sequential line stages)."""
     src = os.path.join(HOSTCORE_DIR, "lines_host.cpp")

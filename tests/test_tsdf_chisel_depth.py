@@ -191,3 +191,71 @@ def test_hip_counter_read_without_polling(spin_us, tmp_path):
                        text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     assert r.stdout.count("chunks") == 2
+
+
+_RIM_SCRIPT = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from tests import oracle_lib
+from tests.plvs_amd_synth import TUM1, make_rgbd_frames
+from tests.test_tsdf_chisel_depth import _clouds, _integrate_depth
+from plvs_amd.tsdf import TsdfChisel
+images, laps = int(sys.argv[2]), int(sys.argv[3])
+oracle = oracle_lib.load()
+grid = oracle.cam_grid_points(640, 480, 2, TUM1["fx"], TUM1["fy"], TUM1["cx"], TUM1["cy"])
+frames = make_rgbd_frames(images, seed=13, holes=True)
+kf = list(range(images))
+clouds = _clouds(oracle, frames, grid, 2, 0.1, 5.0, kf)
+ora = oracle.chisel(0.05)
+dev = TsdfChisel(0.05, max_chunks=8192, order_free=True)
+for lap in range(laps):
+    _integrate_depth(dev, frames, grid, 2, 0.1, 5.0, kf)
+    for c in clouds:
+        ora.integrate(c["xyz"], c["rgb"], c["kfid"], c["Twc"])
+    ids = {tuple(x) for x in ora.chunk_ids()}
+    assert ids == {tuple(x) for x in dev.chunk_ids()}, f"call {lap}: the sets of chunks differ"
+    for cid in sorted(ids):
+        a, b = ora.get_chunk(*cid), dev.get_chunk(*cid)
+        known = a[1] > 0
+        assert np.array_equal(known, b[1] > 0), f"call {lap}: the sets of observed voxels of chunk {cid} differ"
+        assert np.array_equal(a[2], b[2]), f"call {lap}: kfid of chunk {cid}"
+        bad = int((a[3][known] != b[3][known]).sum())
+        assert bad == 0, f"call {lap}: {bad} colours of chunk {cid} differ"
+    print("call", lap, "chunks", len(ids), flush=True)
+dev.close()
+"""
+
+
+@pytest.mark.gpu
+def test_hip_predicted_chain_of_a_mid_size_call_at_the_rim_of_a_saturated_map(tmp_path):
+    """Calls of 20 images (3 000 tiles) over the same view, again and again: the colours saturate, and what is left of the
+    colour runs — the rim of the map, a few thousand — is what the next call's chain is sized by.  A predicted call of
+    2 048 < tiles <= 4 096 whose predecessor left 2 049 ... 9 830 runs sorts them on a bound of 8 192 ... 16 384 with the
+    general chain, whose compaction reads the scanned run counts (sort_kind, tsdf_walk_plan.hpp: the scan is queued exactly
+    when the sort is the general one).  After every call: chunks, observed voxels, kfid and colours of the oracle's
+    sequential integrate of the same images' clouds.  The trace must show that such a call was made.
+    (Before sort_kind decided both sides, such a call was not scanned for — its bound is not above 16 384 — and still took
+    the general chain, for its more than 2 048 tiles: on MI355X the first such call, the 14th here, on an expectation of
+    8 933 runs, ended in an illegal memory access.)"""
+    import os
+    import re
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "rim.py"
+    script.write_text(_RIM_SCRIPT)
+    laps = 16   # (the runs left go 437 661, 82 019, 48 307 ... 9 869, 8 933, 8 129: the 14th call is the first of the kind)
+    r = subprocess.run([sys.executable, str(script), root, "20", str(laps)], env=dict(os.environ, PLVS_HIP_TSDF_TRACE="1"),
+                       capture_output=True, text=True, timeout=1500)
+    calls = [(int(m.group(1)), int(m.group(2)), int(m.group(3)), m.group(4) is not None)
+             for m in re.finditer(r"\[tsdf_chisel\] tiles (\d+) .* runs (\d+) .* chain (\d+)( REPEATED)?", r.stderr)]
+    for c in calls:
+        print("tiles %d runs %d chain %d%s" % (c[0], c[1], c[2], " REPEATED" if c[3] else ""))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    assert r.stdout.count("chunks") == laps and len(calls) == laps
+    reached = 0
+    for prev, cur in zip(calls, calls[1:]):
+        expect = int(float(prev[1]) * float(cur[0]) / float(max(1, prev[0])))   # (E: the call before scaled to this call's tiles)
+        reached += cur[2] == 1 and 2048 < cur[0] <= 4096 and not cur[3] and 2049 <= expect <= 9830
+    assert reached >= 1, "no predicted call of 2 048 < tiles <= 4 096 on an expectation of 2 049 ... 9 830 runs"
