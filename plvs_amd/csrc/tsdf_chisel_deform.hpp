@@ -1,4 +1,5 @@
-// Chisel::Deform on the device (included at the end of tsdf_chisel.hip: it works on the map handle's internals).
+// Chisel::Deform on the device (part of the tsdf_chisel.hip translation unit: it works on the map handle's internals,
+// tsdf_chisel_handle.hpp).
 //
 // Reference: ChunkManager::Deform, Thirdparty/open_chisel/src/ChunkManager.cpp:918-1063, behind Chisel::Deform
 // (Chisel.cpp:588-591) <- ChiselServer::Deform (ChiselServer.cpp:617-621) <- PointCloudMapChisel::OnMapChange.
@@ -25,6 +26,9 @@
 #pragma once
 #include <algorithm>
 #include <unordered_map>
+
+#include "tsdf_chisel_handle.hpp"
+#include "tsdf_chisel_halo.hpp"
 
 namespace {
 

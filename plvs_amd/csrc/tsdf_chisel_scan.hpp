@@ -1,5 +1,5 @@
-// Projective depth + colour scan integrate (included at the end of tsdf_chisel.hip: it works on the map handle's
-// internals and on the carving path's frustum).
+// Projective depth + colour scan integrate (part of the tsdf_chisel.hip translation unit: it works on the map handle's
+// internals, tsdf_chisel_handle.hpp, and on the carving path's frustum, tsdf_chisel_carve.hpp).
 //
 // Reference: PointCloudMapChisel::InsertDepthScanColor (src/PointCloudMapChisel.cc:134-189) ->
 // ChiselServer::IntegrateLastDepthImage (ChiselServer.cpp:632-647) ->
@@ -24,6 +24,9 @@
 //                     fresh voxels alone — so folding every scan over the chunk gives the reference's planes bit for bit.
 // kfid is not written by this integrator.
 #pragma once
+#include "tsdf_chisel_handle.hpp"
+#include "tsdf_chisel_halo.hpp"
+#include "tsdf_chisel_carve.hpp"
 
 namespace {
 

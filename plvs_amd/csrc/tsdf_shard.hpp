@@ -1,5 +1,5 @@
-// Ray-sharded multi-GPU integrate of the open_chisel back end (order-free mode; included by tsdf_chisel.hip
-// after tsdf_walk.hpp).  New design: the reference is a single process.
+// Ray-sharded multi-GPU integrate of the open_chisel back end (order-free mode; kernels — the host side is
+// tsdf_chisel_shard.hpp, which includes this after tsdf_walk.hpp).  New design: the reference is a single process.
 //
 // The map is sharded by chunk (owner = three-prime ChunkHasher mod N, ChunkManager.h:42-54), the WORK by
 // tile of the point stream: rank r walks the tiles t = r (mod N) of every call — its share of the rays,

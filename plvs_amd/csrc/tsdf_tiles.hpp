@@ -4,7 +4,7 @@
 //     decoupled look-back that numbers the runs across tiles;
 //   * the run pipeline behind it: run_counts, mark_blocks, gather_runs (runs -> voxel order),
 //     voxel_heads (voxel list + updated blocks).
-// See the stage description in tsdf_chisel.hip.  Everything lives in an anonymous namespace:
+// See the stage description in tsdf_chisel_ordered.hpp.  Everything lives in an anonymous namespace:
 // each translation unit instantiates its own copy.
 #pragma once
 #include <hip/hip_runtime.h>

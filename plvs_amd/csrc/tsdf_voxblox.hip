@@ -1,7 +1,7 @@
 // TSDF integrate for the voxblox back end (PointCloudMapVoxblox::InsertCloud ->
 // TsdfServer::insertPointCloud -> SimpleTsdfIntegrator::integratePointCloud).
 //
-// Same device pipeline as the chisel path (tsdf_chisel.hip): count -> scan ->
+// Same device pipeline as the chisel path (tsdf_chisel_ordered.hpp): count -> scan ->
 // fill -> stable radix sort by voxel -> expand (order-independent operands) ->
 // chain (one thread folds each voxel's records in the reference's visiting
 // order).  The visiting order is voxblox's ThreadSafeIndex "mixed" order; a
@@ -369,7 +369,7 @@ __device__ unsigned long long g_chain_prof[kProfWaves][4];
 #define CHAIN_PROBE(i)
 #endif
 
-// RN(1/b) for b in [2^-20, 2^40] (tsdf_chisel.hip's rcp_rn: checked for every significand by plvs_hip_selftest_rcp) and
+// RN(1/b) for b in [2^-20, 2^40] (tsdf_chisel_ordered.hpp's rcp_rn: checked for every significand by plvs_hip_selftest_rcp) and
 // RN(a/b) from it (dist_update_rcp's correction step), exact for a = 0 or |a| in [2^-60, 2^60]
 __device__ __forceinline__ float vb_rcp_rn(float b) {
   const float y0 = __builtin_amdgcn_rcpf(b);

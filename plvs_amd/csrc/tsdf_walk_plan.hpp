@@ -1,4 +1,4 @@
-// The policy of the order-free chisel integrate (integrate_walk_acc, tsdf_chisel.hip): every decision of one attempt of a
+// The policy of the order-free chisel integrate (integrate_walk_acc, tsdf_chisel_order_free.hpp): every decision of one attempt of a
 // call as data, made from the call's size and what the handle remembers of the call before.  Plain C++17, no HIP: the
 // driver launches what the plan says, tests/host/walk_plan_host.cpp compiles this header with a host compiler.
 // The measurements behind the thresholds: DESIGN §4.1-4.5.
