@@ -83,6 +83,35 @@ struct DevBuf {
   }
 };
 
+template <typename T>
+static hipError_t grow_keep(DevBuf<T>& b, size_t used, size_t want) {   // reserve() that keeps the first `used` elements
+  if (want <= b.cap) return hipSuccess;
+  DevBuf<T> nb;
+  hipError_t e = nb.reserve(std::max(want, 2 * b.cap));
+  if (e != hipSuccess) return e;
+  if (used) e = hipMemcpy(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) { nb.release(); return e; }
+  b.release();
+  b = nb;
+  return hipSuccess;
+}
+
+// The cloud offsets of a TSDF integrate call (non-null, nclouds >= 0: the caller has checked): nclouds + 1 of them, from 0,
+// non-decreasing.  *n: the call's points.
+static int check_offsets(const int32_t* offsets, int nclouds, int* n) {
+  *n = nclouds > 0 ? offsets[nclouds] - offsets[0] : 0;
+  PLVS_REQUIRE(nclouds == 0 || (offsets[0] == 0 && *n >= 0), "offsets must start at 0 and be non-decreasing");
+  for (int c = 0; c < nclouds; ++c) PLVS_REQUIRE(offsets[c + 1] >= offsets[c], "offsets must be non-decreasing");
+  return PLVS_OK;
+}
+
+// Bits of a voxel key (pool slot * 4096 + voxel) in a TSDF map of `chunks` chunks / blocks: what a sort by voxel has to look at.
+static int voxel_key_bits(long long chunks) {
+  int bits = 12;
+  while ((1ll << (bits - 12)) < chunks) ++bits;
+  return bits;
+}
+
 // Host helper threads kept between calls (the line stage's routing / fitting threads, the ORB quadtree's level threads):
 // creating them per frame cost the calling thread 15-25 us EACH before it could start its own share.
 class HostPool {

@@ -188,19 +188,6 @@ struct plvs_tsdf_chisel {
   int64_t prof_calls = 0;
 };
 
-template <typename T>
-static hipError_t grow_keep(DevBuf<T>& b, size_t used, size_t want) {   // reserve() that keeps the first `used` elements
-  if (want <= b.cap) return hipSuccess;
-  DevBuf<T> nb;
-  hipError_t e = nb.reserve(std::max(want, 2 * b.cap));
-  if (e != hipSuccess) return e;
-  if (used) e = hipMemcpy(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice);
-  if (e != hipSuccess) { nb.release(); return e; }
-  b.release();
-  b = nb;
-  return hipSuccess;
-}
-
 // Every entry point that reads or changes the map integrates the queued key-frame clouds first (plvs_hip_tsdf_chisel_queue).
 extern "C" int plvs_hip_tsdf_chisel_flush(plvs_tsdf_chisel* h);
 #define PLVS_FLUSH_QUEUE(h)                                        \
@@ -302,22 +289,6 @@ static int walk_fail(plvs_tsdf_chisel* h, uint32_t err) {
   plvs::set_error("tsdf_chisel integrate: %s%s(err=%u)", (err & kErrPoolFull) ? "chunk pool full (raise max_chunks) " : "",
                   (err & kErrCoordRange) ? "voxel coordinates beyond +-2^20 (outside the supported map extent) " : "", err);
   return poisoned(h);
-}
-
-// The cloud offsets of a call (non-null, nclouds >= 0: the caller has checked): nclouds + 1 of them, from 0,
-// non-decreasing.  *n: the call's points.
-static int check_offsets(const int32_t* offsets, int nclouds, int* n) {
-  *n = nclouds > 0 ? offsets[nclouds] - offsets[0] : 0;
-  PLVS_REQUIRE(nclouds == 0 || (offsets[0] == 0 && *n >= 0), "offsets must start at 0 and be non-decreasing");
-  for (int c = 0; c < nclouds; ++c) PLVS_REQUIRE(offsets[c + 1] >= offsets[c], "offsets must be non-decreasing");
-  return PLVS_OK;
-}
-
-// Bits of a voxel key (pool slot * 4096 + voxel) in a map of `chunks` chunks: what a sort by voxel has to look at.
-static int voxel_key_bits(long long chunks) {
-  int bits = 12;
-  while ((1ll << (bits - 12)) < chunks) ++bits;
-  return bits;
 }
 
 // ---- stage times (plvs_hip_tsdf_chisel_set_profiling): event i in front of stage i, on the stream the stage runs on, and

@@ -1,4 +1,5 @@
-// Pieces of the tile pipeline shared by the TSDF back ends (tsdf_chisel.hip, tsdf_voxblox.hip):
+// Pieces of the tile pipeline of the chisel TSDF back end (tsdf_chisel_ordered.hpp, tsdf_walk.hpp; the voxblox back end,
+// tsdf_voxblox_kernels.hpp, keeps one record per visit and does not use them):
 //   * the LDS phases of a tile kernel once the visits of the tile sit in LDS — group by voxel
 //     key (hash table), stable radix sort of the (group, slot) tags, run heads — and the
 //     decoupled look-back that numbers the runs across tiles;

@@ -1,6 +1,7 @@
 // FastTsdfIntegrator (Thirdparty/voxblox/src/integrator/tsdf_integrator.cc:505-605; PLVS's YAML default) — which rays of a
-// scan are cast and how far, decided on the device for the reference's ONE-thread schedule.  Included by
-// tsdf_voxblox.hip, which then sends the surviving voxel visits through the ordered pipeline of the simple integrator.
+// scan are cast and how far, decided on the device for the reference's ONE-thread schedule
+// (vb_fast_plan); the surviving voxel visits then go through the ordered pipeline of the simple integrator
+// (tsdf_voxblox_integrate.hpp, mode kFast).  One of the headers of tsdf_voxblox.hip's translation unit.
 //
 // The integrator (per scan, points in the mixed order): a point starts a ray only if no earlier point of the scan lies
 // in the same voxel of HALF the voxel size ("start set"); the ray is cast from its far end towards the sensor and stops
@@ -18,8 +19,13 @@
 // schedule (tests/test_tsdf_voxblox_fast.py runs the same procedure on the CPU against the plain loop).  Rounds needed on depth-camera clouds: 4-15 (40 with carving at 2 cm).  The arrays live on the device with the
 // map, and keep their content from scan to scan as the reference's do.
 #pragma once
+#include <algorithm>
+#include <vector>
+
+#include "tsdf_voxblox_kernels.hpp"
 
 namespace {
+namespace {   // (nested: the kernels keep the symbol names they had inside tsdf_voxblox.hip's own namespace)
 
 constexpr int kApproxBits = 20;
 constexpr uint32_t kApproxMask = (1u << kApproxBits) - 1u;
@@ -215,3 +221,132 @@ __global__ void vbf_publish(const uint32_t* __restrict__ total, const uint32_t* 
 }
 
 }  // namespace
+}  // namespace
+
+// The two approximate sets in their initial state: before a map's first scan and at every full reset.
+static int vb_fast_tables(plvs_tsdf_voxblox* h, hipStream_t s, bool reset) {
+  if (h->ap_ready && !reset) return PLVS_OK;
+  PLVS_HIP_TRY(h->ap_start.reserve(kApproxWords));
+  PLVS_HIP_TRY(h->ap_seen.reserve(kApproxWords));
+  if (!h->h_ff) PLVS_HIP_TRY(hipHostMalloc((void**)&h->h_ff, 2 * sizeof(uint32_t)));
+  hipLaunchKernelGGL(vbf_init_table, dim3(ceil_div(kApproxWords, 256)), dim3(256), 0, s, h->ap_start.p, kApproxWords);
+  hipLaunchKernelGGL(vbf_init_table, dim3(ceil_div(kApproxWords, 256)), dim3(256), 0, s, h->ap_seen.p, kApproxWords);
+  PLVS_KERNEL_CHECK();
+  h->ap_ready = true;
+  return PLVS_OK;
+}
+
+// Which rays of the batch's scans are cast and how many voxels each updates (h->ff_L, per sequence position): the
+// rounds described in tsdf_voxblox_fast.hpp.  The offsets and poses of the call are on the device already.
+static int vb_fast_plan(plvs_tsdf_voxblox* h, const float* d_xyz, int n, int nclouds, const PoseRt* d_poses, uint32_t first_offset,
+                        hipStream_t s) {
+  const unsigned nb = ceil_div((size_t)n, 256);
+  PLVS_HIP_TRY(h->ff_skey0.reserve((size_t)n)); PLVS_HIP_TRY(h->ff_skey1.reserve((size_t)n));
+  PLVS_HIP_TRY(h->ff_sval0.reserve((size_t)n)); PLVS_HIP_TRY(h->ff_sval1.reserve((size_t)n));
+  PLVS_HIP_TRY(h->ff_shash.reserve((size_t)n)); PLVS_HIP_TRY(h->ff_full.reserve((size_t)n));
+  PLVS_HIP_TRY(h->ff_Q.reserve((size_t)n)); PLVS_HIP_TRY(h->ff_L.reserve((size_t)n));
+  PLVS_HIP_TRY(h->ff_qoff.reserve((size_t)n)); PLVS_HIP_TRY(h->ff_flags.reserve(2));
+  PLVS_HIP_TRY(h->scratch.reserve(std::max(radix_scratch_words((size_t)n), scan_scratch_words((size_t)n))));
+  hipLaunchKernelGGL(vbf_start, dim3(nb), dim3(256), 0, s, h->P, d_xyz, n, h->offsets.p, nclouds, d_poses, first_offset,
+                     h->ff_skey0.p, h->ff_sval0.p, h->ff_shash.p, h->ff_full.p, h->d_ctr);
+  PLVS_KERNEL_CHECK();
+  bool second = false;
+  PLVS_HIP_TRY(radix_sort_pairs(h->ff_skey0.p, h->ff_sval0.p, h->ff_skey1.p, h->ff_sval1.p, (size_t)n, 0, kApproxKeyBits,
+                                h->scratch.p, s, &second));
+  const uint32_t* sk = second ? h->ff_skey1.p : h->ff_skey0.p;
+  const uint32_t* sv = second ? h->ff_sval1.p : h->ff_sval0.p;
+  hipLaunchKernelGGL(vbf_alive, dim3(nb), dim3(256), 0, s, sk, sv, (uint32_t)n, h->ff_shash.p, h->ap_start.p, h->ff_full.p, h->ff_Q.p);
+  hipLaunchKernelGGL(vbf_write_back, dim3(nb), dim3(256), 0, s, sk, sv, (uint32_t)n, h->ff_shash.p, h->ap_start.p);
+  PLVS_KERNEL_CHECK();
+  h->fast_rounds = 0;
+  h->fast_sequential = false;
+  PLVS_HIP_TRY(hipMemsetAsync(h->ff_flags.p, 0, 2 * sizeof(uint32_t), s));
+  const uint32_t *qk = nullptr, *qv = nullptr;
+  uint32_t M = 0;
+  for (;;) {
+    // queries of the round; did the round before change anything?
+    PLVS_HIP_TRY(exclusive_scan_u32(h->ff_Q.p, h->ff_qoff.p, (size_t)n, h->ff_flags.p, h->scratch.p, s));
+    hipLaunchKernelGGL(vbf_publish, dim3(1), dim3(1), 0, s, h->ff_flags.p, h->ff_flags.p + 1, h->h_ff);
+    PLVS_KERNEL_CHECK();
+    PLVS_HIP_TRY(hipStreamSynchronize(s));
+    if (h->fast_rounds > 0 && h->h_ff[1] == 0) break;   // (the sorted queries of the last round are the scans' queries)
+    {   // a cloud whose rounds do not settle (one round per ray at worst): finish on one thread, in the reference's own order
+      static const int max_rounds = plvs::env_int("PLVS_VB_FAST_MAX_ROUNDS", 512, 0, 100000);
+      if (h->fast_rounds >= max_rounds) {
+        hipLaunchKernelGGL(vbf_sequential, dim3(1), dim3(1), 0, s, h->P, d_xyz, n, h->offsets.p, nclouds, d_poses, first_offset,
+                           h->ff_Q.p, h->ff_full.p, h->ap_seen.p, h->ff_L.p);
+        PLVS_KERNEL_CHECK();
+        h->fast_sequential = true;
+        return PLVS_OK;   // (the observed set already holds what the queries leave)
+      }
+    }
+    M = h->h_ff[0];
+    ++h->fast_rounds;
+    PLVS_HIP_TRY(hipMemsetAsync(h->ff_flags.p + 1, 0, sizeof(uint32_t), s));
+    if (M == 0) {   // no ray at all: nothing to ask
+      hipLaunchKernelGGL(vbf_trim, dim3(nb), dim3(256), 0, s, n, h->ff_qoff.p, h->ff_full.p, (const uint8_t*)nullptr, h->ff_Q.p,
+                         h->ff_L.p, h->ff_flags.p + 1);
+      PLVS_KERNEL_CHECK();
+      continue;
+    }
+    PLVS_HIP_TRY(h->ff_qkey0.reserve(M)); PLVS_HIP_TRY(h->ff_qkey1.reserve(M));
+    PLVS_HIP_TRY(h->ff_qval0.reserve(M)); PLVS_HIP_TRY(h->ff_qval1.reserve(M));
+    PLVS_HIP_TRY(h->ff_qhash.reserve(M)); PLVS_HIP_TRY(h->ff_seen.reserve(M));
+    PLVS_HIP_TRY(h->scratch.reserve(std::max(radix_scratch_words((size_t)M), scan_scratch_words((size_t)n))));
+    hipLaunchKernelGGL(vbf_emit, dim3(nb), dim3(256), 0, s, h->P, d_xyz, n, h->offsets.p, nclouds, d_poses, first_offset, h->ff_Q.p,
+                       h->ff_qoff.p, h->ff_qkey0.p, h->ff_qval0.p, h->ff_qhash.p);
+    PLVS_KERNEL_CHECK();
+    bool sec = false;
+    PLVS_HIP_TRY(radix_sort_pairs(h->ff_qkey0.p, h->ff_qval0.p, h->ff_qkey1.p, h->ff_qval1.p, (size_t)M, 0, kApproxKeyBits,
+                                  h->scratch.p, s, &sec));
+    qk = sec ? h->ff_qkey1.p : h->ff_qkey0.p;
+    qv = sec ? h->ff_qval1.p : h->ff_qval0.p;
+    hipLaunchKernelGGL(vbf_seen, dim3(ceil_div((size_t)M, 256)), dim3(256), 0, s, qk, qv, M, h->ff_qhash.p, h->ap_seen.p, h->ff_seen.p);
+    hipLaunchKernelGGL(vbf_trim, dim3(nb), dim3(256), 0, s, n, h->ff_qoff.p, h->ff_full.p, h->ff_seen.p, h->ff_Q.p, h->ff_L.p,
+                       h->ff_flags.p + 1);
+    PLVS_KERNEL_CHECK();
+  }
+  if (M > 0 && qk) {
+    hipLaunchKernelGGL(vbf_write_back, dim3(ceil_div((size_t)M, 256)), dim3(256), 0, s, qk, qv, M, h->ff_qhash.p, h->ap_seen.p);
+    PLVS_KERNEL_CHECK();
+  }
+  return PLVS_OK;
+}
+
+// The ordered pipeline (tsdf_voxblox_integrate.hpp, which includes this header for vb_fast_plan).
+static int vb_integrate_impl(plvs_tsdf_voxblox* h, const float* d_xyz, const uint8_t* d_rgba, const int32_t* offsets, int nclouds,
+                             const float* d_Twc, void* stream, int mode, const float* d_aux, const uint8_t* d_clr,
+                             uint32_t fast_offset);
+
+// plvs_hip_tsdf_voxblox_integrate_fast_batch_dev behind its argument checks.
+static int vb_integrate_fast_batches(plvs_tsdf_voxblox* h, const float* d_xyz, const uint8_t* d_rgba, const int32_t* offsets,
+                                     int nclouds, const float* d_Twc, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // Every cloud is a scan, every scan begins with the sets' "reset": offset + 1, and the 10 000th zeroes them
+  // (approx_hash_array.h:141-150).  A batch is cut where that happens.
+  std::vector<int32_t> sub;
+  int c0 = 0;
+  int rounds = 0;
+  plvs_tsdf_stats total{};
+  while (c0 < nclouds) {
+    const bool zero = h->ap_next >= kApproxReset;
+    int rc = vb_fast_tables(h, s, zero);
+    if (rc != PLVS_OK) return rc;
+    if (zero) h->ap_next = 0;
+    const int count = std::min<int>(nclouds - c0, (int)(kApproxReset - h->ap_next));
+    sub.assign((size_t)count + 1, 0);
+    for (int c = 0; c <= count; ++c) sub[(size_t)c] = offsets[c0 + c] - offsets[c0];
+    const size_t p0 = (size_t)offsets[c0];
+    rc = vb_integrate_impl(h, d_xyz ? d_xyz + 3 * p0 : nullptr, d_rgba ? d_rgba + 4 * p0 : nullptr, sub.data(), count,
+                           d_Twc ? d_Twc + 12 * (size_t)c0 : nullptr, stream, kFast, nullptr, nullptr, h->ap_next);
+    if (rc != PLVS_OK) return rc;
+    h->ap_next += (uint32_t)count;
+    c0 += count;
+    rounds = std::max(rounds, h->fast_rounds);
+    total.points += h->stats.points; total.visits += h->stats.visits; total.new_chunks += h->stats.new_chunks;
+    total.updated_chunks = h->stats.updated_chunks; total.voxels = h->stats.voxels; total.max_run = h->stats.max_run;
+  }
+  if (nclouds > 0) h->stats = total;
+  h->fast_rounds = rounds;
+  return PLVS_OK;
+}

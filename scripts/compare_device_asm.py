@@ -7,7 +7,8 @@
 A refactor that moves kernels between files may reorder them, and the compiler numbers its local labels by
 the function's position in the unit.  So: every function (kernel or not) is cut out with its kernel descriptor and
 its resource summary, the per-function index in local labels (.LBB<n>_, .Lfunc_end<n>, BB<n>_ in comments) is
-normalised, and the bodies are compared name by name.  What is left of the file (header, metadata, trailer) must be
+normalised (with the padding in front of a label's comment, which follows the label's width), and the bodies are
+compared name by name.  What is left of the file (header, metadata, trailer) must be
 equal as a multiset of lines; lines naming the per-compilation __hip_cuid_ symbol are dropped.
 
 Prints the kernel count of each file and every function that is missing or differs; exits 1 if anything does.
@@ -18,6 +19,7 @@ import sys
 
 BEGIN = re.compile(r"^\t\.(globl|protected|weak|hidden|p2align)\t([^;]+); -- Begin function (\S+)")
 LOCAL = re.compile(r"(\.LBB|\.Lfunc_end|\.Lfunc_begin|\bBB)\d+")
+LABEL_PAD = re.compile(r"^(\.LBB#_\d+:)\s+;")
 
 
 def split(path):
@@ -41,7 +43,7 @@ def split(path):
                 end += 1
         if name in funcs:
             sys.exit(f"{path}: function {name} appears twice")
-        funcs[name] = [LOCAL.sub(lambda m: m.group(1) + "#", l) for l in lines[first:end]]
+        funcs[name] = [LABEL_PAD.sub(r"\1 ;", LOCAL.sub(lambda m: m.group(1) + "#", l)) for l in lines[first:end]]
         if k + 1 == len(starts):
             rest += lines[end:]
     kernels = sum(1 for l in lines if l.lstrip().startswith(".amdhsa_kernel "))
