@@ -975,7 +975,7 @@ int plvs_hip_elas_create_grid(plvs_elas* e, const int32_t* support, int n_suppor
  * Replaces sgm::StereoSGM as PointCloudKeyFrame::ProcessStereoLibsgm uses it
  * (src/PointCloudKeyFrame.cc:435-481): StereoSGM(width, height, 64, 8, 8, HOST2HOST) with
  * Parameters(P1 = 10, P2 = 120, uniqueness = 0.95f) (Thirdparty/libsgm/include/libsgm.h:62-88),
- * execute(left, right, dst) (src/stereo_sgm.cpp:133-181): census, 8-path aggregation,
+ * execute(left, right, dst) (src/stereo_sgm.cpp:136-182): census, 8-path aggregation,
  * winner-takes-all + uniqueness, 3x3 median, left-right check.  Images are width x height u8,
  * tightly packed; the disparity is u8, 0 = invalid (PLVS: depth = bf / disparity). */
 typedef struct plvs_sgm plvs_sgm;
@@ -984,11 +984,17 @@ int plvs_hip_sgm_create(int width, int height, int disparity_size, int p1, int p
 int plvs_hip_sgm_destroy(plvs_sgm* s);
 /* Host images in, host disparity out; synchronous (EXECUTE_INOUT_HOST2HOST). */
 int plvs_hip_sgm_execute(plvs_sgm* s, const uint8_t* left, const uint8_t* right, uint8_t* disparity);
-/* Device images / disparity (EXECUTE_INOUT_CUDA2CUDA); asynchronous on `stream`. */
+/* Device images / disparity (EXECUTE_INOUT_CUDA2CUDA); asynchronous on `stream`.  The handle owns the working
+ * buffers, so it orders a call after the one before it, whichever streams the two are on: every call ends by
+ * recording an event that the next call's stream waits on.  (The caller still orders its own use of the images
+ * and of d_disparity.) */
 int plvs_hip_sgm_execute_dev(plvs_sgm* s, const uint8_t* d_left, const uint8_t* d_right,
                              uint8_t* d_disparity, void* stream);
 /* Parity accessors of the last call: which = 0 / 1 census left / right (u32 per pixel), 2 summed path
- * costs (u16, width * height * 64), 3 / 4 raw left / right disparity, 5 / 6 after the median (u8). */
+ * costs (u16, width * height * 64), 3 / 4 raw left / right disparity, 5 / 6 after the median (u8), 7 the eight path
+ * volumes one after another (u8, width * height * 64 each; width * height * 64 * 8 bytes) in the reference's order
+ * (PathAggregation::get_output(), path_aggregation.cu:59-82: down, up, right, left, down-right, down-left, up-left,
+ * up-right).  The last call must have finished: execute has; after execute_dev synchronise its stream first. */
 int plvs_hip_sgm_download(plvs_sgm* s, int which, void* out);
 
 /* ------------------------------------------------- depth image -> cloud (T0)

@@ -4,20 +4,21 @@
  * CPU restatement of the dense stereo path PLVS runs through libsgm:
  *   PointCloudKeyFrame::ProcessStereoLibsgm          src/PointCloudKeyFrame.cc:435-481
  *     sgm::StereoSGM(w, h, 64, 8, 8, HOST2HOST), P1 = 10, P2 = 120, uniqueness = 0.95 (libsgm.h:62-70)
- *   StereoSGM::execute                               Thirdparty/libsgm/src/stereo_sgm.cpp:133-181
- *     census_transform_kernel        census_transform.cu:33-101    9 x 7 centre-symmetric census, 31 bits
+ *   StereoSGM::execute                               Thirdparty/libsgm/src/stereo_sgm.cpp:136-182
+ *     census_transform_kernel        census_transform.cu:30-103    9 x 7 centre-symmetric census, 31 bits
  *     DynamicProgramming::update     path_aggregation_common.hpp:45-92   the SGM recurrence, 8 paths
  *       aggregate_{vertical,horizontal,oblique}_path_kernel (start / border rules of the paths)
- *     winner_takes_all_kernel        winner_takes_all.cu:109-236   sum of the 8 paths, best two, uniqueness
+ *     winner_takes_all_kernel        winner_takes_all.cu:110-236   sum of the 8 paths, best two, uniqueness
  *     median_kernel_3x3_8u[_v4]      median_filter.cu:95-189       interior pixels only
- *     check_consistency_kernel       check_consistency.cu:22-37    on the (w/16*16) x (h/16*16) region only
+ *     check_consistency_kernel       check_consistency.cu:21-35    on the (w/16*16) x (h/16*16) region only
  * The reference is CUDA; every stage is integer arithmetic (one float comparison in the uniqueness test),
  * so the result does not depend on how the work is split into threads.
  *
  * One point the reference leaves undefined: the census feature of the 4 / 3-pixel image border is never
- * written (census_transform.cu:71) and the buffer is not cleared (device_buffer.hpp) — taken as 0 here.
- * Parity unpinned: the reference holds no stored output for libsgm (the stored disparities under
- * Thirdparty/libelas-gpu/GPU_test are libelas').
+ * written (census_transform.cu:76) and the buffer is not cleared (device_buffer.hpp:44) — taken as 0 here.
+ * Pinned by libsgm's own kernels, compiled for the CPU and executed by the stand-in of oracle/ref/cuda_shim/
+ * (oracle/_ref/libsgm_ref.so, with that one buffer zeroed: oracle/ref/sgm_zero_malloc.h): every stage below equals
+ * theirs byte for byte (tests/test_oracle_pinned_sgm.py, tests/golden/sgm_reference_digests.json).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -96,7 +97,7 @@ static void aggregate(const uint32_t* left, const uint32_t* right, int w, int h,
   }
 }
 
-static uint32_t compute_disparity(uint32_t v0, uint32_t v1, float uniqueness) {   /* winner_takes_all.cu:94-107 */
+static uint32_t compute_disparity(uint32_t v0, uint32_t v1, float uniqueness) {   /* winner_takes_all.cu:96-108 */
   const float cost0 = (float)(v0 >> 16), cost1 = (float)(v1 >> 16);
   const int disp0 = (int)(v0 & 0xffffu), disp1 = (int)(v1 & 0xffffu);
   if (cost1 * uniqueness >= cost0) return (uint32_t)disp0;
@@ -147,10 +148,11 @@ static void median3x3(const uint8_t* src, int w, int h, uint8_t* dst) {   /* dst
 
 /* left / right: w x h u8 images; disparity: w x h u8 (0 = invalid).  Optional stage outputs for the tests
  * (any may be NULL): census_left, census_right (w*h u32), cost_sum (w*h*64 u16), raw_left, raw_right
- * (before the median), median_left, median_right. */
+ * (before the median), median_left, median_right, paths (the eight path volumes one by one, w*h*64 u8 each, in
+ * PathAggregation::get_output()'s order: path_aggregation.cu:59-82). */
 void oracle_sgm(const uint8_t* left, const uint8_t* right, int w, int h, int p1, int p2, float uniqueness,
                 uint8_t* disparity, uint32_t* census_left, uint32_t* census_right, uint16_t* cost_sum,
-                uint8_t* raw_left, uint8_t* raw_right, uint8_t* median_left, uint8_t* median_right) {
+                uint8_t* raw_left, uint8_t* raw_right, uint8_t* median_left, uint8_t* median_right, uint8_t* paths) {
   const size_t n = (size_t)w * h;
   uint32_t* cl = (uint32_t*)malloc(sizeof(uint32_t) * n);
   uint32_t* cr = (uint32_t*)malloc(sizeof(uint32_t) * n);
@@ -158,7 +160,7 @@ void oracle_sgm(const uint8_t* left, const uint8_t* right, int w, int h, int p1,
   census(right, w, h, cr);
   uint8_t* cost = (uint8_t*)malloc(n * MAX_DISPARITY * NUM_PATHS);
   const size_t step = n * MAX_DISPARITY;
-  static const int dirs[NUM_PATHS][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {-1, 1}, {-1, -1}, {1, -1}};  /* path_aggregation.cu:56-79 */
+  static const int dirs[NUM_PATHS][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {-1, 1}, {-1, -1}, {1, -1}};  /* path_aggregation.cu:59-82 */
   for (int p = 0; p < NUM_PATHS; p++) aggregate(cl, cr, w, h, dirs[p][0], dirs[p][1], (uint32_t)p1, (uint32_t)p2, cost + p * step);
   uint16_t* sum = (uint16_t*)malloc(sizeof(uint16_t) * step);
   uint8_t* dl = (uint8_t*)malloc(n);
@@ -179,6 +181,7 @@ void oracle_sgm(const uint8_t* left, const uint8_t* right, int w, int h, int p1,
   if (census_left) memcpy(census_left, cl, sizeof(uint32_t) * n);
   if (census_right) memcpy(census_right, cr, sizeof(uint32_t) * n);
   if (cost_sum) memcpy(cost_sum, sum, sizeof(uint16_t) * step);
+  if (paths) memcpy(paths, cost, step * NUM_PATHS);
   if (raw_left) memcpy(raw_left, dl, n);
   if (raw_right) memcpy(raw_right, dr, n);
   if (median_left) memcpy(median_left, ml, n);

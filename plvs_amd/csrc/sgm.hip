@@ -2,7 +2,7 @@
 // configurations (BASELINE config 5).
 //
 // Replaces sgm::StereoSGM(w, h, 64, 8, 8, ...)::execute as PointCloudKeyFrame::ProcessStereoLibsgm uses it
-// (src/PointCloudKeyFrame.cc:435-481; Thirdparty/libsgm/src/stereo_sgm.cpp:133-181): 9 x 7 centre-symmetric
+// (src/PointCloudKeyFrame.cc:435-481; Thirdparty/libsgm/src/stereo_sgm.cpp:136-182): 9 x 7 centre-symmetric
 // census (census_transform.cu), the SGM recurrence over 8 paths with P1 / P2 (path_aggregation_common.hpp:45-92
 // and the vertical / horizontal / oblique kernels), winner-takes-all on the summed costs with the uniqueness
 // test for the left and the right view (winner_takes_all.cu), 3 x 3 median of both (median_filter.cu), left-right
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void sgm_census(const uint8_t* __restrict__ sr
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
   uint32_t f = 0;
-  if (x >= 4 && x < w - 4 && y >= 3 && y < h - 3) {   // census_transform.cu:71; the border keeps 0
+  if (x >= 4 && x < w - 4 && y >= 3 && y < h - 3) {   // census_transform.cu:76; the border keeps 0
     for (int dy = -3; dy < 0; ++dy)
 #pragma unroll
       for (int dx = -4; dx <= 4; ++dx) {
@@ -247,6 +247,10 @@ struct plvs_sgm {
   hipStream_t stream = nullptr;
   hipStream_t path_stream[kSideStreams] = {};   // the eight path passes are independent: they run side by side
   hipEvent_t ev_census = nullptr, ev_path[kSideStreams] = {};
+  // The working buffers belong to the handle, not to a call: a call on another stream must not start while the one
+  // before it still reads or writes them.  Recorded at the end of every call; the next call's stream waits on it.
+  hipEvent_t ev_done = nullptr;
+  bool has_done = false;
   uint8_t *d_left = nullptr, *d_right = nullptr, *d_cost = nullptr, *d_dl = nullptr, *d_dr = nullptr, *d_ml = nullptr,
           *d_mr = nullptr, *d_out = nullptr;
   uint32_t *d_cl = nullptr, *d_cr = nullptr;
@@ -266,6 +270,7 @@ int plvs_hip_sgm_destroy(plvs_sgm* s) {
     if (s->ev_path[i]) (void)hipEventDestroy(s->ev_path[i]);
   }
   if (s->ev_census) (void)hipEventDestroy(s->ev_census);
+  if (s->ev_done) (void)hipEventDestroy(s->ev_done);
   delete s;
   return PLVS_OK;
 }
@@ -288,6 +293,7 @@ int plvs_hip_sgm_create(int width, int height, int disparity_size, int p1, int p
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_path[i], hipEventDisableTiming);
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_census, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming);
   auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
   alloc((void**)&s->d_left, n);
   alloc((void**)&s->d_right, n);
@@ -317,13 +323,15 @@ int plvs_hip_sgm_execute_dev(plvs_sgm* s, const uint8_t* d_left, const uint8_t* 
   const int w = s->w, h = s->h;
   const size_t n = (size_t)w * h, step = n * kDisp;
   const dim3 grid2d(plvs::ceil_div((size_t)w, 64), plvs::ceil_div((size_t)h, 4)), block(256);
+  // after the call before this one, whatever stream that was on (the side streams follow through ev_census)
+  if (s->has_done) PLVS_HIP_TRY(hipStreamWaitEvent(st, s->ev_done, 0));
   sgm_census<<<grid2d, block, 0, st>>>(d_left, w, h, s->d_cl);
   sgm_census<<<grid2d, block, 0, st>>>(d_right, w, h, s->d_cr);
   const uint32_t p1 = (uint32_t)s->p1, p2 = (uint32_t)s->p2;
   const unsigned gv = plvs::ceil_div((size_t)w, 4), gh = plvs::ceil_div((size_t)h, 4), go = plvs::ceil_div((size_t)(w + h - 1), 4);
   // A path pass is a chain of dependent steps with at most a wave or two per SIMD: alone it leaves the machine
   // idle.  The eight passes write disjoint volumes, so they run side by side (libsgm does the same,
-  // path_aggregation.cu:56-83) — on FOUR streams, because the runtime feeds the device through four hardware
+  // path_aggregation.cu:59-86) — on FOUR streams, because the runtime feeds the device through four hardware
   // queues and streams beyond that share one (measured with eight: a queue got both 1240-step horizontal passes
   // and a third pass, 605 of the stage's 616 us).  The passes are dealt by their measured lengths: the longest
   // horizontal pass alone on the call's own stream, the other three streams about equal.
@@ -350,6 +358,8 @@ int plvs_hip_sgm_execute_dev(plvs_sgm* s, const uint8_t* d_left, const uint8_t* 
   sgm_median<<<grid2d, block, 0, st>>>(s->d_dr, w, h, s->d_mr);
   sgm_check<<<grid2d, block, 0, st>>>(d_left, s->d_ml, s->d_mr, w, h, d_disparity);
   PLVS_KERNEL_CHECK();
+  PLVS_HIP_TRY(hipEventRecord(s->ev_done, st));
+  s->has_done = true;
   return PLVS_OK;
 }
 
@@ -366,12 +376,14 @@ int plvs_hip_sgm_execute(plvs_sgm* s, const uint8_t* left, const uint8_t* right,
 }
 
 // Parity accessors of the last call: which = 0 census left, 1 census right (u32), 2 cost sums (u16, w*h*64),
-// 3 / 4 raw left / right disparity, 5 / 6 median-filtered left / right (u8).
+// 3 / 4 raw left / right disparity, 5 / 6 median-filtered left / right (u8), 7 the eight path volumes one after
+// another (u8, w*h*64 each) in the reference's order (path_aggregation.cu:59-82: down, up, right, left, down-right,
+// down-left, up-left, up-right).  The call must have finished (execute does; after execute_dev synchronise its stream).
 int plvs_hip_sgm_download(plvs_sgm* s, int which, void* out) {
-  PLVS_REQUIRE(s && out && which >= 0 && which <= 6, "bad argument");
+  PLVS_REQUIRE(s && out && which >= 0 && which <= 7, "bad argument");
   const size_t n = (size_t)s->w * s->h;
-  const void* src[] = {s->d_cl, s->d_cr, s->d_sum, s->d_dl, s->d_dr, s->d_ml, s->d_mr};
-  const size_t bytes[] = {n * 4, n * 4, n * kDisp * 2, n, n, n, n};
+  const void* src[] = {s->d_cl, s->d_cr, s->d_sum, s->d_dl, s->d_dr, s->d_ml, s->d_mr, s->d_cost};
+  const size_t bytes[] = {n * 4, n * 4, n * kDisp * 2, n, n, n, n, n * kDisp * kPaths};
   PLVS_HIP_TRY(hipMemcpy(out, src[which], bytes[which], hipMemcpyDeviceToHost));
   return PLVS_OK;
 }

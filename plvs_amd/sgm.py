@@ -54,17 +54,20 @@ class StereoSGM:
         return out
 
     def execute_dev(self, d_left, d_right, d_disparity):
-        """torch uint8 CUDA tensors [height, width]; asynchronous on the current stream."""
+        """torch uint8 CUDA tensors [height, width]; asynchronous on the current stream.  Calls on one handle are ordered
+        one after another by the handle, whichever streams they are on."""
         _lib.check(L.plvs_hip_sgm_execute_dev(self._h, _lib.t_ptr(d_left), _lib.t_ptr(d_right), _lib.t_ptr(d_disparity),
                                               _lib.current_stream_ptr()))
 
     def stage(self, which):
         """Parity accessor of the last call: 'census_left', 'census_right', 'cost_sum', 'raw_left', 'raw_right',
-        'median_left', 'median_right'."""
-        code = ["census_left", "census_right", "cost_sum", "raw_left", "raw_right", "median_left", "median_right"].index(which)
-        n = self.width * self.height
+        'median_left', 'median_right', 'paths' (the eight path volumes [8, height, width, 64] uint8 in the reference's
+        order).  The call must have finished (after execute_dev: synchronise its stream first)."""
+        code = ["census_left", "census_right", "cost_sum", "raw_left", "raw_right", "median_left", "median_right",
+                "paths"].index(which)
         out = (np.empty((self.height, self.width), np.uint32) if code < 2 else
                np.empty((self.height, self.width, 64), np.uint16) if code == 2 else
+               np.empty((8, self.height, self.width, 64), np.uint8) if code == 7 else
                np.empty((self.height, self.width), np.uint8))
         _lib.check(L.plvs_hip_sgm_download(self._h, code, _lib.np_ptr(out)))
         return out

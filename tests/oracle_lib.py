@@ -86,7 +86,8 @@ class Oracle:
 
     # ------------------------------------------------------------ dense stereo (libsgm)
     def sgm(self, left, right, p1=10, p2=120, uniqueness=0.95, stages=False):
-        """-> disparity [h, w] u8, or (disparity, dict of stage arrays) with stages=True."""
+        """-> disparity [h, w] u8, or (disparity, dict of stage arrays) with stages=True ("paths": the eight path
+        volumes [8, h, w, 64] u8 in the reference's order)."""
         left = np.ascontiguousarray(left, dtype=np.uint8)
         right = np.ascontiguousarray(right, dtype=np.uint8)
         h, w = left.shape
@@ -96,11 +97,11 @@ class Oracle:
             st = dict(census_left=np.zeros((h, w), np.uint32), census_right=np.zeros((h, w), np.uint32),
                       cost_sum=np.zeros((h, w, 64), np.uint16), raw_left=np.zeros((h, w), np.uint8),
                       raw_right=np.zeros((h, w), np.uint8), median_left=np.zeros((h, w), np.uint8),
-                      median_right=np.zeros((h, w), np.uint8))
+                      median_right=np.zeros((h, w), np.uint8), paths=np.zeros((8, h, w, 64), np.uint8))
         f = self.lib.oracle_sgm
         f.restype = None
-        f.argtypes = [_vp, _vp, _i, _i, _i, _i, _f] + [_vp] * 8
-        order = ["census_left", "census_right", "cost_sum", "raw_left", "raw_right", "median_left", "median_right"]
+        f.argtypes = [_vp, _vp, _i, _i, _i, _i, _f] + [_vp] * 9
+        order = ["census_left", "census_right", "cost_sum", "raw_left", "raw_right", "median_left", "median_right", "paths"]
         f(_ptr(left), _ptr(right), w, h, p1, p2, uniqueness, _ptr(disp), *[_ptr(st[k]) if stages else None for k in order])
         return (disp, st) if stages else disp
 
@@ -765,6 +766,34 @@ def load_hostlines():
     src = os.path.join(HOSTCORE_DIR, "lines_host.cpp")
     hdr = os.path.join(ROOT, "plvs_amd", "csrc", "lines_host.hpp")
     return ctypes.CDLL(_host_build("libhostlines", src, [hdr]))
+
+
+def load_hostcudashim():
+    """Host build of tests/host/cuda_shim_host.cu — test kernels of our own — against the CUDA stand-in that executes
+    libsgm's kernels for oracle/_ref/libsgm_ref.so (oracle/ref/cuda_shim/): the launches are rewritten by the same sed
+    script and with the same flags as oracle/ref/Makefile uses.  Needs nothing of the reference."""
+    shim = os.path.join(ORACLE_DIR, "ref", "cuda_shim")
+    src = os.path.join(HOSTCORE_DIR, "cuda_shim_host.cu")
+    deps = [src] + [os.path.join(shim, f) for f in ("cuda_runtime.h", "cuda_shim.cpp", "launch_rewrite.sed")]
+    so = os.path.join(HOSTCORE_DIR, "libhostcudashim.so")
+    if not os.path.exists(so) or max(os.path.getmtime(f) for f in deps) > os.path.getmtime(so):
+        gen = os.path.join(HOSTCORE_DIR, "cuda_shim_host.gen.cpp")
+        with open(gen, "w") as f:
+            subprocess.run(["sed", "-E", "-f", os.path.join(shim, "launch_rewrite.sed"), src], check=True, stdout=f)
+        with open(gen) as f:
+            assert f.read().count("cuda_shim::launch(") == 6, "launch sites of cuda_shim_host.cu"
+        subprocess.run(["g++", "-O2", "-std=c++14", "-fPIC", "-shared", "-ffp-contract=off", "-fno-strict-aliasing", "-w",
+                        "-DCUDA_VERSION=9000", "-I" + shim, gen, os.path.join(shim, "cuda_shim.cpp"), "-o", so], check=True)
+    lib = ctypes.CDLL(so)
+    lib.shimtest_shfl.argtypes = [_vp, _i, ctypes.c_uint, _i]
+    lib.shimtest_packed.argtypes = [_vp, _vp, _vp, _i]
+    for f in (lib.shimtest_exchange, lib.shimtest_early_exit, lib.shimtest_dead_lane, lib.shimtest_outside_mask):
+        f.argtypes = [_vp]
+    lib.shimtest_malloc_byte.argtypes = [_i]
+    lib.shimtest_malloc_byte.restype = ctypes.c_uint
+    lib.cuda_shim_set_fill.argtypes = [_i]
+    lib.cuda_shim_undefined_shuffles.restype = ctypes.c_ulong
+    return lib
 
 
 def load():
