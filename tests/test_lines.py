@@ -144,6 +144,23 @@ def test_hip_lines_device_input_resize_and_empty(oracle):
     kl0, d0 = dev(flat)
     assert len(kl0) == 0 and d0.shape == (0, 32)
     dev.close()
+    # the setting above has nfeatures = 0: nothing is sorted before the min-length cut, which then stops at the first short
+    # line — one KeyLine on `cones`.  A non-default octave count and scale with nfeatures > 0, from device input, with the
+    # maps of all four octaves (the oracle gives 100 lines here, in the four octaves 24 / 43 / 22 / 11)
+    dev = LineExtractor(100, LSDOptions(numOctaves=4, scale=1.5, lineFitErrThreshold=2.5))
+    ora = oracle.lines(nfeatures=100, nlevels=4, scale=1.5, fit_err=2.5)
+    okl, odesc = ora.extract(img)
+    assert len(okl) >= 20 and len(np.unique(okl["octave"])) == 4
+    kl, desc = dev(torch.from_numpy(img).cuda())
+    for o in range(4):
+        for which in ("blur", "dx", "dy"):
+            assert np.array_equal(dev.octave_map(o, which), ora.octave_map(o, which)), f"{which} octave {o}"
+        gd = dev.octave_map(o, "gd")
+        assert np.array_equal((gd & 0x1ff).astype(np.int16), ora.octave_map(o, "g")), f"gradient octave {o}"
+        assert np.array_equal(np.where(gd & 0x8000, 255, 0), ora.octave_map(o, "dir")), f"direction octave {o}"
+        assert dev.num_in_octave(o) == ora.num_in_octave(o), f"segments in octave {o}"
+    assert kl.tobytes() == okl.tobytes() and np.array_equal(desc, odesc)
+    dev.close()
 
 
 @pytest.mark.gpu

@@ -15,6 +15,10 @@ statement these tests make is: oracle/orb.cpp and oracle/lines.cpp equal the ref
  * CPU, always: the restatements reproduce tests/golden/frontend_reference_digests.json, the digests the compiled
    reference produced (scripts/make_frontend_golden.py) — the fallback where oracle/_ref is absent.
  * GPU: the HIP path reproduces the same file through the C ABI.
+ * The geometry cases of tests/frontend_cases.py (shipped sizes and settings, cell / tile edges, saturated and low-contrast
+   contents): CPU, always — the floors that keep them from comparing nothing hold on the restatement; CPU, needs
+   oracle/_ref — the restatement equals the compiled reference on every one of them.  tests/test_frontend_geometry.py
+   runs the HIP path over the same table: reference -> restatement -> HIP is closed for each shape.
 Nothing here reads /root/reference at run time."""
 import ctypes
 import json
@@ -23,6 +27,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import frontend_cases as C
 from tests import frontend_golden_scenario as S
 from tests import oracle_lib
 from tests.oracle_lib import KP_DTYPE, OracleLines, OracleOrb, golden
@@ -198,6 +203,72 @@ def test_lines_on_the_orb_pyramid_equal_the_reference(oracle, name):
     rk, rd = ref_extractors()[2](img)
     ok, od = oracle_extractors(oracle)[2](img)
     assert len(rk) > 5 and rk.tobytes() == ok.tobytes() and np.array_equal(rd, od)
+
+
+# ------------------------------------------------------------------ the geometry cases (tests/frontend_cases.py)
+def test_geometry_case_floors_hold_on_the_oracle(oracle):
+    for case in C.ORB_CASES:
+        C.check_orb_floor(case, C.oracle_orb(oracle, case))
+    for case in C.LINE_CASES:
+        C.check_lines_floor(case, oracle.lines(**C.LINE_SETTINGS[case.setting]).extract(C.image(case.image))[0])
+
+
+@needs_ref
+@pytest.mark.parametrize("case", C.ORB_CASES, ids=[c.id for c in C.ORB_CASES])
+def test_orb_geometry_case_equals_the_reference(oracle, case):
+    """(66x66: the reference's column count is 0 there and its float division gives an infinite cell width; it returns
+    cleanly with no key point, so the case stays.)"""
+    names = _ref()
+    r, o = _RefOrb(names, *case.settings), C.oracle_orb(oracle, case)
+    C.check_orb_floor(case, o)
+    nl = case.settings[2]
+    assert list(r.features_per_level()) == list(o.features_per_level)
+    t = [np.zeros(nl, np.float32) for _ in range(4)]
+    names.ref_orb_scale_tables.argtypes = [ctypes.c_void_p] * 5
+    assert names.ref_orb_scale_tables(r.h, *[x.ctypes.data for x in t]) == nl
+    for got, want in zip(t, C.scale_tables(case.settings)):
+        assert got.tobytes() == want.tobytes(), f"{case.id}: scale tables"
+    rm, rk, rd = r.extract(C.image(case.image))
+    assert rm == o.mono and _same_kps(rk, o.kps), f"{case.id}: key points differ"
+    assert np.array_equal(rd, o.desc), f"{case.id}: descriptor bits differ"
+    for lv in range(nl):
+        assert np.array_equal(r.level(lv), o.levels[lv]), f"{case.id}: pyramid level {lv}"
+        if o.blurred[lv] is not None:
+            assert np.array_equal(r.level(lv, True), o.blurred[lv]), f"{case.id}: blurred level {lv}"
+
+
+@needs_ref
+def test_orb_lapping_area_at_752x480_equals_the_reference(oracle):
+    case = C.orb_case("aloe_752x480")
+    o = C.oracle_orb(oracle, case, lap=(250, 500))
+    rm, rk, rd = _RefOrb(_ref(), *case.settings).extract(C.image(case.image), (250, 500))
+    assert 100 < rm < len(rk) - 100
+    assert rm == o.mono and _same_kps(rk, o.kps) and np.array_equal(rd, o.desc)
+
+
+@needs_ref
+@pytest.mark.parametrize("case", C.LINE_CASES, ids=[c.id for c in C.LINE_CASES])
+def test_lines_geometry_case_equals_the_reference(oracle, case):
+    kw = C.LINE_SETTINGS[case.setting]
+    r, o = OracleLines(_ref(), **kw), oracle.lines(**kw)
+    rk, rd = r.extract(C.image(case.image))
+    ok, od = o.extract(C.image(case.image))
+    C.check_lines_floor(case, ok)
+    assert len(rk) == len(ok) and rk.tobytes() == ok.tobytes(), f"{case.id}: KeyLine records differ"
+    assert np.array_equal(rd, od), f"{case.id}: LBD bits differ"
+    for oc in range(kw["nlevels"]):
+        assert r.octave_size(oc) == o.octave_size(oc)
+        assert r.num_in_octave(oc) == o.num_in_octave(oc), f"{case.id}: segments in octave {oc}"
+        for which in ("dx", "dy"):
+            assert np.array_equal(r.octave_map(oc, which), o.octave_map(oc, which)), f"{case.id}: {which} octave {oc}"
+
+
+@needs_ref
+def test_lines_on_the_orb_pyramid_at_752x480_equal_the_reference(oracle):
+    img = C.image("aloe_752x480")
+    rk, rd = ref_extractors()[2](img)
+    ok, od = oracle_extractors(oracle)[2](img)
+    assert len(rk) >= 90 and rk.tobytes() == ok.tobytes() and np.array_equal(rd, od)
 
 
 # ------------------------------------------------------------------ the committed digests
