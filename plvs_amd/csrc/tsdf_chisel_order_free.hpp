@@ -36,12 +36,16 @@ __global__ void walk_prologue(const float* __restrict__ Twc, int nclouds, Pose* 
 
 // ------------------------------------------------------------------ single-walk pipeline (tsdf_walk.hpp)
 constexpr unsigned kDeferGrid = 1024;   // workgroups of the general walk over the deferred tiles (it loops over the list)
-// The lean walk comes with two table sizes (tsdf_walk.hpp, FastShared): 2048 entries at two tiles per CU for a call that
+// The lean walk comes with three table sizes (tsdf_walk.hpp, FastShared): 2048 entries at two tiles per CU for a call that
 // fills the device, 4096 entries at one tile per CU for the tiles that overflowed 2048 — a dozen in a hundred on an office
 // scene with points up to 5 m away — and for every tile of a call of at most kSmallCallTiles tiles (a few key frames: one
-// tile per CU is all there is to run, and a deferral costs such a call a second walk's latency).  A tile owns
+// tile per CU is all there is to run, and a deferral costs such a call a second walk's latency); and the small table of
+// the first pass over near surfaces, kFastEntriesSmall (tsdf_walk.hpp) = 1536 entries at three tiles per CU.  A tile owns
 // kRecStride records (the larger table's limit) in the record buffer.
-constexpr int kFastEntriesSmall = 1024, kFastEntries = 2048, kFastEntriesBig = 4096;
+// The plan (tsdf_walk_plan.hpp) names a pass by its table CLASS: `entries` 1024 = the small class, whatever the small
+// table's size has become — launch_walk_passes launches the kFastEntriesSmall instance for it.
+constexpr int kPlanSmallClass = 1024, kFastEntries = 2048, kFastEntriesBig = 4096;
+static_assert(kFastEntriesSmall > kPlanSmallClass && kFastEntriesSmall < kFastEntries, "the small table lies between its class name and the next table");
 constexpr uint32_t kRecStride = kFastEntriesBig * 7 / 8;
 static_assert(kRecStride == (uint32_t)kWalkLimit, "a tile's record region holds a flush of the largest table");
 static_assert(kSortSmallRuns == kSmallRuns && kSortMediumRuns <= kMediumRuns && kCollectPartRuns == kCollectPart &&
@@ -251,7 +255,8 @@ static void launch_walk_fast(plvs_tsdf_chisel* h, const WalkCall& c, const WalkP
 static void launch_walk_passes(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkCall& c, hipStream_t s) {
   for (int i = 0; i < plan.npasses; ++i) {
     const WalkPass& pass = plan.pass[i];
-    if (pass.entries == kFastEntriesSmall) launch_walk_fast<kFastEntriesSmall>(h, c, pass, s);
+    // (the plan's 1024 is the small CLASS, not a size: see kPlanSmallClass)
+    if (pass.entries == kPlanSmallClass) launch_walk_fast<kFastEntriesSmall>(h, c, pass, s);
     else if (pass.entries == kFastEntries) launch_walk_fast<kFastEntries>(h, c, pass, s);
     else launch_walk_fast<kFastEntriesBig>(h, c, pass, s);
   }

@@ -37,6 +37,7 @@
 #include "tsdf_chisel_core.hpp"
 #include "tsdf_directory.hpp"
 #include "tsdf_tiles.hpp"
+#include "tsdf_walk_table.hpp"
 
 namespace {
 
@@ -49,6 +50,8 @@ using plvs::tsdf::kCoordBias;
 using plvs::tsdf::kErrCoordRange;
 using plvs::tsdf::kErrDirectoryMiss;
 using plvs::tsdf::kErrPoolFull;
+using plvs::tsdf::home_bucket;
+using plvs::tsdf::next_bucket;
 
 constexpr int kWalkRays = 512;                  // rays (= threads) per tile
 constexpr int kMaskWords = kWalkRays / 32;      // a run's ray mask
@@ -57,8 +60,8 @@ constexpr int kMaskWords = kWalkRays / 32;      // a run's ray mask
 // the voxel size); with 1024 entries half the tiles of a real office scene overflowed and took the slow general path
 // (rounds 1-3 only ever measured a 6 x 4 m room, depths below 3 m: 300 - 600 voxels per tile).
 // (this constant: the table of the GENERAL kernel, walk_tiles — one tile per CU; the lean kernel walk_fast<E> takes its
-// table size as a template parameter: 2048 entries at two tiles per CU for the bulk of a long call, 4096 for the tiles
-// that overflow that)
+// table size as a template parameter: 1536 entries at three tiles per CU or 2048 at two for the bulk of a long call, 4096
+// for the tiles that overflow that)
 #ifndef PLVS_WALK_ENTRIES
 #define PLVS_WALK_ENTRIES 4096
 #endif
@@ -108,15 +111,15 @@ struct WalkCounters {           // device-side, read back once per call
   uint32_t num_multi;           //   chunks applied in more than one part
   uint32_t ndeferred;           // tiles walk_fast left to the next kernel (several clouds in the tile, table overflow)
   uint32_t ndeferred2;          //   and what the larger-table pass over that list left to walk_tiles
-  uint32_t over_small;          // tiles of a 2048-entry first pass that a 1024-entry table would not have held
+  uint32_t over_small;          // tiles of a 2048-entry first pass that the small table (kFastEntriesSmall) would not have held
   uint32_t skip;                // colour side: a chain launched on predicted sizes found them too small (compact_runs)
   uint32_t collect_top;         // colour side: runs given a place by runs_rowscan (the regions of the (chunk, slab) rows)
   uint32_t collect_parts;       //   and the parts of kCollectPart runs these regions are sorted in
-  uint32_t ndeferred3;          // what a third pass (4096 entries, behind a 1024- and a 2048-entry one) left to walk_tiles
+  uint32_t ndeferred3;          // what a third pass (4096 entries, behind the small table's and a 2048-entry one) left to walk_tiles
 };
 
 // ------------------------------------------------------------------ the walk of one (sub-)tile
-constexpr int kLogLen = 16;                      // visits per ray kept in the tile's visit log
+constexpr int kLogLen = 16;                      // visits per ray kept in the tile's visit log (a table may keep fewer: SH::kLogLen)
 constexpr int kSlabs = 8;                        // a chunk is applied in slabs of kSlabVox voxels
 constexpr int kSlabVox = kChunkVox / kSlabs;
 
@@ -136,7 +139,7 @@ constexpr int kOriginBias = 512;
 
 constexpr int log2_of(int v) { return v <= 1 ? 0 : 1 + log2_of(v / 2); }
 struct WalkShared {       // LDS state of walk_tiles
-  static constexpr int kEntries = kWalkEntries, kBucketCount = kWalkEntries / 4, kBucketShift = 32 - log2_of(kWalkEntries / 4);
+  static constexpr int kEntries = kWalkEntries, kBucketCount = kWalkEntries / 4, kLogLen = ::kLogLen;
   alignas(16) uint32_t ekey[kWalkEntries];
   int32_t org[3];                              // origin of the keys
   uint32_t cand[kWalkRays / 64];               // does the wave have a walking ray ...
@@ -154,21 +157,27 @@ struct WalkShared {       // LDS state of walk_tiles
   uint32_t wsum[kWalkRays / 64];
   uint32_t next, nrays;   // rays of the tile not yet handed out as sub-tiles / rays of the tile
 };
-// LDS state of walk_fast<E>: WalkShared without the sub-tile stack, the table size a template parameter (E = 2048: two
-// tiles per CU, the kernel of a long call; E = 4096: one tile per CU — the tiles that overflowed 2048 entries, and
-// every tile of a call too short to fill the device, where the occupancy is immaterial and a deferral is not)
+// LDS state of walk_fast<E>: WalkShared without the sub-tile stack, the table size a template parameter (E = 1536: three
+// tiles per CU, the first pass over a scene of near surfaces; E = 2048: two tiles per CU, the kernel of a long call;
+// E = 4096: one tile per CU — the tiles that overflowed 2048 entries, and every tile of a call too short to fill the
+// device, where the occupancy is immaterial and a deferral is not).  E need not be a power of two: every thread owns
+// E / kWalkRays entries, a bucket has four (home_bucket / next_bucket, tsdf_walk_table.hpp).
+// The LDS of a CU is handed out in blocks of 1280 B (gfx950): a 1536-entry tile with the visit log of the others would
+// take 54 176 B = 43 blocks, and three of them 129 of the CU's 128.  Its log keeps 15 visits per ray instead of 16
+// (53 152 B, 42 blocks): a ray with more visits walks again for its masks, as it does behind any full log — the same
+// masks, the same map.
 template <int E>
 struct FastShared {
-  static constexpr int kEntries = E, kBucketCount = E / 4, kBucketShift = 32 - log2_of(E / 4);
-  static_assert((E & (E - 1)) == 0 && E >= 1024, "power-of-two table");
+  static constexpr int kEntries = E, kBucketCount = E / 4, kLogLen = E == 1536 ? ::kLogLen - 1 : ::kLogLen;
+  static_assert(E % kWalkRays == 0 && E >= 1024, "every thread owns E / kWalkRays entries (and a bucket four)");
   alignas(16) uint32_t ekey[E];
   uint32_t cand[kWalkRays / 64];
   int32_t worg[kWalkRays / 64][3];
   uint32_t run_total, vis_total;
   uint32_t ccode[kWalkChunks];
   int32_t cslot[kWalkChunks];
-  uint32_t ccnt[kWalkChunks * kSlabs];
-  uint16_t cbase[kWalkChunks * kSlabs];
+  uint32_t ccnt[kWalkChunks * kSlabs];    // (ccnt and cbase stay neighbours: once the records are out their words hold the
+  uint16_t cbase[kWalkChunks * kSlabs];   //  entries' mask indices, walk_fast_tile)
   uint32_t rcnt[kWalkChunks * kSlabs];    // runs of the (chunk, slab) group
   uint16_t rcbase[kWalkChunks * kSlabs];  // the group's first run among the tile's (every wave writes the same table)
   uint32_t any_cold;                      // a voxel of the tile needs a run
@@ -197,16 +206,15 @@ __device__ __forceinline__ void chunk_of_code(uint32_t code, int ox, int oy, int
   *cz = (oz >> 4) + (int)((code >> 24) & 63u);
 }
 // The table stores a voxel key MULTIPLIED by an odd constant ("table key", a bijection of the 32-bit words): its top
-// eight bits are the home bucket, and since the walk moves the key by one of three constants per voxel step the
+// bits are the home bucket (a table of 384 buckets: the high word of table key x 384), and since the walk moves the key by one of three constants per voxel step the
 // table key moves by one of three constants too — the voxel loop carries the table key alone and never multiplies
 // (v_mul_lo_u32 issues at a quarter of the rate of an add).  No voxel key maps to kKeyEmpty (0xF174D0AF would: keys
 // have 30 bits).
-constexpr uint32_t kKeyMul = 2654435761u, kKeyMulInv = 0x0E8B2F51u;
-static_assert((uint32_t)(kKeyMul * kKeyMulInv) == 1u, "inverse of the table-key multiplier");
+constexpr uint32_t kKeyMul = plvs::tsdf::kTableKeyMul, kKeyMulInv = plvs::tsdf::kTableKeyMulInv;
 __device__ __forceinline__ uint32_t table_key(uint32_t key) { return key * kKeyMul; }
 __device__ __forceinline__ uint32_t voxel_key(uint32_t tkey) { return tkey * kKeyMulInv; }
 template <class SH>
-__device__ __forceinline__ uint32_t key_bucket(uint32_t tkey) { return tkey >> SH::kBucketShift; }
+__device__ __forceinline__ uint32_t key_bucket(uint32_t tkey) { return home_bucket<SH::kBucketCount>(tkey); }
 
 // Inclusive prefix sum over the 64 lanes of a wave by DPP (row shifts inside the rows of 16, then the row broadcasts):
 // six VALU instructions, no LDS traffic (a __shfl_up is a ds_bpermute_b32 through the LDS crossbar).
@@ -237,7 +245,7 @@ __device__ __forceinline__ int bucket_match(const uint4 k4, uint32_t want) {
 // a first touch (the bucket, the compare-and-swap): every wave step of the walk has a few lanes on this path and
 // the step is as slow as its slowest lane.  Entries are not counted here — the flush counts them (entries beyond
 // kWalkLimit: the (sub-)tile is cut, as when the table is full).
-constexpr int kProbeCap = 24;
+constexpr int kProbeCap = plvs::tsdf::kTableProbeCap;
 template <class SH>
 __device__ __forceinline__ int table_find_or_insert(SH& S, uint32_t key /* a table key */) {
   uint32_t b = key_bucket<SH>(key);
@@ -254,7 +262,7 @@ __device__ __forceinline__ int table_find_or_insert(SH& S, uint32_t key /* a tab
       if (old == kKeyEmpty || old == key) return (int)(4 * b) + je;
       continue;   // another voxel took the slot: look at this bucket again
     }
-    b = (b + 1) & (SH::kBucketCount - 1);
+    b = next_bucket<SH::kBucketCount>(b);
   }
   S.overflow = 1u;
   return -1;
@@ -266,7 +274,7 @@ __device__ __forceinline__ int table_find(const SH& S, uint32_t key) {
   for (int probe = 0; probe < SH::kBucketCount; ++probe) {
     const int j = bucket_match(*reinterpret_cast<const uint4*>(&S.ekey[4 * b]), key);
     if (j >= 0) return (int)(4 * b) + j;
-    b = (b + 1) & (SH::kBucketCount - 1);
+    b = next_bucket<SH::kBucketCount>(b);
   }
   return -1;
 }
@@ -451,7 +459,7 @@ __device__ __forceinline__ uint32_t walk_lean(const Params& P, const Pose& pose,
         }
       }
       if (__builtin_expect(e < 0, 0)) break;   // the table is full: the (sub-)tile is cut
-      if (kRuns && vp < (uint32_t)(kLogLen * kWalkRays * sizeof(uint16_t)))
+      if (kRuns && vp < (uint32_t)(SH::kLogLen * kWalkRays * sizeof(uint16_t)))
         *reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(vlog) + vp) = (uint16_t)e;
       if (kAcc) {
         atomicAdd(&e_wuu[e], __float2int_rn(wu_scaled * u));
@@ -1207,7 +1215,11 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
 // earlier launch left (entries with bit 31: tiles that overflowed ITS table — the others are not this kernel's case
 // either and go straight on to `deferred`), *ntile_list of them.  rec_stride = records a tile owns in out.rec (the
 // host sizes the regions for the largest table it launches).
-constexpr int walk_fast_waves(int E) { return E > 2048 ? 2 : (E > 1024 ? 4 : 6); }   // waves per SIMD the tile's LDS allows
+constexpr int walk_fast_waves(int E) { return E > 2048 ? 2 : (E > 1536 ? 4 : 6); }   // waves per SIMD the tile's LDS allows
+// The table of the first pass over a scene of near surfaces — the pass the plan calls `entries = 1024`, its small class
+// (tsdf_walk_plan.hpp; launch_walk_passes maps the class to this instance): half as large again as 1024 entries at the same
+// three tiles per CU, so that a tile of 900 - 1 340 voxels is walked once instead of being deferred and walked again.
+constexpr int kFastEntriesSmall = 1536;
 template <int E, bool kGrid>
 __device__ __forceinline__ void walk_fast_tile(
     const Params& P, float scale_u, float scale_w, const float* __restrict__ xyz, int npoints,
@@ -1221,12 +1233,15 @@ __device__ __forceinline__ void walk_fast_tile(
   constexpr int kPer = E / kWalkRays;
   constexpr int kLimit = E * 7 / 8;          // entries a tile may use (kWalkLimit of the general kernel's table)
   constexpr int kMaskCapE = E / 4;           // ray masks built per round: the area of the accumulators
+  constexpr int kLogLen = FastShared<E>::kLogLen;   // (visits per ray in the log of THIS table's tiles)
+  static_assert(kMaskCapE * kMaskWords % kWalkRays == 0, "the mask area is cleared by whole rounds of the tile's threads");
   __shared__ FastShared<E> S;
   __shared__ uint32_t raw[4 * E];                              // accumulators during the walk, ray masks afterwards
   __shared__ uint16_t vlog[kLogLen * kWalkRays];        // entry of visit k of ray r at [k * kWalkRays + r]
-  // mask index of the entry (0xFFFF: none) — in the words of the (chunk, slab) counters, dead once the records are out,
-  // where they hold it
-  constexpr bool kMidxOverlay = sizeof(S.ccnt) >= E * sizeof(uint16_t);
+  // mask index of the entry (0xFFFF: none) — in the words of the (chunk, slab) counters and group bases (ccnt, cbase:
+  // neighbours in FastShared), dead once the records are out, where they hold it
+  static_assert(offsetof(FastShared<E>, cbase) == offsetof(FastShared<E>, ccnt) + sizeof(S.ccnt), "cbase follows ccnt");
+  constexpr bool kMidxOverlay = sizeof(S.ccnt) + sizeof(S.cbase) >= E * sizeof(uint16_t);
   __shared__ uint16_t e_midx_own[kMidxOverlay ? 1 : E];
   uint16_t* const e_midx = kMidxOverlay ? reinterpret_cast<uint16_t*>(S.ccnt) : e_midx_own;
   int32_t* const e_wuu = reinterpret_cast<int32_t*>(raw);                                 // sum of w_u * u, fixed point
@@ -1322,11 +1337,10 @@ __device__ __forceinline__ void walk_fast_tile(
     for (int k = 0; k < kPer; ++k) ekey[k] = kKeyEmpty;
   }
   // ---- entries -> chunks -> pool slots, ranks inside the (chunk, slab) groups, colour weights: no barrier in between.
-  // The chunk cache hands every thread the same index for a chunk whoever inserts it first; nearly every chunk's
-  // slot is already there (the walk's set-up asked the directory for the chunks its rays start and end in); a thread
-  // whose entry lies in a chunk still without one — a chunk a ray only passes through, one not at its home entry of
-  // the directory, a first touch — asks the directory itself (find or insert: a chunk joins the map when one of its
-  // voxels takes an update).  Whether the tile stands at all (table, key box and cache held everything) is only known
+  // The chunk cache hands every thread the same index for a chunk whoever inserts it first.  Nobody has asked the
+  // directory ahead of the walk: the first thread to meet a chunk whose cache entry has no pool slot yet asks the
+  // directory itself (find or insert: a chunk joins the map when one of its voxels takes an update) and leaves the slot
+  // in the cache for the others; threads that come before it is there ask as well and get the same slot.  Whether the tile stands at all (table, key box and cache held everything) is only known
   // at the next barrier: a tile that does not is deferred there — all it has done to global memory by then is to
   // enter chunks its voxels need anyway.
   int ci[kPer];
@@ -1401,7 +1415,8 @@ __device__ __forceinline__ void walk_fast_tile(
   const bool any_cold = S.any_cold != 0u;
   WALK_PROF(5);     // (wait)
   const bool too_many = !defer && S.nent > (uint32_t)kLimit;   // (the voxels do not fit: the next kernel's table is larger / walk_tiles cuts the tile at once)
-  if (E == 2048 && tid == 0 && !defer && S.nent > 1024u * 7u / 8u) atomicAdd(&ctr->over_small, 1u);   // (the host's choice of the next call's table)
+  // (the host's choice of the next call's first table: would the small one — kFastEntriesSmall — have held the tile?)
+  if (E == 2048 && tid == 0 && !defer && S.nent > (uint32_t)(kFastEntriesSmall * 7 / 8)) atomicAdd(&ctr->over_small, 1u);
   if (!defer) defer = S.overflow != 0 || too_many;
   if (defer) {
     if (tid == 0) {
@@ -1500,7 +1515,9 @@ __device__ __forceinline__ void walk_fast_tile(
     }
   } else {
     // the masks come from the visit logs: bit r of a voxel's mask = ray r of the tile visits it
-    __syncthreads();   // (the records are out: the accumulator area and the words of the (chunk, slab) counters are free)
+    // (the records are out — the last reads of ccnt (the scan above) and cbase (the records' places) lie in front of this
+    // barrier, rcnt / rcbase are not overlaid: the accumulator area and the words of ccnt + cbase are free)
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < kPer; ++k) e_midx[tid + k * kWalkRays] = (uint16_t)mrun[k];
     for (uint32_t r0 = 0; fits_runs && r0 < nruns; r0 += kMaskCapE) {
