@@ -465,6 +465,83 @@ int plvs_hip_frame_undistort_keylines(const plvs_keyline* keylines, int n, const
 int plvs_hip_frame_assign_features_to_grid(const plvs_keypoint* kps_un, int n, float min_x, float min_y, float grid_w_inv,
                                            float grid_h_inv, int32_t* cell_start, int32_t* cell_items, int* n_items);
 
+/* ------------------------------------------------------------ Frame glue, RGB-D
+ * The two calls that make a frame RGB-D (the RGB-D constructor, src/Frame.cc:549 and :572) and the constructor as one call.
+ * The depth image is float metres, `depth_pitch` FLOATS from one row to the next (>= width, as plvs_hip_cloudgen_generate
+ * takes it); nothing outside height x depth_pitch is read.  Every float equals the reference's bit for bit (f32 where it
+ * computes in float, f64 where it builds Eigen::Vector3d; tests/test_frame_rgbd.py).
+ *   _compute_stereo_from_rgbd        Frame::ComputeStereoFromRGBD :2251-2279: d = depth at ((int)kps[i].y, (int)kps[i].x);
+ *                                    d > 0 (+inf included, NaN not): depth_out[i] = d, u_right[i] = kps_un[i].x - mbf / d;
+ *                                    otherwise both -1.  A key point outside the image — undefined in the reference — reads
+ *                                    nothing and gets -1.
+ *   _compute_stereo_lines_from_rgbd  Frame::ComputeStereoLinesFromRGBD :2434-2674 (CHECK_RGBD_ENDPOINTS_DEPTH_CONSISTENCY 1)
+ *                                    with computeLocalMinDepth / computeLocalMinMaxDepth :2311-2370: keylines = mvKeyLines
+ *                                    and keylines_un = mvKeyLinesUn AFTER UndistortKeyLines' compaction (same index);
+ *                                    K4 = fx, fy, cx, cy; min_line_length_3d = Frame::skMinLineLength3D (0.01).  Outputs =
+ *                                    mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd (-1: mono).
+ *   _scene_median_depth              Frame::ComputeSceneMedianDepth :2730-2751 over mvDepth (host arithmetic): the positive
+ *                                    depths sorted, element (size - 1) / 2; `fallback` (KeyFrame::skFovCenterDistance = 1.5)
+ *                                    when there is none.
+ * The two host flavours above are there for the drop-in: each uploads the whole image (1.2 MB at 640 x 480) to read a few KB
+ * of it.  THE FLAVOUR MEANT FOR USE IS _stereo_from_rgbd_dev: both loops in one launch on a depth image already resident
+ * in HBM — the buffer plvs_hip_tsdf_chisel_integrate_depth_batch_dev / _integrate_scans_dev take, uploaded once per frame.
+ * Key points and lines are host arrays, either count may be 0 (K4 may be NULL without lines); the outputs are host arrays,
+ * so the call waits for `stream` (a hipStream_t; NULL = the default stream) before it returns. */
+int plvs_hip_frame_compute_stereo_from_rgbd(const plvs_keypoint* kps, const plvs_keypoint* kps_un, int n, const float* depth, int width,
+                                            int height, int depth_pitch, float mbf, float* u_right, float* depth_out);
+int plvs_hip_frame_compute_stereo_lines_from_rgbd(const plvs_keyline* keylines, const plvs_keyline* keylines_un, int n, const float* depth,
+                                                  int width, int height, int depth_pitch, const float* K4, float mbf,
+                                                  float min_line_length_3d, float* u_right_start, float* depth_start,
+                                                  float* u_right_end, float* depth_end);
+int plvs_hip_frame_stereo_from_rgbd_dev(const plvs_keypoint* kps, const plvs_keypoint* kps_un, int n, const plvs_keyline* keylines,
+                                        const plvs_keyline* keylines_un, int n_lines, const float* d_depth, int width, int height,
+                                        int depth_pitch, const float* K4, float mbf, float min_line_length_3d, float* u_right,
+                                        float* depth_out, float* u_right_start, float* depth_start, float* u_right_end,
+                                        float* depth_end, void* stream);
+int plvs_hip_frame_scene_median_depth(const float* depth, int n, float fallback, float* median);
+
+/* The RGB-D constructor (src/Frame.cc:401-600) in one call: grey image and depth image both in HBM (the work that produced
+ * them complete).  Steps: plvs_hip_frame_extract_dev with lapping (0, 0) (plvs_hip_orb_extract_dev when lines = NULL),
+ * UndistortKeyPoints, the point association, and — with a line extractor that found lines — UndistortKeyLines against
+ * bounds4, the compaction of mvKeyLines / mLineDescriptors by its kept_index and the line association (both associations
+ * in one launch), then AssignFeaturesToGrid with min_x = bounds4[0], min_y = bounds4[2].  The results are those of the
+ * separate entries called in that order.  No key points: zero counts, PLVS_OK (the reference returns at :544-545 before it
+ * touches the lines).  More key points / lines than the capacities: PLVS_ERR_CAPACITY. */
+typedef struct plvs_rgbd_calib {
+  float K4[4];                 /* fx, fy, cx, cy                                                        */
+  float dist[8];               /* mDistCoef, the first ndist entries (ndist = 0, 4, 5 or 8)             */
+  int32_t ndist;
+  float mbf;
+  float bounds4[4];            /* mnMinX, mnMaxX, mnMinY, mnMaxY (plvs_hip_frame_compute_image_bounds)   */
+  float grid_w_inv, grid_h_inv;   /* mfGridElementWidthInv / HeightInv                                  */
+  float min_line_length_3d;    /* Frame::skMinLineLength3D                                              */
+  int32_t use_median_depth;    /* Frame::mbUseFovCentersKfGenCriterion                                  */
+  float median_fallback;       /* KeyFrame::skFovCenterDistance                                         */
+} plvs_rgbd_calib;
+typedef struct plvs_rgbd_frame {
+  /* in: capacities and the caller's arrays (line members may be NULL without a line extractor) */
+  int32_t kp_cap, line_cap;
+  plvs_keypoint* kps;          /* mvKeys, kp_cap                 */
+  plvs_keypoint* kps_un;       /* mvKeysUn                       */
+  uint8_t* desc;               /* mDescriptors, kp_cap x 32      */
+  float* u_right;              /* mvuRight                       */
+  float* depth;                /* mvDepth                        */
+  int32_t* cell_start;         /* mGrid as a CSR: 3073 entries   */
+  int32_t* cell_items;         /* kp_cap                         */
+  plvs_keyline* keylines;      /* mvKeyLines (compacted), line_cap */
+  plvs_keyline* keylines_un;   /* mvKeyLinesUn                   */
+  uint8_t* line_desc;          /* mLineDescriptors (compacted), line_cap x 32 */
+  float* u_right_start;        /* mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd */
+  float* depth_start;
+  float* u_right_end;
+  float* depth_end;
+  /* out */
+  int32_t n_kp, mono_index, n_lines, n_items;
+  float median_depth;          /* mMedianDepth */
+} plvs_rgbd_frame;
+int plvs_hip_frame_rgbd_dev(plvs_orb* orb, plvs_lines* lines, const uint8_t* d_image, int w, int hh, int stride, const float* d_depth,
+                            int depth_pitch, const plvs_rgbd_calib* calib, plvs_rgbd_frame* frame, void* stream);
+
 /* Device self-test backing the TSDF chain kernel: counts the binary32 significands b =
  * 1.m * 2^exponent for which the kernel's reciprocal (v_rcp_f32 + one Newton step) differs
  * from the correctly rounded 1/b.  Expected: 0 for every exponent the kernel admits. */

@@ -13,6 +13,8 @@
 //   PLVS2hip::ORBmatcher                include/ORBmatcher.h (DescriptorDistance, SearchByProjection x2, SearchByBoW)
 //   PLVS2hip::LineMatcher               src/LineMatcher.cc:156, :303, :454
 //   PLVS2hip::ComputeStereoMatches      src/Frame.cc:1780
+//   PLVS2hip::UndistortKeyPoints, ComputeImageBounds, UndistortKeyLines, AssignFeaturesToGrid   src/Frame.cc:1507-1778, :716
+//   PLVS2hip::ComputeStereoFromRGBD, ComputeStereoLinesFromRGBD, ComputeSceneMedianDepth, rgbd_frame   src/Frame.cc:2251, :2434, :2730, :401
 //   PLVS2hip::StereoSGM                 Thirdparty/libsgm/include/libsgm.h:57 (as src/PointCloudKeyFrame.cc:435 uses it)
 //   PLVS2hip::PointCloudGenerator       src/PointCloudMapping.cc:796, :929
 //   PLVS2hip::PointCloudMapChisel       include/PointCloudMapChisel.h:61, src/PointCloudMapChisel.cc:76-246
@@ -341,6 +343,124 @@ inline void ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const 
                                          mvDepth.data(), &n);
   plvs_hip_stereo_destroy(s);
   check(rc);
+}
+
+// ------------------------------------------------------------------------------------ frame glue
+// What Frame::Frame runs between extraction and the first search (src/Frame.cc:541-580), as free functions over the vectors
+// a Frame holds.  K4 = fx, fy, cx, cy; dist = mDistCoef (0, 4, 5 or 8 coefficients; empty / first one zero: no distortion).
+inline void UndistortKeyPoints(const std::vector<KeyPoint>& mvKeys, const float* K4, const std::vector<float>& dist,
+                               std::vector<KeyPoint>& mvKeysUn) {   // :1507-1552
+  mvKeysUn.resize(mvKeys.size());
+  check(plvs_hip_frame_undistort_keypoints(mvKeys.data(), (int)mvKeys.size(), K4, dist.data(), (int)dist.size(), mvKeysUn.data()));
+}
+struct ImageBounds {
+  float mnMinX, mnMaxX, mnMinY, mnMaxY, mnMaxDiag;
+};
+inline ImageBounds ComputeImageBounds(int width, int height, const float* K4, const std::vector<float>& dist) {   // :1749-1778
+  float b[5];
+  check(plvs_hip_frame_compute_image_bounds(width, height, K4, dist.data(), (int)dist.size(), b));
+  return ImageBounds{b[0], b[1], b[2], b[3], b[4]};
+}
+// mvKeyLines and mLineDescriptors are compacted in place to the lines that stay inside the bounds, as the reference's loop does
+inline void UndistortKeyLines(std::vector<KeyLine>& mvKeyLines, std::vector<uint8_t>& mLineDescriptors, const float* K4,
+                              const std::vector<float>& dist, const ImageBounds& bounds, std::vector<KeyLine>& mvKeyLinesUn) {   // :1555-1700
+  const int n = (int)mvKeyLines.size();
+  const float b4[4] = {bounds.mnMinX, bounds.mnMaxX, bounds.mnMinY, bounds.mnMaxY};
+  std::vector<int32_t> kept((size_t)n);
+  mvKeyLinesUn.resize((size_t)n);
+  int m = 0;
+  check(plvs_hip_frame_undistort_keylines(mvKeyLines.data(), n, K4, dist.data(), (int)dist.size(), b4, mvKeyLinesUn.data(), kept.data(), &m));
+  for (int j = 0; j < m; ++j) {
+    mvKeyLines[(size_t)j] = mvKeyLines[(size_t)kept[(size_t)j]];
+    std::memmove(mLineDescriptors.data() + 32 * (size_t)j, mLineDescriptors.data() + 32 * (size_t)kept[(size_t)j], 32);
+  }
+  mvKeyLines.resize((size_t)m);
+  mvKeyLinesUn.resize((size_t)m);
+  mLineDescriptors.resize(32 * (size_t)m);
+}
+// mGrid as a CSR: cell = column * 48 + row, cellStart[3073], members in key-point order
+inline void AssignFeaturesToGrid(const std::vector<KeyPoint>& mvKeysUn, float mnMinX, float mnMinY, float mfGridElementWidthInv,
+                                 float mfGridElementHeightInv, std::vector<int32_t>& cellStart, std::vector<int32_t>& cellItems) {   // :716-746
+  cellStart.assign(64 * 48 + 1, 0);
+  cellItems.resize(mvKeysUn.size());
+  int n = 0;
+  check(plvs_hip_frame_assign_features_to_grid(mvKeysUn.data(), (int)mvKeysUn.size(), mnMinX, mnMinY, mfGridElementWidthInv,
+                                               mfGridElementHeightInv, cellStart.data(), cellItems.data(), &n));
+  cellItems.resize((size_t)n);
+}
+
+// ---- RGB-D (src/Frame.cc:549, :572): imDepth is a host image here — these two upload it on every call; a caller that keeps
+// the depth in device memory (the buffer of the TSDF depth entries) calls plvs_hip_frame_stereo_from_rgbd_dev or rgbd_frame.
+inline void ComputeStereoFromRGBD(const std::vector<KeyPoint>& mvKeys, const std::vector<KeyPoint>& mvKeysUn, const Image32F& imDepth,
+                                  float mbf, std::vector<float>& mvuRight, std::vector<float>& mvDepth) {   // :2251-2279
+  if (mvKeys.size() != mvKeysUn.size()) throw std::invalid_argument("ComputeStereoFromRGBD: mvKeys / mvKeysUn sizes differ");
+  mvuRight.assign(mvKeys.size(), -1.0f);
+  mvDepth.assign(mvKeys.size(), -1.0f);
+  check(plvs_hip_frame_compute_stereo_from_rgbd(mvKeys.data(), mvKeysUn.data(), (int)mvKeys.size(), imDepth.data, imDepth.cols,
+                                                imDepth.rows, (int)(imDepth.step / sizeof(float)), mbf, mvuRight.data(), mvDepth.data()));
+}
+inline void ComputeStereoLinesFromRGBD(const std::vector<KeyLine>& mvKeyLines, const std::vector<KeyLine>& mvKeyLinesUn,
+                                       const Image32F& imDepth, const float* K4, float mbf, std::vector<float>& mvuRightLineStart,
+                                       std::vector<float>& mvDepthLineStart, std::vector<float>& mvuRightLineEnd,
+                                       std::vector<float>& mvDepthLineEnd, float skMinLineLength3D = 0.01f) {   // :2434-2674
+  if (mvKeyLines.size() != mvKeyLinesUn.size()) throw std::invalid_argument("ComputeStereoLinesFromRGBD: mvKeyLines / mvKeyLinesUn sizes differ");
+  const size_t n = mvKeyLines.size();
+  mvuRightLineStart.assign(n, -1.0f);
+  mvDepthLineStart.assign(n, -1.0f);
+  mvuRightLineEnd.assign(n, -1.0f);
+  mvDepthLineEnd.assign(n, -1.0f);
+  check(plvs_hip_frame_compute_stereo_lines_from_rgbd(mvKeyLines.data(), mvKeyLinesUn.data(), (int)n, imDepth.data, imDepth.cols,
+                                                      imDepth.rows, (int)(imDepth.step / sizeof(float)), K4, mbf, skMinLineLength3D,
+                                                      mvuRightLineStart.data(), mvDepthLineStart.data(), mvuRightLineEnd.data(),
+                                                      mvDepthLineEnd.data()));
+}
+inline float ComputeSceneMedianDepth(const std::vector<float>& mvDepth, float skFovCenterDistance = 1.5f) {   // :2730-2751
+  float m = skFovCenterDistance;
+  check(plvs_hip_frame_scene_median_depth(mvDepth.data(), (int)mvDepth.size(), skFovCenterDistance, &m));
+  return m;
+}
+
+// The RGB-D constructor (src/Frame.cc:401-600) in one call.  d_image (8-bit grey, `step` bytes a row) and d_depth (float,
+// depthPitch floats a row) are DEVICE pointers (plvs_hip_malloc / plvs_hip_memcpy_h2d, or the caller's own HIP buffers);
+// lines may be nullptr.  The members are what a Frame holds after the constructor.
+struct RgbdFrame {
+  int monoLeft = -1;
+  std::vector<KeyPoint> mvKeys, mvKeysUn;
+  std::vector<uint8_t> mDescriptors;
+  std::vector<float> mvuRight, mvDepth;
+  float mMedianDepth = 1.5f;
+  std::vector<KeyLine> mvKeyLines, mvKeyLinesUn;
+  std::vector<uint8_t> mLineDescriptors;
+  std::vector<float> mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd;
+  std::vector<int32_t> cellStart, cellItems;   // mGrid as a CSR (AssignFeaturesToGrid above)
+};
+inline void rgbd_frame(ORBextractor& orb, LineExtractor* lines, const uint8_t* d_image, int width, int height, int step,
+                       const float* d_depth, int depthPitch, const plvs_rgbd_calib& calib, RgbdFrame& F, int kpCapacity = 8192,
+                       int lineCapacity = 4096, void* stream = nullptr) {
+  const size_t nc = (size_t)kpCapacity, lc = lines ? (size_t)lineCapacity : 0;
+  F.mvKeys.resize(nc); F.mvKeysUn.resize(nc); F.mDescriptors.resize(32 * nc); F.mvuRight.resize(nc); F.mvDepth.resize(nc);
+  F.cellStart.assign(64 * 48 + 1, 0); F.cellItems.resize(nc);
+  F.mvKeyLines.resize(lc); F.mvKeyLinesUn.resize(lc); F.mLineDescriptors.resize(32 * lc);
+  F.mvuRightLineStart.resize(lc); F.mvDepthLineStart.resize(lc); F.mvuRightLineEnd.resize(lc); F.mvDepthLineEnd.resize(lc);
+  plvs_rgbd_frame f;
+  std::memset(&f, 0, sizeof f);
+  f.kp_cap = kpCapacity; f.line_cap = (int)lc;
+  f.kps = F.mvKeys.data(); f.kps_un = F.mvKeysUn.data(); f.desc = F.mDescriptors.data(); f.u_right = F.mvuRight.data();
+  f.depth = F.mvDepth.data(); f.cell_start = F.cellStart.data(); f.cell_items = F.cellItems.data();
+  if (lines) {
+    f.keylines = F.mvKeyLines.data(); f.keylines_un = F.mvKeyLinesUn.data(); f.line_desc = F.mLineDescriptors.data();
+    f.u_right_start = F.mvuRightLineStart.data(); f.depth_start = F.mvDepthLineStart.data();
+    f.u_right_end = F.mvuRightLineEnd.data(); f.depth_end = F.mvDepthLineEnd.data();
+  }
+  check(plvs_hip_frame_rgbd_dev(orb.handle(), lines ? lines->handle() : nullptr, d_image, width, height, step, d_depth, depthPitch,
+                                &calib, &f, stream));
+  const size_t n = (size_t)f.n_kp, nl = (size_t)f.n_lines;
+  F.monoLeft = f.mono_index;
+  F.mMedianDepth = f.median_depth;
+  F.mvKeys.resize(n); F.mvKeysUn.resize(n); F.mDescriptors.resize(32 * n); F.mvuRight.resize(n); F.mvDepth.resize(n);
+  F.cellItems.resize((size_t)f.n_items);
+  F.mvKeyLines.resize(nl); F.mvKeyLinesUn.resize(nl); F.mLineDescriptors.resize(32 * nl);
+  F.mvuRightLineStart.resize(nl); F.mvDepthLineStart.resize(nl); F.mvuRightLineEnd.resize(nl); F.mvDepthLineEnd.resize(nl);
 }
 
 // ------------------------------------------------------------------------------------ dense stereo

@@ -122,3 +122,163 @@ def AssignFeaturesToGrid(kps_un, min_x, min_y, grid_w_inv, grid_h_inv):
     _lib.check(f(_lib.np_ptr(kps), len(kps), float(min_x), float(min_y), float(grid_w_inv), float(grid_h_inv), _lib.np_ptr(start),
                  _lib.np_ptr(items), ctypes.byref(n)))
     return start, items[:n.value].copy()
+
+
+# ---------------------------------------------------------------------------------------------- Frame glue, RGB-D
+# The two calls that make a frame RGB-D (src/Frame.cc:549, :572) and the RGB-D constructor (:401-600) as one call.  The depth
+# image is float32 metres: a numpy array goes through the host flavours (which upload the whole image), a torch CUDA tensor
+# — possibly a pitched view, stride(1) == 1 — through the one-launch device flavour, and is the same buffer the TSDF depth
+# entries take.
+SK_MIN_LINE_LENGTH_3D = 0.01      # Frame::skMinLineLength3D (src/Frame.cc:115)
+SK_FOV_CENTER_DISTANCE = 1.5      # KeyFrame::skFovCenterDistance
+_f = ctypes.c_float
+L.plvs_hip_frame_compute_stereo_from_rgbd.argtypes = [_vp, _vp, _i, _vp, _i, _i, _i, _f, _vp, _vp]
+L.plvs_hip_frame_compute_stereo_lines_from_rgbd.argtypes = [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _vp]
+L.plvs_hip_frame_stereo_from_rgbd_dev.argtypes = [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _f, _f] + [_vp] * 7
+L.plvs_hip_frame_scene_median_depth.argtypes = [_vp, _i, _f, _vp]
+
+
+class RgbdCalib(ctypes.Structure):      # plvs_rgbd_calib
+    _fields_ = [("K4", _f * 4), ("dist", _f * 8), ("ndist", ctypes.c_int32), ("mbf", _f), ("bounds4", _f * 4), ("grid_w_inv", _f),
+                ("grid_h_inv", _f), ("min_line_length_3d", _f), ("use_median_depth", ctypes.c_int32), ("median_fallback", _f)]
+
+
+class RgbdFrameC(ctypes.Structure):     # plvs_rgbd_frame
+    _fields_ = [("kp_cap", ctypes.c_int32), ("line_cap", ctypes.c_int32)] + \
+               [(k, _vp) for k in ("kps", "kps_un", "desc", "u_right", "depth", "cell_start", "cell_items", "keylines", "keylines_un",
+                                   "line_desc", "u_right_start", "depth_start", "u_right_end", "depth_end")] + \
+               [(k, ctypes.c_int32) for k in ("n_kp", "mono_index", "n_lines", "n_items")] + [("median_depth", _f)]
+
+
+L.plvs_hip_frame_rgbd_dev.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, ctypes.POINTER(RgbdCalib), ctypes.POINTER(RgbdFrameC), _vp]
+
+
+def _depth_arg(depth):
+    """-> (pointer, width, height, pitch in floats, on the device?, keep-alive)"""
+    import numpy as np
+    if isinstance(depth, torch.Tensor):
+        assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1
+        torch.cuda.current_stream().synchronize()
+        return _vp(depth.data_ptr()), depth.shape[1], depth.shape[0], depth.stride(0), True, depth
+    d = np.asarray(depth)
+    assert d.dtype == np.float32 and d.ndim == 2
+    if d.strides[1] != 4 or d.strides[0] % 4 or d.strides[0] < 4 * d.shape[1]:
+        d = np.ascontiguousarray(d)
+    return _vp(d.ctypes.data), d.shape[1], d.shape[0], d.strides[0] // 4, False, d
+
+
+def _stereo_from_rgbd_dev(kps, kps_un, kl, kl_un, dp, w, h, pitch, K4, mbf, min_len):
+    import numpy as np
+    n, nl = len(kps), len(kl)
+    out = [np.empty(n, np.float32) for _ in range(2)] + [np.empty(nl, np.float32) for _ in range(4)]
+    _lib.check(L.plvs_hip_frame_stereo_from_rgbd_dev(_lib.np_ptr(kps), _lib.np_ptr(kps_un), n, _lib.np_ptr(kl), _lib.np_ptr(kl_un), nl,
+                                                     dp, w, h, pitch, _lib.np_ptr(K4), float(mbf), float(min_len),
+                                                     *[_lib.np_ptr(o) for o in out], _lib.current_stream_ptr()))
+    return out
+
+
+def ComputeStereoFromRGBD(kps, kps_un, depth, mbf):
+    """Frame::ComputeStereoFromRGBD (src/Frame.cc:2251-2279) -> (mvuRight, mvDepth); -1 where the depth under the (distorted) key
+    point is not > 0, and for a key point outside the image."""
+    import numpy as np
+    from .orb import KP_DTYPE
+    kps, kps_un = np.ascontiguousarray(kps, KP_DTYPE), np.ascontiguousarray(kps_un, KP_DTYPE)
+    assert len(kps) == len(kps_un)
+    dp, w, h, pitch, on_dev, _keep = _depth_arg(depth)
+    if on_dev:
+        from .lines import KEYLINE_DTYPE
+        none = np.zeros(0, KEYLINE_DTYPE)
+        return tuple(_stereo_from_rgbd_dev(kps, kps_un, none, none, dp, w, h, pitch, None, mbf, 0.0)[:2])
+    ur, z = np.empty(len(kps), np.float32), np.empty(len(kps), np.float32)
+    _lib.check(L.plvs_hip_frame_compute_stereo_from_rgbd(_lib.np_ptr(kps), _lib.np_ptr(kps_un), len(kps), dp, w, h, pitch, float(mbf),
+                                                         _lib.np_ptr(ur), _lib.np_ptr(z)))
+    return ur, z
+
+
+def ComputeStereoLinesFromRGBD(keylines, keylines_un, depth, K, mbf, min_line_length_3d=SK_MIN_LINE_LENGTH_3D):
+    """Frame::ComputeStereoLinesFromRGBD (src/Frame.cc:2434-2674) on mvKeyLines / mvKeyLinesUn as UndistortKeyLines leaves them
+    (same index) -> (mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd)."""
+    import numpy as np
+    from .lines import KEYLINE_DTYPE
+    from .orb import KP_DTYPE
+    kl, klu = np.ascontiguousarray(keylines, KEYLINE_DTYPE), np.ascontiguousarray(keylines_un, KEYLINE_DTYPE)
+    assert len(kl) == len(klu)
+    K4 = np.ascontiguousarray(K, np.float32).reshape(4)
+    dp, w, h, pitch, on_dev, _keep = _depth_arg(depth)
+    if on_dev:
+        none = np.zeros(0, KP_DTYPE)
+        return tuple(_stereo_from_rgbd_dev(none, none, kl, klu, dp, w, h, pitch, K4, mbf, min_line_length_3d)[2:])
+    out = [np.empty(len(kl), np.float32) for _ in range(4)]
+    _lib.check(L.plvs_hip_frame_compute_stereo_lines_from_rgbd(_lib.np_ptr(kl), _lib.np_ptr(klu), len(kl), dp, w, h, pitch, _lib.np_ptr(K4),
+                                                               float(mbf), float(min_line_length_3d), *[_lib.np_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def stereo_from_rgbd(kps, kps_un, keylines, keylines_un, depth, K, mbf, min_line_length_3d=SK_MIN_LINE_LENGTH_3D):
+    """Both associations in one launch (plvs_hip_frame_stereo_from_rgbd_dev), depth: a float32 CUDA tensor ->
+    (mvuRight, mvDepth, mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd).  Either set may be empty."""
+    import numpy as np
+    from .lines import KEYLINE_DTYPE
+    from .orb import KP_DTYPE
+    kps, kps_un = np.ascontiguousarray(kps, KP_DTYPE), np.ascontiguousarray(kps_un, KP_DTYPE)
+    kl, klu = np.ascontiguousarray(keylines, KEYLINE_DTYPE), np.ascontiguousarray(keylines_un, KEYLINE_DTYPE)
+    assert len(kps) == len(kps_un) and len(kl) == len(klu)
+    dp, w, h, pitch, on_dev, _keep = _depth_arg(depth)
+    assert on_dev, "stereo_from_rgbd reads the depth image in device memory"
+    K4 = np.ascontiguousarray(K, np.float32).reshape(4)
+    return tuple(_stereo_from_rgbd_dev(kps, kps_un, kl, klu, dp, w, h, pitch, K4, mbf, min_line_length_3d))
+
+
+def ComputeSceneMedianDepth(depths, fallback=SK_FOV_CENTER_DISTANCE):
+    """Frame::ComputeSceneMedianDepth (src/Frame.cc:2730-2751) over mvDepth."""
+    import numpy as np
+    d = np.ascontiguousarray(depths, np.float32).reshape(-1)
+    m = _f()
+    _lib.check(L.plvs_hip_frame_scene_median_depth(_lib.np_ptr(d), len(d), float(fallback), ctypes.byref(m)))
+    return np.float32(m.value)
+
+
+def rgbd_frame(orb: ORBextractor, lines, image: torch.Tensor, depth: torch.Tensor, K, dist, mbf, bounds, grid_w_inv, grid_h_inv,
+               min_line_length_3d=SK_MIN_LINE_LENGTH_3D, use_median_depth=False, median_fallback=SK_FOV_CENTER_DISTANCE):
+    """The RGB-D Frame constructor (src/Frame.cc:401-600) in one call: image (uint8) and depth (float32) are 2-D CUDA tensors of
+    one size; lines = a LineExtractor or None; bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY).  -> dict of what the Frame holds:
+    mono_index, keys, keys_un, descriptors, u_right, depth, median_depth, keylines, keylines_un, line_descriptors,
+    u_right_start, depth_start, u_right_end, depth_end, cell_start, cell_items."""
+    import numpy as np
+    from .lines import KEYLINE_DTYPE
+    from .orb import KP_DTYPE
+    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() == 2 and image.stride(1) == 1
+    dp, w, h, pitch, on_dev, _keep = _depth_arg(depth)
+    assert on_dev and (h, w) == tuple(image.shape)
+    K4, d, nd = _calib(K, dist)
+    c = RgbdCalib()
+    c.K4[:] = [float(x) for x in K4]
+    for k in range(nd):
+        c.dist[k] = float(d[k])
+    c.ndist, c.mbf = nd, float(mbf)
+    c.bounds4[:] = [float(x) for x in np.asarray(bounds, np.float32)[:4]]
+    c.grid_w_inv, c.grid_h_inv, c.min_line_length_3d = float(grid_w_inv), float(grid_h_inv), float(min_line_length_3d)
+    c.use_median_depth, c.median_fallback = int(bool(use_median_depth)), float(median_fallback)
+    ncap, lcap = orb._cap, (lines._cap if lines is not None else 0)
+    a = dict(kps=np.zeros(ncap, KP_DTYPE), kps_un=np.zeros(ncap, KP_DTYPE), desc=np.zeros((ncap, 32), np.uint8),
+             u_right=np.zeros(ncap, np.float32), depth=np.zeros(ncap, np.float32), cell_start=np.zeros(64 * 48 + 1, np.int32),
+             cell_items=np.zeros(ncap, np.int32))
+    if lines is not None:
+        a.update(keylines=np.zeros(lcap, KEYLINE_DTYPE), keylines_un=np.zeros(lcap, KEYLINE_DTYPE), line_desc=np.zeros((lcap, 32), np.uint8),
+                 **{k: np.zeros(lcap, np.float32) for k in ("u_right_start", "depth_start", "u_right_end", "depth_end")})
+    f = RgbdFrameC()
+    f.kp_cap, f.line_cap = ncap, lcap
+    for k, v in a.items():
+        setattr(f, k, v.ctypes.data)
+    _lib.check(L.plvs_hip_frame_rgbd_dev(orb._h, lines._h if lines is not None else None, _vp(image.data_ptr()), w, h, image.stride(0),
+                                         dp, pitch, ctypes.byref(c), ctypes.byref(f), _lib.current_stream_ptr()))
+    n, nl = f.n_kp, f.n_lines
+    empty_l = np.zeros(0, np.float32)
+    line = (lambda k: a[k][:nl].copy()) if lines is not None else (lambda k: empty_l.copy())
+    return dict(mono_index=f.mono_index, keys=a["kps"][:n].copy(), keys_un=a["kps_un"][:n].copy(), descriptors=a["desc"][:n].copy(),
+                u_right=a["u_right"][:n].copy(), depth=a["depth"][:n].copy(), median_depth=np.float32(f.median_depth),
+                keylines=a["keylines"][:nl].copy() if lines is not None else np.zeros(0, KEYLINE_DTYPE),
+                keylines_un=a["keylines_un"][:nl].copy() if lines is not None else np.zeros(0, KEYLINE_DTYPE),
+                line_descriptors=a["line_desc"][:nl].copy() if lines is not None else np.zeros((0, 32), np.uint8),
+                u_right_start=line("u_right_start"), depth_start=line("depth_start"), u_right_end=line("u_right_end"),
+                depth_end=line("depth_end"), cell_start=a["cell_start"].copy(), cell_items=a["cell_items"][:f.n_items].copy())
