@@ -542,6 +542,98 @@ typedef struct plvs_rgbd_frame {
 int plvs_hip_frame_rgbd_dev(plvs_orb* orb, plvs_lines* lines, const uint8_t* d_image, int w, int hh, int stride, const float* d_depth,
                             int depth_pitch, const plvs_rgbd_calib* calib, plvs_rgbd_frame* frame, void* stream);
 
+/* ------------------------------------------------------------ Frame glue, stereo
+ * What gives the lines of a stereo frame their depth, and the stereo constructor as one call.
+ *   _compute_stereo_line_matches  Frame::ComputeStereoLineMatches src/Frame.cc:2008-2248 with LineMatcher::SearchStereoMatchesByKnn
+ *       (src/LineMatcher.cc:454-586) and ComputeDescriptorMatches (:2568-2620) inside it: ONE launch of one workgroup — exact
+ *       k = 2 search (left = query, right = train, the multi-index-hash tie order of plvs_hip_hamming_knn2 / PLVS_TIE_MIH), ratio
+ *       test, distance and octave tests, "replace with better", rotation histogram with its three maxima, the triangulation
+ *       of every match and the 1.5 * 1.48 * median cut.  No host pass in between: one packed upload, one launch, one copy back.
+ *       keylines_un / desc = mvKeyLinesUn / mLineDescriptors, the right side alike (on a rectified pair mvKeyLinesUn ==
+ *       mvKeyLines, which is what the reference reads for the geometry); line_level_sigma2 = mvLineLevelSigma2 (n_levels
+ *       entries); K4 = fx, fy, cx, cy; line_stereo_max_dist = Tracking::skLineStereoMaxDist (20); min_line_length_3d =
+ *       Frame::skMinLineLength3D (0.01); nn_ratio, check_orientation = the LineMatcher(0.7) the function builds: 0.7 and 1
+ *       (the constructor's default, include/LineMatcher.h:61); descriptor_dist = LineMatcher::TH_LOW_STEREO (50).
+ *       Outputs (n floats each) = mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd, -1 = mono;
+ *       *n_stereo (nullable) = lines left with both depths after the median cut.  Every float equals the reference's bit for
+ *       bit (tests/test_frame_stereo.py).  All arrays are host memory; the call waits for `stream` (a hipStream_t, NULL = the
+ *       default stream).  n == 0 or n_right == 0: all -1, *n_stereo = 0, PLVS_OK, nothing launched (:2042-2045).  More than
+ *       512 lines on a side: PLVS_ERR_CAPACITY, nothing read or written.  An octave outside [0, n_levels):
+ *       PLVS_ERR_INVALID_ARG, nothing written. */
+int plvs_hip_frame_compute_stereo_line_matches(const plvs_keyline* keylines_un, const uint8_t* desc, int n,
+                                               const plvs_keyline* keylines_right_un, const uint8_t* desc_right, int n_right,
+                                               const float* line_level_sigma2, int n_levels, const float* K4, float mbf,
+                                               float line_stereo_max_dist, float min_line_length_3d, float nn_ratio,
+                                               int check_orientation, int descriptor_dist, float* u_right_start, float* depth_start,
+                                               float* u_right_end, float* depth_end, int* n_stereo, void* stream);
+/* The same with the matcher stage's result, for tests: per right line t, holders4[4 t ..] = the left line that holds it
+ * (-1 none), their distance, 1 if the match survives the rotation check, and the lowest passing left line that named it
+ * (the order of vMatches) — what plvs_hip_lines_search_stereo_by_knn returns as a list. */
+int plvs_hip_frame_compute_stereo_line_matches_debug(const plvs_keyline* keylines_un, const uint8_t* desc, int n,
+                                                     const plvs_keyline* keylines_right_un, const uint8_t* desc_right, int n_right,
+                                                     const float* line_level_sigma2, int n_levels, const float* K4, float mbf,
+                                                     float line_stereo_max_dist, float min_line_length_3d, float nn_ratio,
+                                                     int check_orientation, int descriptor_dist, float* u_right_start,
+                                                     float* depth_start, float* u_right_end, float* depth_end, int* n_stereo,
+                                                     int32_t* holders4, void* stream);
+
+/* The stereo constructor (src/Frame.cc:214-398) in one call: both rectified grey images in HBM (the work that produced them
+ * complete), one size and stride.  Steps, in the reference's order: the four extractions concurrently on four host threads,
+ * each extractor on its own stream (:314-323; two threads when both line extractors are NULL, :328-331), lapping (0, 0); no
+ * left key points: zero counts, PLVS_OK (:340-341); UndistortKeyPoints; plvs_hip_stereo_matches on `stereo`, which must have
+ * been created from these two ORB handles (PLVS_ERR_INVALID_ARG otherwise); if left lines were found, UndistortKeyLines and
+ * plvs_hip_frame_compute_stereo_line_matches; AssignFeaturesToGrid.  The results are those of the separate entries called in
+ * that order.
+ * ONLY A RECTIFIED PAIR is accepted (ndist == 0 or dist[0] == 0, PLVS_ERR_INVALID_ARG otherwise; the reference asserts at
+ * :1607 and leaves mvKeyLinesRightUn empty against the assert at LineMatcher.cc:456).  UndistortKeyLines therefore takes its
+ * early return (:1563-1568): mvKeyLinesUn = mvKeyLines, mvKeyLinesRightUn = mvKeyLinesRight, and — UNLIKE
+ * plvs_hip_frame_rgbd_dev — NO bounds filter and NO compaction of the lines.  Both line extractors or neither. */
+struct plvs_stereo;   /* the handle of "sparse stereo matching" below (plvs_hip_stereo_create) */
+typedef struct plvs_stereo_calib {
+  float K4[4];                 /* fx, fy, cx, cy                                                        */
+  float dist[8];               /* mDistCoef, the first ndist entries; dist[0] must be 0                 */
+  int32_t ndist;
+  float mbf;                   /* mb = mbf / fx                                                         */
+  float bounds4[4];            /* mnMinX, mnMaxX, mnMinY, mnMaxY (plvs_hip_frame_compute_image_bounds)   */
+  float grid_w_inv, grid_h_inv;   /* mfGridElementWidthInv / HeightInv                                  */
+  float min_line_length_3d;    /* Frame::skMinLineLength3D                                              */
+  float line_stereo_max_dist;  /* Tracking::skLineStereoMaxDist                                         */
+  float nn_ratio;              /* LineMatcher(0.7)                                                      */
+  int32_t check_orientation;   /* its mbCheckOrientation: 1                                             */
+  int32_t descriptor_dist;     /* LineMatcher::TH_LOW_STEREO: 50                                        */
+  int32_t n_line_levels;       /* entries of line_level_sigma2                                          */
+  const float* line_level_sigma2;   /* mvLineLevelSigma2 (host; may be NULL without line extractors)    */
+} plvs_stereo_calib;
+typedef struct plvs_stereo_frame {
+  /* in: capacities and the caller's arrays (line members may be NULL without line extractors) */
+  int32_t kp_cap, kp_right_cap, line_cap, line_right_cap;
+  plvs_keypoint* kps;          /* mvKeys, kp_cap                 */
+  plvs_keypoint* kps_un;       /* mvKeysUn                       */
+  uint8_t* desc;               /* mDescriptors, kp_cap x 32      */
+  float* u_right;              /* mvuRight                       */
+  float* depth;                /* mvDepth                        */
+  int32_t* cell_start;         /* mGrid as a CSR: 3073 entries   */
+  int32_t* cell_items;         /* kp_cap                         */
+  plvs_keypoint* kps_right;    /* mvKeysRight, kp_right_cap      */
+  uint8_t* desc_right;         /* mDescriptorsRight, kp_right_cap x 32 */
+  plvs_keyline* keylines;      /* mvKeyLines, line_cap           */
+  plvs_keyline* keylines_un;   /* mvKeyLinesUn                   */
+  uint8_t* line_desc;          /* mLineDescriptors, line_cap x 32 */
+  float* u_right_start;        /* mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd */
+  float* depth_start;
+  float* u_right_end;
+  float* depth_end;
+  plvs_keyline* keylines_right;      /* mvKeyLinesRight, line_right_cap                                     */
+  plvs_keyline* keylines_right_un;   /* mvKeyLinesRightUn (written when left lines were found)              */
+  uint8_t* line_desc_right;          /* mLineDescriptorsRight, line_right_cap x 32                          */
+  /* out */
+  int32_t n_kp, mono_index, n_kp_right, mono_index_right, n_lines, n_lines_right, n_items;
+  int32_t n_stereo_points, n_stereo_lines;   /* key points / lines with depth */
+} plvs_stereo_frame;
+int plvs_hip_frame_stereo_dev(plvs_orb* orb_left, plvs_orb* orb_right, plvs_lines* lines_left, plvs_lines* lines_right,
+                              struct plvs_stereo* stereo, const uint8_t* d_left, const uint8_t* d_right, int w, int hh, int stride,
+                              const plvs_stereo_calib* calib, plvs_stereo_frame* frame, void* stream);
+
 /* Device self-test backing the TSDF chain kernel: counts the binary32 significands b =
  * 1.m * 2^exponent for which the kernel's reciprocal (v_rcp_f32 + one Newton step) differs
  * from the correctly rounded 1/b.  Expected: 0 for every exponent the kernel admits. */

@@ -463,6 +463,89 @@ inline void rgbd_frame(ORBextractor& orb, LineExtractor* lines, const uint8_t* d
   F.mvuRightLineStart.resize(nl); F.mvDepthLineStart.resize(nl); F.mvuRightLineEnd.resize(nl); F.mvDepthLineEnd.resize(nl);
 }
 
+// ---- stereo (src/Frame.cc:374): Frame::ComputeStereoLineMatches with LineMatcher::SearchStereoMatchesByKnn inside it, one
+// launch.  The pair is rectified: mvKeyLinesUn == mvKeyLines on both sides.  The matcher's arguments default to the
+// LineMatcher(0.7) the reference builds and LineMatcher::TH_LOW_STEREO.  Returns the lines left with both depths.
+inline int ComputeStereoLineMatches(const std::vector<KeyLine>& mvKeyLinesUn, const std::vector<uint8_t>& mLineDescriptors,
+                                    const std::vector<KeyLine>& mvKeyLinesRightUn, const std::vector<uint8_t>& mLineDescriptorsRight,
+                                    const std::vector<float>& mvLineLevelSigma2, const float* K4, float mbf,
+                                    std::vector<float>& mvuRightLineStart, std::vector<float>& mvDepthLineStart,
+                                    std::vector<float>& mvuRightLineEnd, std::vector<float>& mvDepthLineEnd,
+                                    float skLineStereoMaxDist = 20.0f, float skMinLineLength3D = 0.01f, float nnRatio = 0.7f,
+                                    bool checkOrientation = true, int thDescriptorDist = 50, void* stream = nullptr) {   // :2008-2248
+  const size_t n = mvKeyLinesUn.size(), nr = mvKeyLinesRightUn.size();
+  if (mLineDescriptors.size() != 32 * n || mLineDescriptorsRight.size() != 32 * nr)
+    throw std::invalid_argument("ComputeStereoLineMatches: 32 descriptor bytes per line");
+  mvuRightLineStart.assign(n, -1.0f);
+  mvDepthLineStart.assign(n, -1.0f);
+  mvuRightLineEnd.assign(n, -1.0f);
+  mvDepthLineEnd.assign(n, -1.0f);
+  int stereo = 0;
+  check(plvs_hip_frame_compute_stereo_line_matches(mvKeyLinesUn.data(), mLineDescriptors.data(), (int)n, mvKeyLinesRightUn.data(),
+                                                   mLineDescriptorsRight.data(), (int)nr, mvLineLevelSigma2.data(),
+                                                   (int)mvLineLevelSigma2.size(), K4, mbf, skLineStereoMaxDist, skMinLineLength3D, nnRatio,
+                                                   checkOrientation ? 1 : 0, thDescriptorDist, mvuRightLineStart.data(),
+                                                   mvDepthLineStart.data(), mvuRightLineEnd.data(), mvDepthLineEnd.data(), &stereo, stream));
+  return stereo;
+}
+
+// The stereo constructor (src/Frame.cc:214-398) in one call on a RECTIFIED pair.  d_left / d_right (8-bit grey, `step` bytes a
+// row, one size) are DEVICE pointers; the line extractors are both given or both nullptr; `stereo` comes from
+// plvs_hip_stereo_create(left.handle(), right.handle(), ...) and is kept between frames.  calib.line_level_sigma2 points at the
+// caller's mvLineLevelSigma2.  No bounds filter and no compaction of the lines (mvKeyLinesUn = mvKeyLines).  The members are
+// what a Frame holds after the constructor.
+struct StereoFrameMembers {
+  int monoLeft = -1, monoRight = -1;
+  std::vector<KeyPoint> mvKeys, mvKeysUn, mvKeysRight;
+  std::vector<uint8_t> mDescriptors, mDescriptorsRight;
+  std::vector<float> mvuRight, mvDepth;
+  std::vector<KeyLine> mvKeyLines, mvKeyLinesUn, mvKeyLinesRight, mvKeyLinesRightUn;
+  std::vector<uint8_t> mLineDescriptors, mLineDescriptorsRight;
+  std::vector<float> mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd;
+  std::vector<int32_t> cellStart, cellItems;   // mGrid as a CSR (AssignFeaturesToGrid above)
+  int stereoPoints = 0, stereoLines = 0;       // key points / lines with depth
+};
+inline void StereoFrame(ORBextractor& left, ORBextractor& right, LineExtractor* linesLeft, LineExtractor* linesRight, plvs_stereo* stereo,
+                        const uint8_t* d_left, const uint8_t* d_right, int width, int height, int step, const plvs_stereo_calib& calib,
+                        StereoFrameMembers& F, int kpCapacity = 8192, int lineCapacity = 4096, void* stream = nullptr) {
+  const bool withLines = linesLeft != nullptr;
+  const size_t nc = (size_t)kpCapacity, lc = withLines ? (size_t)lineCapacity : 0;
+  F.mvKeys.resize(nc); F.mvKeysUn.resize(nc); F.mDescriptors.resize(32 * nc); F.mvuRight.resize(nc); F.mvDepth.resize(nc);
+  F.mvKeysRight.resize(nc); F.mDescriptorsRight.resize(32 * nc);
+  F.cellStart.assign(64 * 48 + 1, 0); F.cellItems.resize(nc);
+  F.mvKeyLines.resize(lc); F.mvKeyLinesUn.resize(lc); F.mLineDescriptors.resize(32 * lc);
+  F.mvKeyLinesRight.resize(lc); F.mvKeyLinesRightUn.resize(lc); F.mLineDescriptorsRight.resize(32 * lc);
+  F.mvuRightLineStart.resize(lc); F.mvDepthLineStart.resize(lc); F.mvuRightLineEnd.resize(lc); F.mvDepthLineEnd.resize(lc);
+  plvs_stereo_frame f;
+  std::memset(&f, 0, sizeof f);
+  f.kp_cap = f.kp_right_cap = kpCapacity;
+  f.line_cap = f.line_right_cap = (int)lc;
+  f.kps = F.mvKeys.data(); f.kps_un = F.mvKeysUn.data(); f.desc = F.mDescriptors.data(); f.u_right = F.mvuRight.data();
+  f.depth = F.mvDepth.data(); f.cell_start = F.cellStart.data(); f.cell_items = F.cellItems.data();
+  f.kps_right = F.mvKeysRight.data(); f.desc_right = F.mDescriptorsRight.data();
+  if (withLines) {
+    f.keylines = F.mvKeyLines.data(); f.keylines_un = F.mvKeyLinesUn.data(); f.line_desc = F.mLineDescriptors.data();
+    f.keylines_right = F.mvKeyLinesRight.data(); f.keylines_right_un = F.mvKeyLinesRightUn.data();
+    f.line_desc_right = F.mLineDescriptorsRight.data();
+    f.u_right_start = F.mvuRightLineStart.data(); f.depth_start = F.mvDepthLineStart.data();
+    f.u_right_end = F.mvuRightLineEnd.data(); f.depth_end = F.mvDepthLineEnd.data();
+  }
+  check(plvs_hip_frame_stereo_dev(left.handle(), right.handle(), withLines ? linesLeft->handle() : nullptr,
+                                  linesRight ? linesRight->handle() : nullptr, stereo, d_left, d_right, width, height, step, &calib, &f,
+                                  stream));
+  const size_t n = (size_t)f.n_kp, nr = (size_t)f.n_kp_right, nl = (size_t)f.n_lines, nlr = (size_t)f.n_lines_right;
+  F.monoLeft = f.mono_index;
+  F.monoRight = f.mono_index_right;
+  F.stereoPoints = f.n_stereo_points;
+  F.stereoLines = f.n_stereo_lines;
+  F.mvKeys.resize(n); F.mvKeysUn.resize(n); F.mDescriptors.resize(32 * n); F.mvuRight.resize(n); F.mvDepth.resize(n);
+  F.mvKeysRight.resize(nr); F.mDescriptorsRight.resize(32 * nr);
+  F.cellItems.resize((size_t)f.n_items);
+  F.mvKeyLines.resize(nl); F.mvKeyLinesUn.resize(nl); F.mLineDescriptors.resize(32 * nl);
+  F.mvKeyLinesRight.resize(nlr); F.mvKeyLinesRightUn.resize(nl > 0 ? nlr : 0); F.mLineDescriptorsRight.resize(32 * nlr);
+  F.mvuRightLineStart.resize(nl); F.mvDepthLineStart.resize(nl); F.mvuRightLineEnd.resize(nl); F.mvDepthLineEnd.resize(nl);
+}
+
 // ------------------------------------------------------------------------------------ dense stereo
 // sgm::StereoSGM (Thirdparty/libsgm/include/libsgm.h:57-110) for 8-bit images and an 8-bit disparity, the way
 // PointCloudKeyFrame::ProcessStereoLibsgm constructs it; execute() is EXECUTE_INOUT_HOST2HOST.

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "frame_geom.hpp"
 
 namespace {
 
@@ -30,22 +31,12 @@ struct RgbdParams {
   float cos_view_z_angle_max;        // Frame::kCosViewZAngleMax, computed on the host
 };
 
-struct V3 {
-  double x, y, z;
-};
-__device__ __forceinline__ V3 v3(float a, float b, float c) { return V3{(double)a, (double)b, (double)c}; }
-__device__ __forceinline__ V3 cross(const V3& a, const V3& b) {
-  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ double sqnorm(const V3& a) { return a.x * a.x + (a.y * a.y + a.z * a.z); }
-__device__ __forceinline__ double norm(const V3& a) { return sqrt(sqnorm(a)); }
-__device__ __forceinline__ double dot(const V3& a, const V3& b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }
-__device__ __forceinline__ V3 normalized(const V3& a) {   // v / sqrt(squaredNorm) when positive
-  const double z2 = sqnorm(a);
-  if (!(z2 > 0.0)) return a;
-  const double s = sqrt(z2);
-  return V3{a.x / s, a.y / s, a.z / s};
-}
+using plvs::V3;
+using plvs::v3;
+using plvs::cross;
+using plvs::norm;
+using plvs::dot;
+using plvs::normalized;   // Eigen::Vector3d in the reference's evaluation order: frame_geom.hpp, shared with frame_stereo.hip
 
 // float -> int as `const int&` binds it (truncation), kept inside [-2, limit + 1]: the 3 x 3 window of anything beyond
 // misses the image either way, and u + du cannot overflow.
@@ -195,7 +186,7 @@ int associate(const plvs_keypoint* kps, const plvs_keypoint* kps_un, int n, cons
   }
   P.mbf = mbf;
   P.min_line_length_3d = min_line_length_3d;
-  P.cos_view_z_angle_max = (float)cos(30. * M_PI / 180.f);   // kCosViewZAngleMax (:103)
+  P.cos_view_z_angle_max = plvs::cos_view_z_angle_max();   // kCosViewZAngleMax (:103)
   plvs::HostStage& st = plvs::thread_stage();
   const size_t f_in = 3 * (size_t)n + 8 * (size_t)nl, f_out = 2 * (size_t)n + 4 * (size_t)nl;
   const size_t o_out = (sizeof(float) * f_in + 15) & ~(size_t)15, o_img = o_out + ((sizeof(float) * f_out + 15) & ~(size_t)15);

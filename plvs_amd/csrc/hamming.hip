@@ -26,21 +26,12 @@
 // (binary_descriptor_matcher_custom.cpp:633-752, 916-941); an item is first
 // seen at the lexicographically smallest (s, k) with popcount(q_k ^ t_k) == s.
 #include "common.hpp"
+#include "hamming_key.hpp"   // the key, insert_key, merge_keys_wave: shared with frame_stereo.hip
 
 namespace {
 
+using plvs::kNoKey;
 constexpr int kWavesPerBlock = 4;
-constexpr unsigned long long kNoKey = ~0ull;
-
-__device__ __forceinline__ void insert_key(unsigned long long key, unsigned long long& b1,
-                                           unsigned long long& b2) {
-  if (key < b1) {
-    b2 = b1;
-    b1 = key;
-  } else if (key < b2) {
-    b2 = key;
-  }
-}
 
 template <bool kMih>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void hamming_knn2_kernel(
@@ -65,48 +56,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void hamming_knn2_kernel(
     const uint4 ta = train[2 * t], tb = train[2 * t + 1];
     const uint32_t x[8] = {ta.x ^ qw[0], ta.y ^ qw[1], ta.z ^ qw[2], ta.w ^ qw[3],
                            tb.x ^ qw[4], tb.y ^ qw[5], tb.z ^ qw[6], tb.w ^ qw[7]};
-    unsigned long long key;
-    if constexpr (kMih) {
-      uint32_t d = 0, s = 9, k = 0, pat = 0;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        // per-byte popcounts of x[w]
-        uint32_t c = x[w] - ((x[w] >> 1) & 0x55555555u);
-        c = (c & 0x33333333u) + ((c >> 2) & 0x33333333u);
-        c = (c + (c >> 4)) & 0x0f0f0f0fu;
-        d += (c * 0x01010101u) >> 24;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t cb = (c >> (8 * j)) & 0xffu;
-          if (cb < s) {  // strict: the first byte reaching the minimum wins
-            s = cb;
-            k = (uint32_t)(w * 4 + j);
-            pat = (x[w] >> (8 * j)) & 0xffu;
-          }
-        }
-      }
-      key = ((unsigned long long)d << 48) | ((unsigned long long)s << 44) |
-            ((unsigned long long)k << 39) | ((unsigned long long)pat << 31) |
-            (unsigned long long)(uint32_t)t;
-    } else {
-      uint32_t d = 0;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) d += (uint32_t)__popc(x[w]);
-      key = ((unsigned long long)d << 48) | (unsigned long long)(uint32_t)t;
-    }
-    insert_key(key, b1, b2);
+    plvs::insert_key(plvs::hamming_key<kMih>(x, t), b1, b2);
   }
-  // Butterfly merge of the 64 sorted pairs.
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long p1 = __shfl_xor(b1, m, 64);
-    const unsigned long long p2 = __shfl_xor(b2, m, 64);
-    const unsigned long long lo = b1 < p1 ? b1 : p1;
-    const unsigned long long hi = b1 < p1 ? p1 : b1;
-    const unsigned long long s2 = b2 < p2 ? b2 : p2;
-    b1 = lo;
-    b2 = hi < s2 ? hi : s2;
-  }
+  plvs::merge_keys_wave(b1, b2);
   if (lane == 0) {
     idx[2 * q] = b1 == kNoKey ? -1 : (int32_t)(b1 & 0x7fffffffull);
     dist[2 * q] = b1 == kNoKey ? -1 : (int32_t)(b1 >> 48);

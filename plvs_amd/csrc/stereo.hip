@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "orb_internal.hpp"
+#include "stereo_internal.hpp"
 
 namespace {
 
@@ -169,6 +170,10 @@ struct plvs_stereo {
   plvs::DevBuf<int> score;
   std::vector<int> h_score;
 };
+
+bool plvs::stereo_made_from(const plvs_stereo* s, const plvs_orb* left, const plvs_orb* right) {
+  return s != nullptr && s->left == left && s->right == right;
+}
 
 extern "C" {
 

@@ -282,3 +282,129 @@ def rgbd_frame(orb: ORBextractor, lines, image: torch.Tensor, depth: torch.Tenso
                 line_descriptors=a["line_desc"][:nl].copy() if lines is not None else np.zeros((0, 32), np.uint8),
                 u_right_start=line("u_right_start"), depth_start=line("depth_start"), u_right_end=line("u_right_end"),
                 depth_end=line("depth_end"), cell_start=a["cell_start"].copy(), cell_items=a["cell_items"][:f.n_items].copy())
+
+
+# ---------------------------------------------------------------------------------------------- Frame glue, stereo
+# What gives the lines of a stereo frame their depth (Frame::ComputeStereoLineMatches, src/Frame.cc:2008-2248, with
+# LineMatcher::SearchStereoMatchesByKnn inside it: one launch) and the stereo constructor (:214-398) as one call.
+SK_LINE_STEREO_MAX_DIST = 20.0    # Tracking::skLineStereoMaxDist (src/Tracking.cc:91)
+TH_LOW_STEREO = 50                # LineMatcher::TH_LOW_STEREO (src/LineMatcher.cc:89)
+STEREO_LINE_CAPACITY = 512        # lines per side of compute_stereo_line_matches
+_LINE_MATCH_ARGS = [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]
+L.plvs_hip_frame_compute_stereo_line_matches.argtypes = _LINE_MATCH_ARGS + [_vp]
+L.plvs_hip_frame_compute_stereo_line_matches_debug.argtypes = _LINE_MATCH_ARGS + [_vp, _vp]
+
+
+def compute_stereo_line_matches(keylines_un, descriptors, keylines_right_un, descriptors_right, line_level_sigma2, K, mbf,
+                                line_stereo_max_dist=SK_LINE_STEREO_MAX_DIST, min_line_length_3d=SK_MIN_LINE_LENGTH_3D, nn_ratio=0.7,
+                                check_orientation=True, descriptor_dist=TH_LOW_STEREO, holders=False):
+    """Frame::ComputeStereoLineMatches on mvKeyLinesUn / mLineDescriptors and their right twins (a rectified pair) ->
+    (mvuRightLineStart, mvDepthLineStart, mvuRightLineEnd, mvDepthLineEnd, lines with depth).  nn_ratio / check_orientation =
+    the LineMatcher(0.7) the reference builds.  holders=True appends the matcher stage's result: [n_right, 4] int32 = holding
+    left line (-1 none), distance, valid after the rotation check, lowest passing left line that named it."""
+    import numpy as np
+    from .lines import KEYLINE_DTYPE
+    kl, klr = np.ascontiguousarray(keylines_un, KEYLINE_DTYPE), np.ascontiguousarray(keylines_right_un, KEYLINE_DTYPE)
+    d, dr = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32), np.ascontiguousarray(descriptors_right, np.uint8).reshape(-1, 32)
+    assert len(kl) == len(d) and len(klr) == len(dr)
+    s2 = np.ascontiguousarray(line_level_sigma2, np.float32).reshape(-1)
+    K4 = np.ascontiguousarray(K, np.float32).reshape(4)
+    out = [np.empty(len(kl), np.float32) for _ in range(4)]
+    ns = _i()
+    args = (_lib.np_ptr(kl), _lib.np_ptr(d), len(kl), _lib.np_ptr(klr), _lib.np_ptr(dr), len(klr), _lib.np_ptr(s2), len(s2), _lib.np_ptr(K4),
+            float(mbf), float(line_stereo_max_dist), float(min_line_length_3d), float(nn_ratio), int(bool(check_orientation)),
+            int(descriptor_dist), *[_lib.np_ptr(o) for o in out], ctypes.byref(ns))
+    if holders:
+        h = np.full((max(len(klr), 1), 4), -1, np.int32)
+        _lib.check(L.plvs_hip_frame_compute_stereo_line_matches_debug(*args, _lib.np_ptr(h), _lib.current_stream_ptr()))
+        return (*out, ns.value, h[:len(klr)])
+    _lib.check(L.plvs_hip_frame_compute_stereo_line_matches(*args, _lib.current_stream_ptr()))
+    return (*out, ns.value)
+
+
+class StereoCalib(ctypes.Structure):     # plvs_stereo_calib
+    _fields_ = [("K4", _f * 4), ("dist", _f * 8), ("ndist", ctypes.c_int32), ("mbf", _f), ("bounds4", _f * 4), ("grid_w_inv", _f),
+                ("grid_h_inv", _f), ("min_line_length_3d", _f), ("line_stereo_max_dist", _f), ("nn_ratio", _f),
+                ("check_orientation", ctypes.c_int32), ("descriptor_dist", ctypes.c_int32), ("n_line_levels", ctypes.c_int32),
+                ("line_level_sigma2", _vp)]
+
+
+class StereoFrameC(ctypes.Structure):    # plvs_stereo_frame
+    _fields_ = [(k, ctypes.c_int32) for k in ("kp_cap", "kp_right_cap", "line_cap", "line_right_cap")] + \
+               [(k, _vp) for k in ("kps", "kps_un", "desc", "u_right", "depth", "cell_start", "cell_items", "kps_right", "desc_right",
+                                   "keylines", "keylines_un", "line_desc", "u_right_start", "depth_start", "u_right_end", "depth_end",
+                                   "keylines_right", "keylines_right_un", "line_desc_right")] + \
+               [(k, ctypes.c_int32) for k in ("n_kp", "mono_index", "n_kp_right", "mono_index_right", "n_lines", "n_lines_right", "n_items",
+                                              "n_stereo_points", "n_stereo_lines")]
+
+
+L.plvs_hip_frame_stereo_dev.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(StereoCalib),
+                                        ctypes.POINTER(StereoFrameC), _vp]
+
+
+def frame_stereo(orb_left: ORBextractor, orb_right: ORBextractor, lines_left, lines_right, stereo, image_left: torch.Tensor,
+                 image_right: torch.Tensor, K, dist, mbf, bounds, grid_w_inv, grid_h_inv, line_level_sigma2=None,
+                 line_stereo_max_dist=SK_LINE_STEREO_MAX_DIST, min_line_length_3d=SK_MIN_LINE_LENGTH_3D, nn_ratio=0.7,
+                 check_orientation=True, descriptor_dist=TH_LOW_STEREO):
+    """The stereo Frame constructor (src/Frame.cc:214-398) in one call on a RECTIFIED pair (dist None or dist[0] == 0): two 2-D
+    uint8 CUDA tensors of one size and stride; lines_left / lines_right = two LineExtractors or both None; stereo = the
+    StereoMatcher made from orb_left and orb_right.  No bounds filter and no compaction of the lines (mvKeyLinesUn = mvKeyLines).
+    -> dict of what the Frame holds: mono_index, keys, keys_un, descriptors, u_right, depth, keys_right, descriptors_right,
+    keylines, keylines_un, line_descriptors, u_right_start, depth_start, u_right_end, depth_end, keylines_right,
+    keylines_right_un, line_descriptors_right, cell_start, cell_items, n_stereo_points, n_stereo_lines."""
+    import numpy as np
+    from .lines import KEYLINE_DTYPE
+    from .orb import KP_DTYPE
+    for im in (image_left, image_right):
+        assert im.is_cuda and im.dtype == torch.uint8 and im.dim() == 2 and im.stride(1) == 1
+    assert image_left.shape == image_right.shape and image_left.stride(0) == image_right.stride(0)
+    torch.cuda.current_stream().synchronize()
+    h, w = image_left.shape
+    K4, d, nd = _calib(K, dist)
+    c = StereoCalib()
+    c.K4[:] = [float(x) for x in K4]
+    for k in range(min(nd, 8)):
+        c.dist[k] = float(d[k])
+    c.ndist, c.mbf = nd, float(mbf)
+    c.bounds4[:] = [float(x) for x in np.asarray(bounds, np.float32)[:4]]
+    c.grid_w_inv, c.grid_h_inv, c.min_line_length_3d = float(grid_w_inv), float(grid_h_inv), float(min_line_length_3d)
+    c.line_stereo_max_dist, c.nn_ratio = float(line_stereo_max_dist), float(nn_ratio)
+    c.check_orientation, c.descriptor_dist = int(bool(check_orientation)), int(descriptor_dist)
+    s2 = None if line_level_sigma2 is None else np.ascontiguousarray(line_level_sigma2, np.float32).reshape(-1)
+    c.n_line_levels, c.line_level_sigma2 = (0 if s2 is None else len(s2)), (None if s2 is None else s2.ctypes.data)
+    with_lines = lines_left is not None
+    ncap, rcap = orb_left._cap, orb_right._cap
+    lcap, lrcap = (lines_left._cap, lines_right._cap) if with_lines else (0, 0)
+    a = dict(kps=np.zeros(ncap, KP_DTYPE), kps_un=np.zeros(ncap, KP_DTYPE), desc=np.zeros((ncap, 32), np.uint8),
+             u_right=np.zeros(ncap, np.float32), depth=np.zeros(ncap, np.float32), cell_start=np.zeros(64 * 48 + 1, np.int32),
+             cell_items=np.zeros(ncap, np.int32), kps_right=np.zeros(rcap, KP_DTYPE), desc_right=np.zeros((rcap, 32), np.uint8))
+    if with_lines:
+        a.update(keylines=np.zeros(lcap, KEYLINE_DTYPE), keylines_un=np.zeros(lcap, KEYLINE_DTYPE), line_desc=np.zeros((lcap, 32), np.uint8),
+                 keylines_right=np.zeros(lrcap, KEYLINE_DTYPE), keylines_right_un=np.zeros(lrcap, KEYLINE_DTYPE),
+                 line_desc_right=np.zeros((lrcap, 32), np.uint8),
+                 **{k: np.zeros(lcap, np.float32) for k in ("u_right_start", "depth_start", "u_right_end", "depth_end")})
+    f = StereoFrameC()
+    f.kp_cap, f.kp_right_cap, f.line_cap, f.line_right_cap = ncap, rcap, lcap, lrcap
+    for k, v in a.items():
+        setattr(f, k, v.ctypes.data)
+    _lib.check(L.plvs_hip_frame_stereo_dev(orb_left._h, orb_right._h, lines_left._h if with_lines else None,
+                                           lines_right._h if with_lines else None, stereo._h if stereo is not None else None,
+                                           _vp(image_left.data_ptr()), _vp(image_right.data_ptr()), w, h, image_left.stride(0),
+                                           ctypes.byref(c), ctypes.byref(f), _lib.current_stream_ptr()))
+    n, nr, nl, nlr = f.n_kp, f.n_kp_right, f.n_lines, f.n_lines_right
+    nlru = nlr if nl > 0 else 0           # mvKeyLinesRightUn is filled by UndistortKeyLines: only when left lines were found
+    empty = dict(keylines=np.zeros(0, KEYLINE_DTYPE), line_desc=np.zeros((0, 32), np.uint8))      # without line extractors
+
+    def take(k, m):
+        if with_lines:
+            return a[k][:m].copy()
+        return empty.get(k.replace("_right", "").replace("_un", ""), np.zeros(0, np.float32)).copy()
+
+    return dict(mono_index=f.mono_index, keys=a["kps"][:n].copy(), keys_un=a["kps_un"][:n].copy(), descriptors=a["desc"][:n].copy(),
+                u_right=a["u_right"][:n].copy(), depth=a["depth"][:n].copy(), keys_right=a["kps_right"][:nr].copy(),
+                descriptors_right=a["desc_right"][:nr].copy(), keylines=take("keylines", nl), keylines_un=take("keylines_un", nl),
+                line_descriptors=take("line_desc", nl), u_right_start=take("u_right_start", nl), depth_start=take("depth_start", nl),
+                u_right_end=take("u_right_end", nl), depth_end=take("depth_end", nl), keylines_right=take("keylines_right", nlr),
+                keylines_right_un=take("keylines_right_un", nlru), line_descriptors_right=take("line_desc_right", nlr),
+                cell_start=a["cell_start"].copy(), cell_items=a["cell_items"][:f.n_items].copy(),
+                n_stereo_points=f.n_stereo_points, n_stereo_lines=f.n_stereo_lines)
