@@ -22,6 +22,36 @@ def _clustered_desc(rng, n, nbase=8, flips=6):
     return out
 
 
+def _identical_desc(rng, nq, nt):
+    """Every query and train descriptor the same: all distances 0, both ranks decided by the train index alone."""
+    one = _rand_desc(rng, 1)
+    return np.repeat(one, nq, axis=0), np.repeat(one, nt, axis=0)
+
+
+def _interleaved_desc(rng, nq, nt):
+    """Train set A, B, A, B, ...; queries A, B, and copies of them a few bits off: every query ties with half of the
+    train set, spread evenly over the lanes of a wave."""
+    ab = _rand_desc(rng, 2)
+    t = ab[np.arange(nt) % 2].copy()
+    q = ab[rng.integers(0, 2, nq)].copy()
+    for i in range(nq):
+        for _ in range(int(rng.integers(0, 4))):
+            b = int(rng.integers(0, 256))
+            q[i, b >> 3] ^= np.uint8(1 << (b & 7))
+    return q, t
+
+
+TIE_CASES = [(gen, nq, nt, seed) for gen in ("identical", "interleaved")
+             for nq, nt, seed in ((70, 63, 1), (5, 64, 2), (70, 65, 3), (33, 129, 4), (3, 2, 5))]
+
+
+def _tie_case(gen, nq, nt, seed):
+    rng = np.random.default_rng(seed)
+    q, t = (_identical_desc if gen == "identical" else _interleaved_desc)(rng, nq, nt)
+    mask = None if seed % 2 == 0 else (rng.integers(0, 4, size=nq) > 0).astype(np.uint8)
+    return q, t, mask
+
+
 def _np_dist_matrix(q, t):
     x = q[:, None, :] ^ t[None, :, :]
     return np.unpackbits(x, axis=2).sum(axis=2).astype(np.int32)
@@ -84,6 +114,32 @@ def test_oracle_mih_matches_stated_tie_rule(oracle, nq, nt, seed, clustered):
     assert np.array_equal(idx, ridx)
 
 
+@pytest.mark.parametrize("gen,nq,nt,seed", TIE_CASES)
+def test_oracle_total_ties_match_numpy(oracle, gen, nq, nt, seed):
+    q, t, mask = _tie_case(gen, nq, nt, seed)
+    on = np.ones(nq, bool) if mask is None else mask.astype(bool)
+    for mih, ref in ((False, _np_knn2_lowest), (True, _np_knn2_mih)):
+        idx, dist = oracle.knn2(q, t, mask, mih=mih)
+        ridx, rdist = ref(q, t)
+        assert np.array_equal(dist[on], rdist[on]) and np.array_equal(idx[on], ridx[on])
+        assert (idx[~on] == -1).all() and (dist[~on] == -1).all()
+        if gen == "identical":                                    # index alone decides
+            assert (idx[on] == [0, 1]).all() and (dist[on] == 0).all()
+        elif nt > 3:                                              # the two nearest: the first two of one parity, tied
+            assert (idx[on, 1] - idx[on, 0] == 2).all() and (idx[on, 0] < 2).all()
+            assert (dist[on, 0] == dist[on, 1]).all()
+
+
+@pytest.mark.parametrize("nt", [63, 64, 65, 129])
+def test_oracle_bf_and_mih_at_wave_edges(oracle, nt):
+    rng = np.random.default_rng(nt)
+    q, t = _clustered_desc(rng, 37), _clustered_desc(rng, nt)
+    for mih, ref in ((False, _np_knn2_lowest), (True, _np_knn2_mih)):
+        idx, dist = oracle.knn2(q, t, mih=mih)
+        ridx, rdist = ref(q, t)
+        assert np.array_equal(dist, rdist) and np.array_equal(idx, ridx)
+
+
 def test_oracle_mask_and_degenerate(oracle):
     rng = np.random.default_rng(7)
     q, t = _rand_desc(rng, 5), _rand_desc(rng, 1)
@@ -120,6 +176,42 @@ def test_hip_knn2_matches_oracle(oracle, nq, nt, seed, clustered, mih):
     torch.cuda.synchronize()
     assert np.array_equal(didx.cpu().numpy(), oidx)
     assert np.array_equal(ddist.cpu().numpy(), odist)
+
+
+def _hip_both_flavours(q, t, mask, mih):
+    import torch
+    from plvs_amd import _lib
+    from plvs_amd.matcher import knn2_raw
+    rule = _lib.TIE_MIH if mih else _lib.TIE_LOWEST_INDEX
+    idx, dist = knn2_raw(q, t, mask, rule)                         # host flavour
+    dm = None if mask is None else torch.from_numpy(mask).cuda()
+    didx, ddist = knn2_raw(torch.from_numpy(q).cuda(), torch.from_numpy(t).cuda(), dm, rule)   # device flavour
+    torch.cuda.synchronize()
+    return (idx, dist), (didx.cpu().numpy(), ddist.cpu().numpy())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nt", [63, 64, 65, 129])
+@pytest.mark.parametrize("mih", [False, True])
+def test_hip_knn2_at_wave_edges(oracle, nt, mih):
+    """Train sets one short of a wave, a wave, one more, and two waves and one."""
+    rng = np.random.default_rng(nt)
+    q, t = _clustered_desc(rng, 37), _clustered_desc(rng, nt)
+    mask = None if nt % 2 == 0 else (rng.integers(0, 4, size=37) > 0).astype(np.uint8)
+    oidx, odist = oracle.knn2(q, t, mask, mih=mih)
+    for idx, dist in _hip_both_flavours(q, t, mask, mih):
+        assert np.array_equal(dist, odist) and np.array_equal(idx, oidx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gen,nq,nt,seed", TIE_CASES)
+@pytest.mark.parametrize("mih", [False, True])
+def test_hip_knn2_total_ties(oracle, gen, nq, nt, seed, mih):
+    """Every rank decided by the train index alone, across the lanes and through the merge of the lanes' lists."""
+    q, t, mask = _tie_case(gen, nq, nt, seed)
+    oidx, odist = oracle.knn2(q, t, mask, mih=mih)
+    for idx, dist in _hip_both_flavours(q, t, mask, mih):
+        assert np.array_equal(dist, odist) and np.array_equal(idx, oidx)
 
 
 @pytest.mark.gpu

@@ -168,6 +168,39 @@ def test_hip_projection_search_matches_oracle(oracle, seed, stereo, edge, larger
     assert want_n > 5 and got_n == want_n and np.array_equal(got, want)
 
 
+# 520 x 520 = 270 400 descriptor pairs are more than the 2^18 = 262 144 up to which the library computes the whole
+# distance matrix: the candidates' distances then come from the pair-list launch.  512 x 512 = 2^18 is the last matrix size.
+LARGE = [(1, 520, False), (2, 520, True), (1, 512, True)]
+
+
+@pytest.mark.parametrize("seed,n,stereo", LARGE)
+def test_oracle_projection_search_large_case(oracle, seed, n, stereo):
+    assert (n * n > 2 ** 18) == (n == 520)
+    c = make_case(seed, n_cur=n, n_last=n, stereo=stereo)
+    n_ff, a = oracle_ff(oracle, c, False, 0, 0.8, True)
+    assert n_ff > 50 and not c["occupied"][a >= 0].any() and c["valid"][a[a >= 0]].all()
+    n_map, a = oracle_map(oracle, c, False, 0.8)
+    assert n_map > 50 and not c["occupied"][a >= 0].any() and c["valid"][a[a >= 0]].all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n,stereo", LARGE)
+def test_hip_projection_search_large_matches_oracle(oracle, seed, n, stereo):
+    """Both sides of the switch between the distance matrix and the pair list."""
+    from plvs_amd.linematcher import LineMatcher, line_frame_view
+    c = make_case(seed, n_cur=n, n_last=n, stereo=stereo)
+    view = line_frame_view(c["kl"], c["desc"], SCALE, INV_SIGMA2, MAX_DIAG, c["urs"], c["ure"], c["bf"])
+    m = LineMatcher(0.8, True)
+    want_n, want = oracle_ff(oracle, c, False, 0, 0.8, True)
+    got_n, got = m.SearchByProjectionLastFrame(view, c["valid"], c["proj"], c["octave"], c["angle"], c["ldesc"],
+                                               occupied=c["occupied"], has_obs=c["has_obs"], bLargerSearch=False, direction=0)
+    assert got_n == want_n > 50 and np.array_equal(got, want)
+    want_n, want = oracle_map(oracle, c, False, 0.8)
+    got_n, got = m.SearchByProjection(view, c["valid"], c["proj_map"], c["octave"], c["ldesc"], occupied=c["occupied"],
+                                      has_obs=c["has_obs"], bLargerSearch=False)
+    assert got_n == want_n > 50 and np.array_equal(got, want)
+
+
 @pytest.mark.gpu
 def test_hip_projection_search_edge_cases(oracle):
     from plvs_amd import _lib

@@ -53,6 +53,23 @@ def test_search_by_projection_mappoints(oracle, ref, seed, th, far):
     assert np.array_equal(got, want)
 
 
+@pytest.mark.parametrize("far", [False, True])
+@pytest.mark.parametrize("seed,th,n_crowd", [(1, 1.0, 256), (2, 5.0, 256), (3, 1.0, 320), (1, 5.0, 256), (3, 3.0, 256)])
+def test_search_by_projection_mappoints_crowd(oracle, ref, seed, th, n_crowd, far):
+    """The crowded frame with a grid origin off zero, border and out-of-grid keypoints, clipped and empty windows."""
+    F, M, occ, sets = tos.make_crowd_case(seed, n_crowd)
+    want_n, want = tos.oracle_search(oracle.lib, F, M, th, far, 40.0, 0.8, occ)
+    fc, mc = F.as_c(), M.as_c()
+    got = np.full(fc.n, -7, np.int32)
+    fn = ref.ref_orb_search_by_projection
+    fn.argtypes = [_vp, _vp, _f, _i, _f, _f, _vp, _vp]
+    fn.restype = _i
+    got_n = fn(ctypes.byref(fc), ctypes.byref(mc), th, int(far), 40.0, 0.8, _p(occ), _p(got))
+    assert got_n == want_n >= 40
+    assert np.array_equal(got, want)
+    assert (got[sets["outside"]] == -1).all()
+
+
 def test_search_by_projection_mappoints_small_and_empty(oracle, ref):
     fn = ref.ref_orb_search_by_projection
     fn.argtypes = [_vp, _vp, _f, _i, _f, _f, _vp, _vp]
@@ -101,8 +118,26 @@ def _handed_over(Tcw, xyz_w):
 @pytest.mark.parametrize("seed,th,direction,check", [(1, 15.0, 0, 1), (2, 7.0, 0, 1), (3, 15.0, 1, 1), (4, 30.0, 2, 0),
                                                      (6, 15.0, 0, 0)])
 def test_search_by_projection_last_frame(oracle, ref, seed, th, direction, check):
+    got_n, got, want_n, want = _run_last_frame(oracle, ref, tos.make_ff_case(seed), seed, th, direction, check)
+    assert got_n == want_n > 30
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("seed,th,direction,check", [(1, 15.0, 0, 1), (1, 30.0, 1, 0), (2, 15.0, 2, 1), (2, 30.0, 0, 0),
+                                                     (2, 15.0, 1, 1), (1, 30.0, 2, 0)])
+def test_search_by_projection_last_frame_crowd(oracle, ref, seed, th, direction, check):
+    """The crowded frame (grid origin off zero, bounds outside the image): the level gates of a forward / backward
+    motion on crowded windows."""
+    case = tos.make_crowd_ff_case(seed)
+    got_n, got, want_n, want = _run_last_frame(oracle, ref, case[:7], seed, th, direction, check)
+    assert got_n == want_n >= tos.FF_CROWD_FLOOR
+    assert np.array_equal(got, want)
+    assert (got[case[7]["outside"]] == -1).all()
+
+
+def _run_last_frame(oracle, ref, case, seed, th, direction, check):
     from plvs_amd.orbmatcher import LastFrameView
-    F, cur_angle, max_x, max_y, mbf, L, occ = tos.make_ff_case(seed)
+    F, cur_angle, max_x, max_y, mbf, L, occ = case
     rng = np.random.default_rng(seed + 500)
     Tcw = _pose(rng, 7.0, rng.uniform(-0.3, 0.3, 3))
     # world points whose projection is about what the case asks for (points behind the camera for invz < 0)
@@ -131,8 +166,7 @@ def test_search_by_projection_last_frame(oracle, ref, seed, th, direction, check
     desc, has_obs = c32(L.desc, np.uint8), c32(L.has_obs, np.uint8)
     got_n = fn(ctypes.byref(fc), _p(c32(cur_angle, np.float32)), max_x, max_y, mbf, mb, _p(Tcw), _p(Tlw), _p(CAM), len(valid),
                _p(valid), _p(xyz_w), _p(octave), _p(angle), _p(desc), _p(has_obs), th, 0, 0.9, check, _p(occ), _p(got))
-    assert got_n == want_n > 30
-    assert np.array_equal(got, want)
+    return got_n, got, want_n, want
 
 
 # ---------------------------------------------------------------- ORBmatcher::SearchByBoW(pKF, F)
@@ -148,6 +182,22 @@ def test_search_by_bow(oracle, ref, seed, ratio, check):
     got_n = fn(ctypes.byref(kc), _p(kd), kd.shape[0], _p(kv), _p(ka), ctypes.byref(fc), _p(fd), fd.shape[0], _p(fa), ratio,
                check, _p(got))
     assert got_n == want_n > 100
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("seed,ratio,check", [(1, 0.7, 1), (2, 0.9, 0)])
+def test_search_by_bow_sparse(oracle, ref, seed, ratio, check):
+    """30 % of the key frame's keypoints hold a map point: most pairs of a common node are never formed."""
+    KV, kd, kv, ka, FV, fd, fa = tos.make_bow_case(seed, valid_frac=0.3)
+    want_n, want = tos.oracle_search_bow(oracle.lib, KV, kd, kv, ka, FV, fd, fa, ratio, check)
+    kc, fc = KV.as_c(), FV.as_c()
+    got = np.full(fd.shape[0], -7, np.int32)
+    fn = ref.ref_orb_search_by_bow
+    fn.argtypes = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _i, _vp]
+    fn.restype = _i
+    got_n = fn(ctypes.byref(kc), _p(kd), kd.shape[0], _p(kv), _p(ka), ctypes.byref(fc), _p(fd), fd.shape[0], _p(fa), ratio,
+               check, _p(got))
+    assert got_n == want_n > tos.BOW_SPARSE_FLOOR
     assert np.array_equal(got, want)
 
 
@@ -221,6 +271,20 @@ def _line_view(c):
                                                           (5, True, False, True, 0.8)])
 def test_lines_search_by_projection_maplines(oracle, ref, seed, stereo, edge, larger, ratio):
     c = tlp.make_case(seed, n_cur=150, n_last=130, stereo=stereo, theta_edge=edge)
+    got_n, got, want_n, want = _run_maplines(oracle, ref, c, larger, ratio)
+    assert got_n == want_n > 20
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("seed,n,stereo", tlp.LARGE)
+def test_lines_search_by_projection_maplines_large(oracle, ref, seed, n, stereo):
+    c = tlp.make_case(seed, n_cur=n, n_last=n, stereo=stereo)
+    got_n, got, want_n, want = _run_maplines(oracle, ref, c, False, 0.8)
+    assert got_n == want_n > 50
+    assert np.array_equal(got, want)
+
+
+def _run_maplines(oracle, ref, c, larger, ratio):
     want_n, want = tlp.oracle_map(oracle, c, larger, ratio)
     F, keep = _line_view(c)
     got = np.full(len(c["kl"]), -7, np.int32)
@@ -229,8 +293,7 @@ def test_lines_search_by_projection_maplines(oracle, ref, seed, stereo, edge, la
     fn.argtypes = [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp]
     got_n = fn(ctypes.byref(F), tlp._p(c["occupied"]), len(c["valid"]), tlp._p(c["valid"]), tlp._p(c["proj_map"]),
                tlp._p(c["octave"]), tlp._p(c["ldesc"]), tlp._p(c["has_obs"]), int(larger), ratio, _p(got))
-    assert got_n == want_n > 20
-    assert np.array_equal(got, want)
+    return got_n, got, want_n, want
 
 
 def _f32(a):
@@ -262,6 +325,20 @@ def _project_lines(Tcw, xyz_w, bounds):
                                                                     (6, True, False, True, 0, True)])
 def test_lines_search_by_projection_last_frame(oracle, ref, seed, stereo, edge, larger, direction, check):
     c = tlp.make_case(seed, n_cur=150, n_last=130, stereo=stereo, theta_edge=edge)
+    got_n, got, want_n, want = _run_lines_last_frame(oracle, ref, c, seed, larger, direction, check)
+    assert got_n == want_n > 15
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("seed,n,stereo", tlp.LARGE)
+def test_lines_search_by_projection_last_frame_large(oracle, ref, seed, n, stereo):
+    c = tlp.make_case(seed, n_cur=n, n_last=n, stereo=stereo)
+    got_n, got, want_n, want = _run_lines_last_frame(oracle, ref, c, seed, False, 0, True)
+    assert got_n == want_n > 50
+    assert np.array_equal(got, want)
+
+
+def _run_lines_last_frame(oracle, ref, c, seed, larger, direction, check):
     rng = np.random.default_rng(seed + 900)
     Tcw = _pose(rng, 6.0, rng.uniform(-0.2, 0.2, 3))
     # world end points whose projections are about the case's (depth = 1 / proj[:, 4:6])
@@ -289,22 +366,22 @@ def test_lines_search_by_projection_last_frame(oracle, ref, seed, stereo, edge, 
     got_n = fn(ctypes.byref(F), tlp._p(c["occupied"]), _p(bounds), mb, _p(Tcw), _p(Tlw), _p(CAM), len(c["valid"]),
                tlp._p(c["valid"]), _p(xyz_w), tlp._p(c["octave"]), tlp._p(c["angle"]), tlp._p(c["ldesc"]), tlp._p(c["has_obs"]),
                int(larger), 0, 0.8, int(check), _p(got))
-    assert got_n == want_n > 15
-    assert np.array_equal(got, want)
+    return got_n, got, want_n, want
 
 
 # ---------------------------------------------------------------- Frame::ComputeStereoMatches
 from tests import test_stereo as tst  # noqa: E402
 
 
-@pytest.mark.parametrize("name,nfeatures", [("urban1", 2000), ("shift17", 1000), ("swapped", 1000)])
+@pytest.mark.parametrize("name,nfeatures", [("urban1", 2000), ("shift17", 1000), ("swapped", 1000), ("same", 1000),
+                                            ("hinge", 1000)])
 def test_frame_compute_stereo_matches(oracle, ref, name, nfeatures):
     """The reference's own extractor and Frame::ComputeStereoMatches on the pair against the oracle's extractor +
     oracle/stereo.c: the same mvuRight / mvDepth, bit for bit."""
     left, right = tst.pair(name)
     (kl, dl, pl), (kr, dr, pr) = tst.oracle_side(oracle, left, right, nfeatures)
     s, inv = tst.scale_tables()
-    want_u, want_z, _, kept = oracle.stereo_matches(kl, dl, kr, dr, pl, pr, s, inv, tst.MB, np.float32(tst.KITTI_BF))
+    want_u, want_z, _score, kept = oracle.stereo_matches(kl, dl, kr, dr, pl, pr, s, inv, tst.MB, np.float32(tst.KITTI_BF))
     left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
     cap = kl.shape[0] + 16
     u, z = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
@@ -317,5 +394,9 @@ def test_frame_compute_stereo_matches(oracle, ref, name, nfeatures):
     assert n == kl.shape[0] and nr.value == kr.shape[0]
     assert u[:n].tobytes() == want_u.tobytes()
     assert z[:n].tobytes() == want_z.tobytes()
-    if name != "swapped":
+    if name == "same":
+        tst.check_same(u[:n], z[:n], _score, kept)                # median 0 cuts everything in the reference too
+    elif name == "hinge":
+        tst.check_hinge(kl, u[:n], z[:n], _score, kept)           # the reference's own disparity <= 0 clamp
+    elif name != "swapped":
         assert kept > 0.25 * n
