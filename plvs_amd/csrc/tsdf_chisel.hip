@@ -301,7 +301,7 @@ int plvs_hip_tsdf_chisel_destroy(plvs_tsdf_chisel* h) {
   if (h->h_sh_ctl) (void)hipHostFree(h->h_sh_ctl);
   if (h->h_sh_off) (void)hipHostFree(h->h_sh_off);
   h->q_xyz.release(); h->q_rgb.release(); h->q_kfid.release();
-  h->w_rec.release(); h->w_seg.release(); h->w_sorted_seg.release(); h->w_chunk_nseg.release();
+  h->w_rec.release(); h->w_seg.release(); h->w_sorted_seg.release(); h->w_seg_ticket.release(); h->w_chunk_nseg.release();
   h->w_chunk_off.release(); h->w_chunk_fill.release(); h->w_active_off.release(); h->w_masks.release();
   h->w_dummy.release(); h->w_runkey.release(); h->w_run_cnt.release(); h->w_run_off.release(); h->w_val0.release();
   h->w_val1.release(); h->w_seg_cnt.release(); h->w_tile_visits.release(); h->w_deferred.release(); h->w_part_off.release(); h->w_multi_idx.release();

@@ -134,6 +134,7 @@ struct plvs_tsdf_chisel {
   uint32_t seq_next = 0;
   double wait_ema_us[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};       // how long the host's last waits for the published counters took (wait_published)
   DevBuf<uint4> w_rec, w_seg, w_sorted_seg;
+  DevBuf<uint32_t> w_seg_ticket;   // per segment descriptor slot of w_seg: its index among its chunk's segments (AccOut::seg_ticket)
   // a long call's runs chunk by chunk (runs_count ... parts_place): the segments' run descriptors and the runs of the
   // same row in the block's earlier tiles; runs per (row, block); chunk slot -> place among the updated; region, runs and
   // first part of every row; the parts' rows and histograms

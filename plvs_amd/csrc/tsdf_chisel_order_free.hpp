@@ -125,7 +125,8 @@ static int reserve_chunk_tables(plvs_tsdf_chisel* h, size_t chunks, uint32_t par
 }
 
 // ---- segment sort (w_seg -> w_sorted_seg, by chunk) and apply stage: seg_pass<false> counts the chunks' segments where the
-// walk has not (AccOut::chunk_nseg), seg_scan scans and lists the updated chunks, seg_pass<true> places.
+// walk has not (AccOut::chunk_nseg), seg_scan scans and lists the updated chunks, seg_pass<true> places.  Where the walk
+// has counted them, every segment holds a ticket and seg_place — or runs_count — places it without counting again.
 
 // The descriptor slots a pass looks at: the tiles' own regions and the spill area behind them (walk_out), or a dense list
 // of seg_cap descriptors (ntiles = 0, no seg_cnt).
@@ -134,11 +135,21 @@ struct SegSrc {
   uint32_t seg_cap, ntiles;
   const uint32_t* seg_cnt;
 };
-template <bool kScatter, int kSpan = kSegSpan>
+template <bool kScatter>
 static void launch_seg_pass(plvs_tsdf_chisel* h, const SegSrc& src, hipStream_t q) {
-  hipLaunchKernelGGL((seg_pass<kScatter, kSpan>), dim3(ceil_div(src.slots, kSpan)), dim3(256), 0, q, h->w_seg.p, src.seg_cap,
+  hipLaunchKernelGGL((seg_pass<kScatter>), dim3(ceil_div(src.slots, kSegSpan)), dim3(256), 0, q, h->w_seg.p, src.seg_cap,
                      src.ntiles, src.seg_cnt, h->w_chunk_nseg.p, h->w_chunk_off.p, h->w_chunk_fill.p, h->w_sorted_seg.p,
                      h->d_wctr);
+}
+// The place of the walk's ticketed segments in chunk order (w_sorted_seg holds two uint4 per segment).
+static SegPlace seg_place_args(const plvs_tsdf_chisel* h, uint32_t seg_cap) {
+  return SegPlace{h->w_seg_ticket.p, h->w_chunk_off.p, h->w_sorted_seg.p, (uint32_t)std::min<size_t>(h->w_sorted_seg.cap / 2, 0xFFFFFFFFu),
+                  seg_cap};
+}
+static void launch_seg_place(plvs_tsdf_chisel* h, const SegSrc& src, hipStream_t q) {
+  const SegPlace a = seg_place_args(h, src.seg_cap);
+  hipLaunchKernelGGL(seg_place, dim3(ceil_div(src.slots, 256)), dim3(256), 0, q, h->w_seg.p, a.ticket, src.seg_cap, src.ntiles,
+                     src.seg_cnt, a.chunk_off, a.sorted, a.sorted_cap, h->d_wctr);
 }
 
 // num_chunks / chunk_cap: the directory the segments' slots belong to; tile_visits, run_cnt: per tile, summed on the way
@@ -197,6 +208,7 @@ static int reserve_walk_scratch(plvs_tsdf_chisel* h, uint32_t ntiles, const Walk
   if (h->w_rec.cap < w.rec_own + w.rec_spill) PLVS_HIP_TRY(h->w_rec.reserve(2 * w.rec_own + w.rec_spill));
   if (h->w_seg.cap < 2 * (w.seg_own + w.seg_spill)) PLVS_HIP_TRY(h->w_seg.reserve(2 * (2 * w.seg_own + w.seg_spill)));
   PLVS_HIP_TRY(h->w_sorted_seg.reserve(h->w_seg.cap));
+  PLVS_HIP_TRY(h->w_seg_ticket.reserve(h->w_seg.cap / 2));
   const size_t run_slots = (size_t)ntiles << h->run_r1_log2;
   if (h->w_runkey.cap < run_slots) {
     PLVS_HIP_TRY(h->w_runkey.reserve(2 * run_slots));
@@ -207,7 +219,8 @@ static int reserve_walk_scratch(plvs_tsdf_chisel* h, uint32_t ntiles, const Walk
 }
 static AccOut walk_out(const plvs_tsdf_chisel* h, const WalkScratch& w, uint32_t* chunk_nseg) {
   return AccOut{h->w_rec.p, (uint32_t)std::min<size_t>(w.rec_own + w.rec_spill, 0xFFFFFFFFu), h->w_seg.p,
-                (uint32_t)std::min<size_t>(w.seg_own + w.seg_spill, 0xFFFFFFFFu), h->w_seg_cnt.p, h->w_tile_visits.p, chunk_nseg};
+                (uint32_t)std::min<size_t>(w.seg_own + w.seg_spill, 0xFFFFFFFFu), h->w_seg_cnt.p, h->w_tile_visits.p, chunk_nseg,
+                chunk_nseg ? h->w_seg_ticket.p : nullptr};
 }
 // kErrScratch: room for twice what the walk asked for (h_wctr).  false: the tiles' run slots would leave the index range.
 static bool grow_walk_scratch(plvs_tsdf_chisel* h, uint32_t ntiles, WalkScratch& w) {
@@ -277,7 +290,8 @@ static int segments_and_apply(plvs_tsdf_chisel* h, const WalkPlan& plan, const W
     const bool queued = plan.chain == kChainCollected;   // (rows_place then publishes the walk's counters for the host)
     PLVS_HIP_TRY(hipStreamWaitEvent(q, h->ev_zero, 0));
     hipLaunchKernelGGL(runs_count, dim3(plan.collect_blocks), dim3(kSegSpan), 0, q, h->w_seg.p, h->w_rseg.p, c.ntiles, h->w_seg_cnt.p,
-                       h->w_active_idx.p, plan.collect_rows, plan.collect_blocks, h->w_run_matrix.p, h->w_rpre.p, h->d_wctr, c.last_count);
+                       h->w_active_idx.p, plan.collect_rows, plan.collect_blocks, h->w_run_matrix.p, h->w_rpre.p, h->d_wctr, c.last_count,
+                       seg_place_args(h, c.out.seg_cap));
     hipLaunchKernelGGL(runs_rowscan, dim3(std::min<uint32_t>(ceil_div(plan.collect_rows, 4), 1024u)), dim3(256), 0, q,
                        h->w_run_matrix.p, plan.collect_rows, plan.collect_blocks, h->d_wctr, h->w_item_cnt.p);
     hipLaunchKernelGGL(rows_place, dim3(1), dim3(1024), 0, q, h->w_item_cnt.p, plan.collect_rows, plan.collect_bound,
@@ -288,11 +302,9 @@ static int segments_and_apply(plvs_tsdf_chisel* h, const WalkPlan& plan, const W
                        queued ? c.collect_seq : 0u);
     PLVS_HIP_TRY(hipEventRecord(h->ev_seg, q));
   }
-  // (a long call: 4096 descriptor slots — 64 tiles — per workgroup instead of 1024: a quarter of the workgroups, and what
-  // the kernel waits for is their atomics on the counters of a hundred-odd chunks)
-  const SegSrc src{c.seg_slots, c.out.seg_cap, c.ntiles, h->w_seg_cnt.p};
-  if (plan.size_class == 2) launch_seg_pass<true, kSegSpanLong>(h, src, q);
-  else launch_seg_pass<true>(h, src, q);
+  // (the walk has ticketed its segments: runs_count has placed them on its way, whatever the chain then does; no launch
+  // between the counting stages and the apply stage)
+  if (!plan.collect_ready) launch_seg_place(h, SegSrc{c.seg_slots, c.out.seg_cap, c.ntiles, h->w_seg_cnt.p}, q);
   PLVS_HIP_TRY(stage_mark(h, 2, q));
   launch_apply<false, false>(h, h->w_rec.p, c.d_kfid, EmitOut{}, c.gsrc ? c.gsrc->key_bits : 0u, q);
   PLVS_KERNEL_CHECK();

@@ -16,7 +16,10 @@
 //               voxel is still below 254 the log is turned into the BIT MASK of the tile's rays that
 //               visit the voxel — a ray visits a voxel at most once, so ray order = point order = the
 //               reference's update order — and one run (voxel key + mask) leaves the tile.
-//   seg_pass / seg_scan           counting sort of the segment descriptors by chunk (LDS-aggregated).
+//   seg_scan, seg_place           the segment descriptors to chunk order: the walk counts a chunk's segments as it
+//               writes them, the count's old value is the segment's place among them (a ticket per descriptor),
+//               seg_scan scans the counts and a scatter places — seg_place, or runs_count on its way in a long call.
+//               (seg_pass: the counting sort, LDS-aggregated, for segments nobody has ticketed: the ray-sharded integrate.)
 //   apply_chunks                  "LDS-staged blocks": a workgroup owns a slab of one chunk, adds the
 //               slab's records into 64-bit LDS accumulators and applies ONE update per voxel,
 //                   sdf <- (W * sdf + sum w_u u) / (W + sum w_u),   W <- W + sum w_u,
@@ -685,6 +688,10 @@ struct AccOut {
   // (tile, chunk), spread over the walk — instead of by a pass over every descriptor slot behind it (seg_pass<false>:
   // 46 us for the 960 000 slots of a 100-key-frame call, nine tenths of them empty).  nullptr: seg_pass<false> counts.
   uint32_t* chunk_nseg;
+  // ... and what that atomic returns is the segment's index among its chunk's: a TICKET, kept per descriptor slot (indexed
+  // like seg's segments: the tiles' own regions and the spill area).  chunk_off[slot] + ticket is the descriptor's place in
+  // chunk order (place_segment) — no pass that counts them again.  Set together with chunk_nseg.
+  uint32_t* seg_ticket;
 };
 // Runs: one descriptor + 256-bit ray mask per (tile, voxel) that needs its visits in order.
 // Tile t owns run slots [t << r1_log2, (t + 1) << r1_log2) and fills them from the front, in the order
@@ -1003,6 +1010,9 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
       // regions from the spill counters: wave 0 scans, the others wait.
       const bool own_region = flushes == 0;
       uint32_t rbase = tile * rec_stride;
+      // (the chunk's ticket is asked for where the segment is known and stored behind the records: a returning
+      // device-scope atomic is a round trip to the L2, nothing waits for it in front of the record stores)
+      uint32_t ticket = 0, ticket_sg = 0xFFFFFFFFu;
       if (own_region || tid < 64) {
         const int cl = lane;   // the chunk of this lane
         uint32_t sub[kSlabs], c = 0;
@@ -1036,9 +1046,12 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
         if (c && tid < 64) {
           const uint32_t sg = sbase + sinc - 1u;
           if (sg < out.seg_cap) {
+            if (out.chunk_nseg) {
+              ticket = atomicAdd(&out.chunk_nseg[S.cslot[cl]], 1u);
+              ticket_sg = sg;
+            }
             out.seg[2 * (size_t)sg] = make_uint4((uint32_t)S.cslot[cl], rbase + inc - c, c, gtile);
             out.seg[2 * (size_t)sg + 1] = pack_suboffsets(sub);
-            if (out.chunk_nseg) atomicAdd(&out.chunk_nseg[S.cslot[cl]], 1u);
           }
         }
       }
@@ -1054,7 +1067,7 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
         const uint4 r = make_uint4(vid | ((uint32_t)(ewc[k] >> 32) << 12),
                                    grid ? grid_order_key(*grid, gt, elast[k]) : first + elast[k], (uint32_t)e_wuu[e],
                                    (uint32_t)ewc[k]);
-        uint32_t at;
+        uint32_t at, own_ticket = 0, own_sg = 0xFFFFFFFFu;
         if (ci[k] >= 0) {
           at = rbase + S.cbase[ci[k] * kSlabs + (int)(vid / kSlabVox)] + rank[k];
         } else {   // beyond the chunk cache (scattered clouds): a segment of its own in the spill area
@@ -1068,11 +1081,16 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
             for (int s = 0; s < kSlabs; ++s) sub[s] = (uint32_t)s > vid / kSlabVox ? 1u : 0u;
             out.seg[2 * (size_t)sg] = make_uint4((uint32_t)slot_of[k], at, 1u, gtile);
             out.seg[2 * (size_t)sg + 1] = pack_suboffsets(sub);
-            if (out.chunk_nseg) atomicAdd(&out.chunk_nseg[slot_of[k]], 1u);
+            if (out.chunk_nseg) {
+              own_ticket = atomicAdd(&out.chunk_nseg[slot_of[k]], 1u);
+              own_sg = sg;
+            }
           }
         }
         if (at < out.rec_cap) out.rec[at] = r;
+        if (own_sg != 0xFFFFFFFFu) out.seg_ticket[own_sg] = own_ticket;
       }
+      if (ticket_sg != 0xFFFFFFFFu) out.seg_ticket[ticket_sg] = ticket;
     }
 
     ++flushes;
@@ -1436,6 +1454,9 @@ __device__ __forceinline__ void walk_fast_tile(
   // nobody waits for wave 0 behind a barrier; wave 0 alone writes the segment descriptors.
   const uint32_t rbase = tile * rec_stride;
   uint32_t nruns;   // runs of the tile (every wave computes it)
+  // (wave 0, lane = chunk: the segment's ticket — AccOut::seg_ticket — is asked for here and stored in the tile's epilogue;
+  // the atomic's round trip to the L2 runs beside the records and the runs, nothing in front of them waits for it)
+  uint32_t ticket = 0, ticket_sg = 0xFFFFFFFFu;
   {
     uint32_t sub[kSlabs], c = 0, rsub[kSlabs], rc = 0;
 #pragma unroll
@@ -1467,13 +1488,16 @@ __device__ __forceinline__ void walk_fast_tile(
       if (lane == 0) out.seg_cnt[tile] = stot;
       if (c) {
         const uint32_t sg = tile * (uint32_t)kWalkChunks + sinc - 1u;
+        if (out.chunk_nseg) {
+          ticket = atomicAdd(&out.chunk_nseg[S.cslot[lane]], 1u);
+          ticket_sg = sg;
+        }
         out.seg[2 * (size_t)sg] = make_uint4((uint32_t)S.cslot[lane], rbase + inc - c, c, gtile);
         out.seg[2 * (size_t)sg + 1] = pack_suboffsets(sub);
         if (runs.rseg) {
           runs.rseg[2 * (size_t)sg] = make_uint4((tile << runs.r1_log2) + rinc - rc, rc, 0u, 0u);
           runs.rseg[2 * (size_t)sg + 1] = pack_suboffsets(rsub);
         }
-        if (out.chunk_nseg) atomicAdd(&out.chunk_nseg[S.cslot[lane]], 1u);
       }
     }
   }
@@ -1570,6 +1594,7 @@ __device__ __forceinline__ void walk_fast_tile(
     runs.run_cnt[tile] = min(S.run_total, 1u << runs.r1_log2);
     out.tile_visits[tile] = S.vis_total;
   }
+  if (ticket_sg != 0xFFFFFFFFu) out.seg_ticket[ticket_sg] = ticket;
 }
 
 template <int E, bool kGrid = false>
@@ -1601,12 +1626,13 @@ __global__ __launch_bounds__(kWalkRays, walk_fast_waves(E)) void walk_fast(
 // (segments of neighbouring tiles: a handful of chunks), counts them per chunk in an LDS table and
 // goes to the global per-chunk counters once per (workgroup, chunk): seg_pass<false> counts,
 // seg_scan scans (and lists the updated chunks, sums the per-tile visit counts), seg_pass<true> places.
+// Segments the walk has counted itself (AccOut::chunk_nseg) carry a ticket and need neither pass: seg_scan, then
+// place_segment per descriptor (seg_place, or runs_count on its way through the descriptors of a long call).
 constexpr int kSegSpan = 1024;     // descriptor slots per workgroup (16 tiles)
-constexpr int kSegSpanLong = 4096; // ... of seg_pass<true> in a long call (64 tiles: a quarter of the atomics on the chunks' counters)
 constexpr uint32_t kPartSegs = 256;   // segments of a busy chunk one work item of the apply stage takes (default)
 constexpr uint32_t kPartMin = 512;    // a chunk with more segments than this is applied in parts (default; round 6: 2048 -> 512, apply 0.18 -> 0.14 ms on the stream)
 constexpr int kSegTable = 512;
-template <bool kScatter, int kSpan = kSegSpan>
+template <bool kScatter>
 __global__ __launch_bounds__(256) void seg_pass(const uint4* __restrict__ seg, uint32_t seg_cap, uint32_t ntiles,
                                                 const uint32_t* __restrict__ seg_cnt, uint32_t* __restrict__ chunk_nseg,
                                                 const uint32_t* __restrict__ chunk_off, uint32_t* __restrict__ chunk_fill,
@@ -1620,7 +1646,7 @@ __global__ __launch_bounds__(256) void seg_pass(const uint4* __restrict__ seg, u
     hcnt[k] = 0;
   }
   __syncthreads();
-  constexpr int kPer = kSpan / 256;
+  constexpr int kSpan = kSegSpan, kPer = kSpan / 256;
   int ent[kPer];
   uint32_t rnk[kPer], slot[kPer];
 #pragma unroll
@@ -1661,6 +1687,37 @@ __global__ __launch_bounds__(256) void seg_pass(const uint4* __restrict__ seg, u
       atomicAdd(&chunk_nseg[slot[q]], 1u);
     }
   }
+}
+
+// Is descriptor slot j one the walk has written?  (seg_pass's test: the first seg_cnt[tile] slots of a tile's own region,
+// and the spill area as far as it was handed out.)
+__device__ __forceinline__ bool segment_written(uint32_t j, uint32_t seg_cap, uint32_t ntiles, const uint32_t* __restrict__ seg_cnt,
+                                                const WalkCounters* __restrict__ ctr) {
+  const uint32_t own = ntiles * (uint32_t)kWalkChunks;
+  if (j < own) return (j % kWalkChunks) < seg_cnt[j / kWalkChunks];
+  return j < min(own + ctr->seg_top, seg_cap);
+}
+// A ticketed descriptor to its place among its chunk's segments: their order there is the order the tickets were drawn in,
+// different from run to run — the apply stage adds fixed-point sums and takes maxima, in any order the same.
+// (sorted_cap, in segments: a slot of the spill area that a walk out of scratch has handed out and not written holds an
+// earlier call's ticket; such a call sets err and seg_place / runs_count leave — the bound is the second lock.)
+__device__ __forceinline__ void place_segment(const uint4* __restrict__ seg, const uint32_t* __restrict__ seg_ticket,
+                                              const uint32_t* __restrict__ chunk_off, uint4* __restrict__ sorted,
+                                              uint32_t sorted_cap, uint32_t j) {
+  const uint4 d0 = seg[2 * (size_t)j], d1 = seg[2 * (size_t)j + 1];
+  const uint32_t at = chunk_off[d0.x] + seg_ticket[j];
+  if (at >= sorted_cap) return;
+  sorted[2 * (size_t)at] = d0;
+  sorted[2 * (size_t)at + 1] = d1;
+}
+// A thread per descriptor slot; behind seg_scan.  No table, no barrier, no atomic.
+__global__ __launch_bounds__(256) void seg_place(const uint4* __restrict__ seg, const uint32_t* __restrict__ seg_ticket,
+                                                 uint32_t seg_cap, uint32_t ntiles, const uint32_t* __restrict__ seg_cnt,
+                                                 const uint32_t* __restrict__ chunk_off, uint4* __restrict__ sorted,
+                                                 uint32_t sorted_cap, const WalkCounters* __restrict__ ctr) {
+  if (ctr->err != 0u) return;   // (the call is repeated with more room, the apply stage leaves at once)
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (segment_written(j, seg_cap, ntiles, seg_cnt, ctr)) place_segment(seg, seg_ticket, chunk_off, sorted, sorted_cap, j);
 }
 
 __global__ __launch_bounds__(1024) void seg_scan(const uint32_t* __restrict__ chunk_nseg, uint32_t* __restrict__ chunk_off,
@@ -2429,7 +2486,8 @@ constexpr uint32_t kWireTileBits = 20;   // tile index of the call in the upper 
 // (chunk, slab) and says beside every segment descriptor where they are (RunOut::rseg).  A ROW = (updated chunk, slab); the
 // descriptor slots are cut into blocks of kSegSpan (16 tiles):
 //   runs_count     a workgroup per block: the runs of every row in the block -> matrix [row][block]; per descriptor, the runs
-//                  of its rows in the block's earlier tiles (rpre)
+//                  of its rows in the block's earlier tiles (rpre).  First of all, and whatever becomes of the chain, it
+//                  places the segment descriptors it passes in chunk order (place_segment): the segment sort of a long call
 //   runs_rowscan   a wave per row: exclusive scan along the blocks; the row's total gives it a region of the output and its
 //                  parts of kCollectPart runs
 //   runs_scatter   a workgroup per block: the slots of its runs to region + matrix + rpre — the row's runs in TILE order,
@@ -2454,16 +2512,34 @@ __device__ __forceinline__ void slab_runs(const uint4& r0, const uint4& r1, int 
   *cnt = hi - lo;
 }
 
+// What runs_count needs to place the segments it passes (place_segment); seg_cap bounds the spill area's descriptors.
+struct SegPlace {
+  const uint32_t *ticket, *chunk_off;
+  uint4* sorted;
+  uint32_t sorted_cap, seg_cap;
+};
 __global__ __launch_bounds__(kSegSpan) void runs_count(const uint4* __restrict__ seg, const uint4* __restrict__ rseg, uint32_t ntiles,
                                                        const uint32_t* __restrict__ seg_cnt, const uint32_t* __restrict__ active_idx,
                                                        uint32_t rows_cap, uint32_t nblocks, uint32_t* __restrict__ M,
                                                        uint4* __restrict__ rpre, WalkCounters* __restrict__ ctr,
-                                                       const uint32_t* __restrict__ left_to_walk_tiles) {
+                                                       const uint32_t* __restrict__ left_to_walk_tiles, SegPlace place) {
   // (a thread per descriptor slot: one chain of dependent loads per thread, all of the block's in flight together)
   __shared__ uint32_t hkey[kRunTable];
   __shared__ alignas(16) uint16_t tbl[kRunTable][kSpanTiles][kSlabs];
   static_assert(kSpanTiles == 16 && kSegSpan == 1024, "16 tiles per block");
   const int tid = threadIdx.x;
+  const uint32_t j = blockIdx.x * (uint32_t)kSegSpan + (uint32_t)tid;
+  const uint32_t tile = j / kWalkChunks;
+  const bool written = tile < ntiles && (j % kWalkChunks) < seg_cnt[tile];
+  // ---- the segment sort's placement, for whatever chain folds the call's colours: this kernel is at every descriptor of
+  // the tiles' own regions anyway, and seg_scan has run in front of it.  The spill area (empty, or this is not the
+  // collected chain's call) is shared out among all threads.
+  if (ctr->err == 0u) {   // (uniform)
+    if (written) place_segment(seg, place.ticket, place.chunk_off, place.sorted, place.sorted_cap, j);
+    const uint32_t own = ntiles * (uint32_t)kWalkChunks, n = min(own + ctr->seg_top, place.seg_cap);
+    for (uint32_t k = own + j; k < n; k += gridDim.x * (uint32_t)kSegSpan)
+      place_segment(seg, place.ticket, place.chunk_off, place.sorted, place.sorted_cap, k);
+  }
   // (a tile left to walk_tiles: its runs are not grouped by chunk, its segments may lie in the spill area — not this chain's call)
   // (... nor a call that has to be repeated with more room: err); the run descriptors of such tiles are not valid
   if (*left_to_walk_tiles != 0u || ctr->seg_top != 0u || ctr->err != 0u) {   // (uniform)
@@ -2474,11 +2550,9 @@ __global__ __launch_bounds__(kSegSpan) void runs_count(const uint4* __restrict__
   if (tid < kRunTable) hkey[tid] = 0xFFFFFFFFu;
   for (int k = tid; k < kRunTable * kSpanTiles * kSlabs / 2; k += kSegSpan) reinterpret_cast<uint32_t*>(&tbl[0][0][0])[k] = 0u;
   __syncthreads();
-  const uint32_t j = blockIdx.x * (uint32_t)kSegSpan + (uint32_t)tid;
-  const uint32_t tile = j / kWalkChunks;
   const int tl = tid / kWalkChunks;
   int ent = -1;
-  if (tile < ntiles && (j % kWalkChunks) < seg_cnt[tile]) {
+  if (written) {
     const uint4 r0 = rseg[2 * (size_t)j], r1 = rseg[2 * (size_t)j + 1];
     const uint32_t slot = seg[2 * (size_t)j].x;
     if (r0.y != 0u) {   // (runs in this chunk)
