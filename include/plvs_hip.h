@@ -1454,6 +1454,103 @@ int plvs_hip_tsdf_chisel_integrate_scans_dev(plvs_tsdf_chisel* h, const float* d
                                              int channels, const plvs_scan_camera* camera, const float* d_Twc,
                                              int nscans, int use_carving, float carving_dist, void* stream);
 
+/* ------------------------------------------------------ Frame glue, local map
+ * Frame::isInFrustum(MapPointPtr&, viewingCosLimit) and Frame::isInFrustum(MapLinePtr&, viewingCosLimit)
+ * (src/Frame.cc:955-1017, :1033-1142) over the local map — the loops of Tracking::SearchLocalPoints / SearchLocalLines
+ * (src/Tracking.cc:4430-4579) — in one launch, and the two searches behind them in one call.  Single-camera frames
+ * with a pinhole camera only (Nleft == NlinesLeft == -1): any other request (n_cameras != 1, camera_model !=
+ * PLVS_CAMERA_PINHOLE — the isInFrustumChecks branches of a fisheye pair) is refused with PLVS_ERR_INVALID_ARG before
+ * anything is launched.  All arrays are host memory; the float results equal the reference's bit for bit. */
+#define PLVS_CAMERA_PINHOLE 0
+typedef struct plvs_track_camera {
+  int32_t n_cameras;            /* 1 (Nleft == -1, no mpCamera2)                                            */
+  int32_t camera_model;         /* PLVS_CAMERA_PINHOLE                                                      */
+  const float* K4;              /* fx, fy, cx, cy (mpCamera's parameters)                                   */
+  float mbf;
+  const float* bounds4;         /* mnMinX, mnMaxX, mnMinY, mnMaxY                                           */
+  const float* Rcw;             /* mRcw after UpdatePoseMatrices: 9 floats as Eigen::Matrix3f holds them    */
+  const float* tcw;             /* mtcw, 3                                                                  */
+  const float* Ow;              /* mOw, 3                                                                   */
+  float viewing_cos_limit;      /* 0.5 in Tracking                                                          */
+  float log_scale_factor;       /* mfLogScaleFactor                                                         */
+  int32_t n_levels;             /* mnScaleLevels (>= 1 when there are points)                               */
+  float line_log_scale_factor;  /* mfLineLogScaleFactor                                                     */
+  int32_t n_line_levels;        /* mnLineScaleLevels (>= 1 when there are lines)                            */
+} plvs_track_camera;
+/* Map points.  skip[k] != 0: pMP->mnLastFrameSeen == frame id || pMP->isBad() (the two `continue`s of :4459-4462).
+ * Outputs, m entries each — what the reference leaves on the map point: in_view = mbTrackInView, proj_x / proj_y /
+ * proj_xr = mTrackProjX / Y / XR, track_depth = mTrackDepth, level = mnTrackScaleLevel, view_cos = mTrackViewCos.
+ * A point rejected after the bounds test keeps its proj_x / proj_y, one rejected before (or skipped) has -1; the
+ * fields the reference leaves stale on a rejected point (proj_xr, track_depth, level, view_cos) are 0.  A point at
+ * the camera centre (dist == 0: the reference's level is undefined) is reported as not in view. */
+typedef struct plvs_track_points {
+  int32_t m;
+  const uint8_t* skip;
+  const float* pos;             /* GetWorldPos(), 3 m                                                       */
+  const float* normal;          /* GetNormal(), 3 m                                                         */
+  const float* min_dist;        /* mfMinDistance / mfMaxDistance, raw                                       */
+  const float* max_dist;
+  const uint8_t* desc;          /* GetDescriptor(), m x 32 (the search only)                                */
+  const uint8_t* has_obs;       /* Observations() > 0; NULL = all (the search only)                         */
+  uint8_t* in_view;
+  float* proj_x;
+  float* proj_y;
+  float* proj_xr;
+  float* track_depth;
+  int32_t* level;
+  float* view_cos;
+} plvs_track_points;
+/* Map lines.  The tests run on the middle point 0.5 * (start + end), in the band [0.8f, 1.2f] * mfMaxDistance
+ * (MapLine::GetMinDistanceInvariance, src/MapLine.cc:710); the end points are projected untested.  proj[6 k ..] =
+ * mTrackProjStartX, StartY, EndX, EndY, mTrackStartDepth, mTrackEndDepth — the layout
+ * plvs_hip_lines_search_by_projection reads —, proj_xr[2 k ..] = mTrackProjStartXR, EndXR.  Not in view: the four
+ * projections and the two XR are -1, the rest 0. */
+typedef struct plvs_track_lines {
+  int32_t m;
+  const uint8_t* skip;
+  const float* start;           /* GetWorldEndPoints(), 3 m each                                            */
+  const float* end;
+  const float* normal;          /* GetNormal(), 3 m                                                         */
+  const float* max_dist;        /* mfMaxDistance, raw                                                       */
+  const uint8_t* desc;          /* GetDescriptor(), m x 32 (the search only)                                */
+  const uint8_t* has_obs;       /* Observations() > 0; NULL = all (the search only)                         */
+  uint8_t* in_view;
+  float* proj;
+  float* proj_xr;
+  int32_t* level;
+  float* view_cos;
+} plvs_track_lines;
+/* Both loops in one launch.  points / lines may be NULL or hold m == 0.  *n_in_view_points / *n_in_view_lines = the
+ * reference's nToMatch.  The predicted level (PredictScale: ceil(log(ratio) / logScaleFactor) on the host's libm) is
+ * decided on the device except where the quotient lies within a derived eps of an integer; those elements — about
+ * 3 in 10^6 of the ratios the distance band admits — are evaluated by the reference's own expression on the calling process's libm after the wait.
+ * stats (4 entries, may be NULL): map points resolved that way, map lines resolved that way, levels the host's
+ * expression changed, window launches (the search; 1 on the common path).  stream: a hipStream_t, NULL = the calling
+ * thread's staging stream; the call waits for it before it returns. */
+int plvs_hip_frame_is_in_frustum(const plvs_track_camera* cam, const plvs_track_points* points,
+                                 const plvs_track_lines* lines, int* n_in_view_points, int* n_in_view_lines,
+                                 int32_t* stats, void* stream);
+/* The frustum loops, then ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) and
+ * LineMatcher::SearchByProjection(F, vpMapLines, bLargerSearch) on their results, with one device wait on the common
+ * path (more candidates than nq * 32 + 4096, or a level the host decided otherwise: one more launch and wait for the
+ * windows concerned; more than 2^18 map line x key line pairs, i.e. beyond 512 x 512 lines: the line distances go
+ * through plvs_hip_hamming_pairs, one more launch and wait; the repeated launches run on the calling thread's staging
+ * stream, after the wait for `stream`).  F / LF, occupied_*, assigned_*, nmatches_* as in plvs_hip_orb_search_by_projection and
+ * plvs_hip_lines_search_by_projection; F->scale_factors holds n_levels entries.  A kind whose nToMatch is 0 is not
+ * searched (:4475, :4569).  No lines (mbLineTrackerOn off): lines == NULL or m == 0, LF == NULL. */
+int plvs_hip_frame_search_local_map(const plvs_track_camera* cam, const plvs_frame_view* F,
+                                    const plvs_line_frame_view* LF, const plvs_track_points* points,
+                                    const plvs_track_lines* lines, float th, int far_points, float th_far,
+                                    float nn_ratio, int larger_search, const uint8_t* occupied_points,
+                                    const uint8_t* occupied_lines, int32_t* assigned_points, int* nmatches_points,
+                                    int32_t* assigned_lines, int* nmatches_lines, int* n_in_view_points,
+                                    int* n_in_view_lines, int32_t* stats, void* stream);
+/* ---- TESTING ONLY: not part of the stable ABI (no mirror exposes it; it may change or go without a version bump).
+ * The map point (calling thread) whose device-side level, if marked ambiguous, is turned to the other side of the
+ * integer, so that the host's correction and the repeated window launch can be exercised where this libm and the
+ * device agree everywhere.  -1 = off (the default). */
+void plvs_hip_frame_track_test_flip(int point_index);
+
 #ifdef __cplusplus
 }
 #endif

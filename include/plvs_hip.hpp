@@ -15,6 +15,7 @@
 //   PLVS2hip::ComputeStereoMatches      src/Frame.cc:1780
 //   PLVS2hip::UndistortKeyPoints, ComputeImageBounds, UndistortKeyLines, AssignFeaturesToGrid   src/Frame.cc:1507-1778, :716
 //   PLVS2hip::ComputeStereoFromRGBD, ComputeStereoLinesFromRGBD, ComputeSceneMedianDepth, rgbd_frame   src/Frame.cc:2251, :2434, :2730, :401
+//   PLVS2hip::IsInFrustum, SearchLocalMap   src/Frame.cc:955, :1033 and src/Tracking.cc:4430-4579 (the local-map link of TrackLocalMap)
 //   PLVS2hip::StereoSGM                 Thirdparty/libsgm/include/libsgm.h:57 (as src/PointCloudKeyFrame.cc:435 uses it)
 //   PLVS2hip::PointCloudGenerator       src/PointCloudMapping.cc:796, :929
 //   PLVS2hip::PointCloudMapChisel       include/PointCloudMapChisel.h:61, src/PointCloudMapChisel.cc:76-246
@@ -544,6 +545,56 @@ inline void StereoFrame(ORBextractor& left, ORBextractor& right, LineExtractor* 
   F.mvKeyLines.resize(nl); F.mvKeyLinesUn.resize(nl); F.mLineDescriptors.resize(32 * nl);
   F.mvKeyLinesRight.resize(nlr); F.mvKeyLinesRightUn.resize(nl > 0 ? nlr : 0); F.mLineDescriptorsRight.resize(32 * nlr);
   F.mvuRightLineStart.resize(nl); F.mvDepthLineStart.resize(nl); F.mvuRightLineEnd.resize(nl); F.mvDepthLineEnd.resize(nl);
+}
+
+// ---- the local map (src/Tracking.cc:4430-4579): Frame::isInFrustum over the local map points and lines in one launch, and the
+// two searches of TrackLocalMap behind it in one call.  The vectors are what the reference leaves on the map elements
+// (mbTrackInView, mTrackProj*, mTrackDepth, mnTrackScaleLevel, mTrackViewCos); single-camera pinhole frames only.
+struct LocalMapFields {
+  std::vector<uint8_t> pointInView, lineInView;
+  std::vector<float> trackProjX, trackProjY, trackProjXR, trackDepth, trackViewCos;
+  std::vector<int32_t> trackScaleLevel, lineScaleLevel;
+  std::vector<float> lineProj, lineProjXR, lineViewCos;   // 6 / 2 / 1 per line
+  int nToMatchPoints = 0, nToMatchLines = 0;
+  int32_t stats[4] = {0, 0, 0, 0};                         // see plvs_hip_frame_is_in_frustum
+  std::vector<int32_t> assignedPoints, assignedLines;      // SearchLocalMap only
+  int nMatchesPoints = 0, nMatchesLines = 0;
+};
+namespace detail {
+inline void bind(LocalMapFields& o, plvs_track_points* P, plvs_track_lines* L) {
+  if (P) {
+    const size_t m = (size_t)P->m;
+    o.pointInView.assign(m, 0); o.trackProjX.assign(m, -1.0f); o.trackProjY.assign(m, -1.0f); o.trackProjXR.assign(m, 0.0f);
+    o.trackDepth.assign(m, 0.0f); o.trackViewCos.assign(m, 0.0f); o.trackScaleLevel.assign(m, 0);
+    P->in_view = o.pointInView.data(); P->proj_x = o.trackProjX.data(); P->proj_y = o.trackProjY.data(); P->proj_xr = o.trackProjXR.data();
+    P->track_depth = o.trackDepth.data(); P->level = o.trackScaleLevel.data(); P->view_cos = o.trackViewCos.data();
+  }
+  if (L) {
+    const size_t m = (size_t)L->m;
+    o.lineInView.assign(m, 0); o.lineProj.assign(6 * m, 0.0f); o.lineProjXR.assign(2 * m, -1.0f); o.lineViewCos.assign(m, 0.0f);
+    o.lineScaleLevel.assign(m, 0);
+    L->in_view = o.lineInView.data(); L->proj = o.lineProj.data(); L->proj_xr = o.lineProjXR.data(); L->level = o.lineScaleLevel.data();
+    L->view_cos = o.lineViewCos.data();
+  }
+}
+}  // namespace detail
+// points / lines: the input members filled by the caller (m, skip, pos / start / end, normal, the distances, desc, has_obs);
+// the output members are pointed at `out`.  Either may be nullptr.
+inline void IsInFrustum(const plvs_track_camera& cam, plvs_track_points* points, plvs_track_lines* lines, LocalMapFields& out,
+                        void* stream = nullptr) {
+  detail::bind(out, points, lines);
+  check(plvs_hip_frame_is_in_frustum(&cam, points, lines, &out.nToMatchPoints, &out.nToMatchLines, out.stats, stream));
+}
+// Tracking::SearchLocalPoints + SearchLocalLines: LF / lines nullptr without the line tracker.
+inline void SearchLocalMap(const plvs_track_camera& cam, const plvs_frame_view& F, const plvs_line_frame_view* LF, plvs_track_points& points,
+                           plvs_track_lines* lines, float th, bool bFarPoints, float thFarPoints, float nnRatio, bool bLargerSearch,
+                           const uint8_t* occupiedPoints, const uint8_t* occupiedLines, LocalMapFields& out, void* stream = nullptr) {
+  detail::bind(out, &points, lines);
+  out.assignedPoints.assign((size_t)(F.n > 0 ? F.n : 0), -1);
+  out.assignedLines.assign((size_t)(LF && LF->n > 0 ? LF->n : 0), -1);
+  check(plvs_hip_frame_search_local_map(&cam, &F, LF, &points, lines, th, bFarPoints ? 1 : 0, thFarPoints, nnRatio, bLargerSearch ? 1 : 0,
+                                        occupiedPoints, occupiedLines, out.assignedPoints.data(), &out.nMatchesPoints, out.assignedLines.data(),
+                                        &out.nMatchesLines, &out.nToMatchPoints, &out.nToMatchLines, out.stats, stream));
 }
 
 // ------------------------------------------------------------------------------------ dense stereo

@@ -11,244 +11,9 @@
 #include <vector>
 
 #include "common.hpp"
+#include "orb_window.hpp"
 
-namespace {
-
-constexpr int kGridCols = 64;   // FRAME_GRID_COLS, include/Frame.h:68
-constexpr int kGridRows = 48;   // FRAME_GRID_ROWS, include/Frame.h:67
-constexpr int kThHigh = 100;    // ORBmatcher::TH_HIGH, src/ORBmatcher.cc:57
-constexpr int kThLow = 50;      // ORBmatcher::TH_LOW, :58
-constexpr int kHistoLength = 12; // ORBmatcher::HISTO_LENGTH, :61
-
-// dist[p] = ORBmatcher::DescriptorDistance(query[pair_q[p]], train[pair_t[p]]) (src/ORBmatcher.cc:2198)
-__global__ __launch_bounds__(256) void hamming_pairs_kernel(const uint4* __restrict__ query,
-                                                            const uint4* __restrict__ train,
-                                                            const int32_t* __restrict__ pair_q,
-                                                            const int32_t* __restrict__ pair_t, int npairs,
-                                                            int32_t* __restrict__ dist) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npairs) return;
-  const uint4 a0 = query[2 * pair_q[p]], a1 = query[2 * pair_q[p] + 1];
-  const uint4 b0 = train[2 * pair_t[p]], b1 = train[2 * pair_t[p] + 1];
-  dist[p] = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// Frame::AssignFeaturesToGrid (src/Frame.cc:717-752): cell lists in keypoint order
-struct FrameGrid {
-  // mGrid as one array in the reference's enumeration order — column ix, row iy, insertion order inside the cell —
-  // with the fields the window test reads next to the index: a window is one contiguous range per column.
-  struct Member { float x, y; int octave, idx; };
-  std::vector<int> start;
-  std::vector<Member> members;
-  explicit FrameGrid(const plvs_frame_view* F) : start(kGridCols * kGridRows + 1, 0), members(F->n) {
-    std::vector<int> cell(F->n);
-    for (int i = 0; i < F->n; ++i) {
-      const int px = (int)std::round((F->x[i] - F->min_x) * F->grid_w_inv);   // PosInGrid, :1305-1316
-      const int py = (int)std::round((F->y[i] - F->min_y) * F->grid_h_inv);
-      cell[i] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
-      if (cell[i] >= 0) ++start[cell[i] + 1];
-    }
-    for (int c = 0; c < kGridCols * kGridRows; ++c) start[c + 1] += start[c];
-    std::vector<int> fill(start.begin(), start.end() - 1);
-    for (int i = 0; i < F->n; ++i)
-      if (cell[i] >= 0) members[fill[cell[i]]++] = Member{F->x[i], F->y[i], F->octave[i], i};
-  }
-  // Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel) (src/Frame.cc:1231-1303), appended to `out`
-  // in the reference's order (defaults: minLevel = -1, maxLevel = kMaxInt, include/Frame.h:173)
-  template <typename Fn>
-  void for_each_in_area(const plvs_frame_view* F, float x, float y, float r, int min_level, int max_level, Fn&& fn) const {
-    int c0 = (int)std::floor((x - F->min_x - r) * F->grid_w_inv);
-    if (c0 < 0) c0 = 0;
-    if (c0 >= kGridCols) return;
-    int c1 = (int)std::ceil((x - F->min_x + r) * F->grid_w_inv);
-    if (c1 > kGridCols - 1) c1 = kGridCols - 1;
-    if (c1 < 0) return;
-    int r0 = (int)std::floor((y - F->min_y - r) * F->grid_h_inv);
-    if (r0 < 0) r0 = 0;
-    if (r0 >= kGridRows) return;
-    int r1 = (int)std::ceil((y - F->min_y + r) * F->grid_h_inv);
-    if (r1 > kGridRows - 1) r1 = kGridRows - 1;
-    if (r1 < 0) return;
-    const bool check_levels = (min_level > 0) || (max_level >= 0);
-    for (int ix = c0; ix <= c1; ++ix) {
-      const Member* m = members.data() + start[ix * kGridRows + r0];
-      const Member* const end = members.data() + start[ix * kGridRows + r1 + 1];   // rows r0 .. r1 of the column
-      for (; m < end; ++m) {
-        if (check_levels && (m->octave < min_level || m->octave > max_level)) continue;
-        const float dx = m->x - x, dy = m->y - y;
-        if (std::fabs(dx) < r && std::fabs(dy) < r) fn(m->idx);
-      }
-    }
-  }
-};
-
-// Frame::GetFeaturesInArea + the stereo gate + the Hamming distance of every candidate, on the device: a wave per
-// query walks the query's grid window in the reference's order — column after column, each column's rows one
-// contiguous range of the CSR members —, and the accepted candidates leave as (index, distance) in that order (ballot
-// compaction keeps it).  Two passes over the window: count, reserve the query's output range, emit.
-struct WinQuery {
-  float u, v, r, ur;            // window centre, radius, predicted right coordinate
-  int min_level, max_level;     // inclusive; tested only when check_levels
-  int src;                      // descriptor row of the query
-  int check_levels;
-};
-struct WinFrame {
-  const FrameGrid::Member* members;
-  const int* start;
-  const float* u_right;
-  const uint4* desc;            // two uint4 per keypoint
-  float min_x, min_y, grid_w_inv, grid_h_inv;
-};
-__global__ __launch_bounds__(256) void orb_window_candidates(const WinQuery* __restrict__ queries, int nq, WinFrame F,
-                                                             const uint4* __restrict__ qdesc, uint32_t* __restrict__ cursor,
-                                                             int32_t* __restrict__ q_first, int32_t* __restrict__ q_count,
-                                                             int2* __restrict__ out, uint32_t out_cap) {
-  const int lane = threadIdx.x & 63;
-  const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (qi >= nq) return;
-  const WinQuery q = queries[qi];
-  int c0 = (int)floorf((q.u - F.min_x - q.r) * F.grid_w_inv);
-  int c1 = (int)ceilf((q.u - F.min_x + q.r) * F.grid_w_inv);
-  int r0 = (int)floorf((q.v - F.min_y - q.r) * F.grid_h_inv);
-  int r1 = (int)ceilf((q.v - F.min_y + q.r) * F.grid_h_inv);
-  bool empty = c0 >= kGridCols || c1 < 0 || r0 >= kGridRows || r1 < 0;
-  c0 = max(c0, 0); c1 = min(c1, kGridCols - 1); r0 = max(r0, 0); r1 = min(r1, kGridRows - 1);
-  auto accept = [&](const FrameGrid::Member& m) {
-    if (q.check_levels && (m.octave < q.min_level || m.octave > q.max_level)) return false;
-    const float dx = m.x - q.u, dy = m.y - q.v;
-    if (!(fabsf(dx) < q.r && fabsf(dy) < q.r)) return false;
-    const float ur = F.u_right[m.idx];
-    if (ur > 0) {
-      const float er = fabsf(q.ur - ur);
-      if (er > q.r) return false;
-    }
-    return true;
-  };
-  uint32_t total = 0;
-  if (!empty)
-    for (int ix = c0; ix <= c1; ++ix) {
-      const int s = F.start[ix * kGridRows + r0], e = F.start[ix * kGridRows + r1 + 1];
-      for (int b = s; b < e; b += 64) {
-        const bool ok = b + lane < e && accept(F.members[b + lane]);
-        total += (uint32_t)__popcll(__ballot(ok));
-      }
-    }
-  uint32_t first = 0;
-  if (lane == 0) {
-    first = total ? atomicAdd(cursor, total) : 0u;
-    q_first[qi] = (int32_t)first;
-    q_count[qi] = (int32_t)total;
-  }
-  first = (uint32_t)__shfl((int)first, 0);
-  if (total == 0 || first + total > out_cap) return;   // (the host sees cursor > out_cap and repeats with more room)
-  const uint4 qa = qdesc[2 * (size_t)q.src], qb = qdesc[2 * (size_t)q.src + 1];
-  uint32_t at = first;
-  for (int ix = c0; ix <= c1; ++ix) {
-    const int s = F.start[ix * kGridRows + r0], e = F.start[ix * kGridRows + r1 + 1];
-    for (int b = s; b < e; b += 64) {
-      FrameGrid::Member m{};
-      bool ok = false;
-      if (b + lane < e) {
-        m = F.members[b + lane];
-        ok = accept(m);
-      }
-      const unsigned long long mask = __ballot(ok);
-      if (ok) {
-        const uint4 ta = F.desc[2 * (size_t)m.idx], tb = F.desc[2 * (size_t)m.idx + 1];
-        const int d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
-                      __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
-        out[at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = make_int2(m.idx, d);
-      }
-      at += (uint32_t)__popcll(mask);
-    }
-  }
-}
-
-// The windows of `wq` on frame F (orb_window_candidates): per query k the accepted candidates pair_t / dist
-// [q_at[k], q_at[k] + q_n[k]) in the reference's enumeration order.  qdesc: the queries' descriptor rows (n_qdesc x 32).
-int window_candidates(const plvs_frame_view* F, const FrameGrid& grid, const std::vector<WinQuery>& wq, const uint8_t* qdesc,
-                      int n_qdesc, std::vector<int32_t>& q_at, std::vector<int32_t>& q_n, std::vector<int32_t>& pair_t,
-                      std::vector<int32_t>& dist) {
-  const int nq = (int)wq.size();
-  q_at.assign((size_t)nq, 0);
-  q_n.assign((size_t)nq, 0);
-  pair_t.clear();
-  dist.clear();
-  if (nq == 0) return PLVS_OK;
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t nm = grid.members.size();
-  plvs::HostStage& st = plvs::thread_stage();
-  size_t out_cap = (size_t)nq * 32 + 4096;
-  for (int attempt = 0;; ++attempt) {
-    const size_t o_wq = 0, o_mem = o_wq + up16(sizeof(WinQuery) * (size_t)nq), o_start = o_mem + up16(sizeof(FrameGrid::Member) * nm),
-                 o_ur = o_start + up16(sizeof(int) * grid.start.size()), o_fd = o_ur + up16(sizeof(float) * (size_t)F->n),
-                 o_qd = o_fd + up16((size_t)F->n * 32), o_cur = o_qd + up16((size_t)n_qdesc * 32), o_first = o_cur + 16,
-                 o_count = o_first + up16(sizeof(int32_t) * (size_t)nq), o_out = o_count + up16(sizeof(int32_t) * (size_t)nq),
-                 total = o_out + up16(sizeof(int2) * out_cap);
-    PLVS_HIP_TRY(st.reserve(total));
-    memcpy(st.pinned + o_wq, wq.data(), sizeof(WinQuery) * (size_t)nq);
-    memcpy(st.pinned + o_mem, grid.members.data(), sizeof(FrameGrid::Member) * nm);
-    memcpy(st.pinned + o_start, grid.start.data(), sizeof(int) * grid.start.size());
-    memcpy(st.pinned + o_ur, F->u_right, sizeof(float) * (size_t)F->n);
-    memcpy(st.pinned + o_fd, F->desc, (size_t)F->n * 32);
-    memcpy(st.pinned + o_qd, qdesc, (size_t)n_qdesc * 32);
-    memset(st.pinned + o_cur, 0, 16);
-    PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, o_first, hipMemcpyHostToDevice, st.stream));
-    const WinFrame wf{reinterpret_cast<const FrameGrid::Member*>(st.dev + o_mem), reinterpret_cast<const int*>(st.dev + o_start),
-                      reinterpret_cast<const float*>(st.dev + o_ur), reinterpret_cast<const uint4*>(st.dev + o_fd),
-                      F->min_x, F->min_y, F->grid_w_inv, F->grid_h_inv};
-    hipLaunchKernelGGL(orb_window_candidates, dim3(plvs::ceil_div((size_t)nq, 4)), dim3(256), 0, st.stream,
-                       reinterpret_cast<const WinQuery*>(st.dev + o_wq), nq, wf, reinterpret_cast<const uint4*>(st.dev + o_qd),
-                       reinterpret_cast<uint32_t*>(st.dev + o_cur), reinterpret_cast<int32_t*>(st.pinned + o_first),
-                       reinterpret_cast<int32_t*>(st.pinned + o_count), reinterpret_cast<int2*>(st.pinned + o_out), (uint32_t)out_cap);
-    // (first / count / records go straight into the pinned block — posted writes over the link, a few tens of KB —:
-    // one copy in, one launch, one wait; the copies back and the second wait they needed cost more than the search's
-    // arithmetic.  The cursor stays in HBM: it is the target of the waves' atomics.)
-    PLVS_KERNEL_CHECK();
-    PLVS_HIP_TRY(hipStreamSynchronize(st.stream));
-    const int32_t* qf = reinterpret_cast<const int32_t*>(st.pinned + o_first);
-    const int32_t* qc = reinterpret_cast<const int32_t*>(st.pinned + o_count);
-    size_t found = 0;
-    for (int k = 0; k < nq; ++k) found += (size_t)qc[k];
-    if (found > out_cap) {   // more candidates than room: once more with what is needed
-      PLVS_REQUIRE(attempt == 0, "candidate count changed between two identical launches");
-      out_cap = found + 64;
-      continue;
-    }
-    const int2* rec = reinterpret_cast<const int2*>(st.pinned + o_out);
-    pair_t.resize(found);
-    dist.resize(found);
-    // (the ranges were reserved in the order the waves arrived: copied here query after query)
-    uint32_t at = 0;
-    for (int k = 0; k < nq; ++k) {
-      q_at[k] = (int32_t)at;
-      q_n[k] = qc[k];
-      for (int c = 0; c < qc[k]; ++c) {
-        pair_t[at + c] = rec[qf[k] + c].x;
-        dist[at + c] = rec[qf[k] + c].y;
-      }
-      at += (uint32_t)qc[k];
-    }
-    return PLVS_OK;
-  }
-}
-
-// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:2123-2170) on bin counts
-void three_maxima(const int* count, int L, int& ind1, int& ind2, int& ind3) {
-  int max1 = 0, max2 = 0, max3 = 0;
-  ind1 = ind2 = ind3 = -1;
-  for (int i = 0; i < L; ++i) {
-    const int s = count[i];
-    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-    else if (s > max3) { max3 = s; ind3 = i; }
-  }
-  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
-
-}  // namespace
+using namespace plvs::orbwin;
 
 constexpr size_t kDirectReadBytes = 96 * 1024;   // inputs up to this size are read in place from pinned host memory
 
@@ -354,57 +119,24 @@ int plvs_hip_orb_search_by_projection(const plvs_frame_view* F, const plvs_mappo
   const FrameGrid grid(F);
   // ---- candidate windows (GetFeaturesInArea) of every map point the reference would process,
   // in the reference's order; everything but the "already claimed" test is decided here
-  struct Query { int k; float r_scaled; int first, count; };
   std::vector<WinQuery> wq;
   wq.reserve((size_t)M->m);
-  const bool factor = th != 1.0f;
+  const int factor = th != 1.0f ? 1 : 0;
   for (int k = 0; k < M->m; ++k) {
     if (!M->track_in_view[k]) continue;
     if (far_points && M->track_depth[k] > th_far) continue;
     if (M->bad[k]) continue;
     const int level = M->level[k];
     PLVS_REQUIRE(level >= 0, "negative predicted level");
-    float r = ((double)M->view_cos[k] > 0.998) ? 2.5f : 4.0f;   // RadiusByViewingCos, :246-252
-    if (factor) r *= th;
-    const float rr = r * F->scale_factors[level];
-    // GetFeaturesInArea(x, y, rr, level - 1, level); a keypoint with a stereo coordinate must agree with the
-    // point's predicted one within rr (RGB-D / stereo frames)
-    wq.push_back(WinQuery{M->proj_x[k], M->proj_y[k], rr, M->proj_xr[k], level - 1, level, k, (level - 1 > 0 || level >= 0) ? 1 : 0});
+    // a keypoint with a stereo coordinate must agree with the point's predicted one within the radius (RGB-D / stereo frames)
+    wq.push_back(map_point_query(M->proj_x[k], M->proj_y[k], M->proj_xr[k], M->view_cos[k], level, th, factor, F->scale_factors[level], k));
   }
-  std::vector<Query> queries;
-  std::vector<int32_t> pair_t, dist, q_at, q_n;
+  std::vector<int32_t> pair_t, dist, q_at, q_n, src(wq.size());
   int rc = window_candidates(F, grid, wq, M->desc, M->m, q_at, q_n, pair_t, dist);
   if (rc != PLVS_OK) return rc;
-  for (size_t k = 0; k < wq.size(); ++k)
-    if (q_n[k]) queries.push_back(Query{wq[k].src, wq[k].r, q_at[k], q_n[k]});
+  for (size_t k = 0; k < wq.size(); ++k) src[k] = wq[k].src;
   // ---- greedy assignment in map-point order (:106-163)
-  std::vector<uint8_t> blocked(F->n);
-  for (int i = 0; i < F->n; ++i) blocked[i] = occupied ? occupied[i] : 0;
-  int n = 0;
-  for (const Query& q : queries) {
-    int best = 256, best2 = 256, best_level = -1, best_level2 = -1, best_idx = -1;
-    for (int p = q.first; p < q.first + q.count; ++p) {
-      const int idx = pair_t[p];
-      if (blocked[idx]) continue;   // F.mvpMapPoints[idx] && Observations() > 0
-      const int d = dist[p];
-      if (d < best) {
-        best2 = best; best = d;
-        best_level2 = best_level; best_level = F->octave[idx];
-        best_idx = idx;
-      } else if (d < best2) {
-        best_level2 = F->octave[idx];
-        best2 = d;
-      }
-    }
-    if (best <= kThHigh) {
-      if (best_level == best_level2 && (float)best > nn_ratio * (float)best2) continue;
-      if (best_level != best_level2 || (float)best <= nn_ratio * (float)best2) {
-        assigned[best_idx] = q.k;
-        blocked[best_idx] = M->has_obs ? M->has_obs[q.k] : 1;
-        ++n;
-      }
-    }
-  }
+  const int n = greedy_points(F, src.data(), wq.size(), q_at, q_n, pair_t, dist, nn_ratio, occupied, M->has_obs, assigned);
   *nmatches = n;
   return PLVS_OK;
 }

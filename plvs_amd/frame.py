@@ -408,3 +408,115 @@ def frame_stereo(orb_left: ORBextractor, orb_right: ORBextractor, lines_left, li
                 keylines_right_un=take("keylines_right_un", nlru), line_descriptors_right=take("line_desc_right", nlr),
                 cell_start=a["cell_start"].copy(), cell_items=a["cell_items"][:f.n_items].copy(),
                 n_stereo_points=f.n_stereo_points, n_stereo_lines=f.n_stereo_lines)
+
+
+# ---------------------------------------------------------------------------------------------- the local map (TrackLocalMap)
+# Frame::isInFrustum over the local map points and lines (src/Frame.cc:955-1142, the loops of Tracking::SearchLocalPoints /
+# SearchLocalLines) in one launch, and the two searches behind them in one call.
+class TrackCameraC(ctypes.Structure):       # plvs_track_camera
+    _fields_ = [("n_cameras", ctypes.c_int32), ("camera_model", ctypes.c_int32), ("K4", _vp), ("mbf", ctypes.c_float), ("bounds4", _vp),
+                ("Rcw", _vp), ("tcw", _vp), ("Ow", _vp), ("viewing_cos_limit", ctypes.c_float), ("log_scale_factor", ctypes.c_float),
+                ("n_levels", ctypes.c_int32), ("line_log_scale_factor", ctypes.c_float), ("n_line_levels", ctypes.c_int32)]
+
+
+class TrackPointsC(ctypes.Structure):       # plvs_track_points
+    _fields_ = [("m", ctypes.c_int32)] + [(k, _vp) for k in ("skip", "pos", "normal", "min_dist", "max_dist", "desc", "has_obs", "in_view",
+                                                             "proj_x", "proj_y", "proj_xr", "track_depth", "level", "view_cos")]
+
+
+class TrackLinesC(ctypes.Structure):        # plvs_track_lines
+    _fields_ = [("m", ctypes.c_int32)] + [(k, _vp) for k in ("skip", "start", "end", "normal", "max_dist", "desc", "has_obs", "in_view",
+                                                             "proj", "proj_xr", "level", "view_cos")]
+
+
+PLVS_CAMERA_PINHOLE = 0
+L.plvs_hip_frame_is_in_frustum.argtypes = [_vp] * 7
+L.plvs_hip_frame_search_local_map.argtypes = ([_vp] * 5 + [ctypes.c_float, _i, ctypes.c_float, ctypes.c_float, _i] + [_vp] * 10)
+L.plvs_hip_frame_track_test_flip.argtypes = [_i]
+L.plvs_hip_frame_track_test_flip.restype = None
+
+
+def _track_camera(cam):
+    import numpy as np
+    keep = [np.ascontiguousarray(cam[k], np.float32) for k in ("K4", "bounds4", "Rcw", "tcw", "Ow")]
+    assert keep[0].size == 4 and keep[1].size == 4 and keep[2].size == 9 and keep[3].size == 3 and keep[4].size == 3
+    c = TrackCameraC(int(cam.get("n_cameras", 1)), int(cam.get("camera_model", PLVS_CAMERA_PINHOLE)), _lib.np_ptr(keep[0]), float(cam["mbf"]),
+                     _lib.np_ptr(keep[1]), _lib.np_ptr(keep[2]), _lib.np_ptr(keep[3]), _lib.np_ptr(keep[4]), float(cam["viewing_cos_limit"]),
+                     float(cam["log_scale_factor"]), int(cam["n_levels"]), float(cam["line_log_scale_factor"]), int(cam["n_line_levels"]))
+    return c, keep
+
+
+def _track_points(points):
+    import numpy as np
+    f, u8 = (lambda a: np.ascontiguousarray(a, np.float32)), (lambda a: None if a is None else np.ascontiguousarray(a, np.uint8))
+    m = len(points["skip"])
+    ins = [u8(points["skip"]), f(points["pos"]), f(points["normal"]), f(points["min_dist"]), f(points["max_dist"]), u8(points.get("desc")),
+           u8(points.get("has_obs"))]
+    out = dict(in_view=np.zeros(m, np.uint8), proj_x=np.zeros(m, np.float32), proj_y=np.zeros(m, np.float32), proj_xr=np.zeros(m, np.float32),
+               track_depth=np.zeros(m, np.float32), level=np.zeros(m, np.int32), view_cos=np.zeros(m, np.float32))
+    c = TrackPointsC(m, *[_lib.np_ptr(a) for a in ins], *[_lib.np_ptr(out[k]) for k in ("in_view", "proj_x", "proj_y", "proj_xr", "track_depth",
+                                                                                       "level", "view_cos")])
+    return c, ins, out
+
+
+def _track_lines(lines):
+    import numpy as np
+    f, u8 = (lambda a: np.ascontiguousarray(a, np.float32)), (lambda a: None if a is None else np.ascontiguousarray(a, np.uint8))
+    m = len(lines["skip"])
+    ins = [u8(lines["skip"]), f(lines["start"]), f(lines["end"]), f(lines["normal"]), f(lines["max_dist"]), u8(lines.get("desc")),
+           u8(lines.get("has_obs"))]
+    out = dict(in_view=np.zeros(m, np.uint8), proj=np.zeros((m, 6), np.float32), proj_xr=np.zeros((m, 2), np.float32),
+               level=np.zeros(m, np.int32), view_cos=np.zeros(m, np.float32))
+    c = TrackLinesC(m, *[_lib.np_ptr(a) for a in ins], *[_lib.np_ptr(out[k]) for k in ("in_view", "proj", "proj_xr", "level", "view_cos")])
+    return c, ins, out
+
+
+_STATS = ("ambiguous_points", "ambiguous_lines", "levels_changed", "window_launches")
+
+
+def is_in_frustum(cam, points=None, lines=None):
+    """Frame::isInFrustum over the local map.  cam: dict(K4, mbf, bounds4, Rcw [9, as Eigen::Matrix3f holds mRcw], tcw, Ow,
+    viewing_cos_limit, log_scale_factor, n_levels, line_log_scale_factor, n_line_levels); points: dict(skip, pos, normal,
+    min_dist, max_dist) or None; lines: dict(skip, start, end, normal, max_dist) or None.
+    -> dict(points=dict(in_view, proj_x, proj_y, proj_xr, track_depth, level, view_cos) | None, lines=dict(in_view, proj [m, 6],
+    proj_xr [m, 2], level, view_cos) | None, n_in_view_points, n_in_view_lines (the reference's nToMatch), stats)."""
+    import numpy as np
+    c, keep = _track_camera(cam)
+    pc, pk, po = _track_points(points) if points is not None else (None, None, None)
+    lc, lk, lo = _track_lines(lines) if lines is not None else (None, None, None)
+    nv, nvl, stats = _i(), _i(), np.zeros(4, np.int32)
+    _lib.check(L.plvs_hip_frame_is_in_frustum(ctypes.byref(c), ctypes.byref(pc) if pc else None, ctypes.byref(lc) if lc else None,
+                                              ctypes.byref(nv), ctypes.byref(nvl), _lib.np_ptr(stats), None))
+    return dict(points=po, lines=lo, n_in_view_points=nv.value, n_in_view_lines=nvl.value, stats=dict(zip(_STATS, (int(s) for s in stats))))
+
+
+def search_local_map(cam, frame_view, line_view, points, lines=None, th=1.0, far_points=False, th_far=50.0, nn_ratio=0.8, larger_search=False,
+                     occupied_points=None, occupied_lines=None):
+    """The frustum loops, then ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) and
+    LineMatcher::SearchByProjection(F, vpMapLines, bLargerSearch), with one device wait on the common path.  frame_view: an
+    orbmatcher.FrameView; line_view: what linematcher.line_frame_view returns, or None (no lines); points / lines as in
+    is_in_frustum, plus desc and (optionally) has_obs.  -> is_in_frustum's dict plus assigned_points, nmatches_points,
+    assigned_lines, nmatches_lines."""
+    import numpy as np
+    c, keep = _track_camera(cam)
+    fc = frame_view.as_c()
+    pc, pk, po = _track_points(points)
+    lc, lk, lo = _track_lines(lines) if lines is not None else (None, None, None)
+    lv = line_view[0] if line_view is not None else None
+    u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+    occ_p, occ_l = u8(occupied_points), u8(occupied_lines)
+    ap = np.full(max(fc.n, 1), -7, np.int32)
+    al = np.full(max(lv.n if lv is not None else 0, 1), -7, np.int32)
+    np_, nl_, nv, nvl, stats = _i(), _i(), _i(), _i(), np.zeros(4, np.int32)
+    _lib.check(L.plvs_hip_frame_search_local_map(ctypes.byref(c), ctypes.byref(fc), ctypes.byref(lv) if lv is not None else None, ctypes.byref(pc),
+                                                 ctypes.byref(lc) if lc else None, float(th), int(far_points), float(th_far), float(nn_ratio),
+                                                 int(larger_search), _lib.np_ptr(occ_p), _lib.np_ptr(occ_l), _lib.np_ptr(ap), ctypes.byref(np_),
+                                                 _lib.np_ptr(al), ctypes.byref(nl_), ctypes.byref(nv), ctypes.byref(nvl), _lib.np_ptr(stats), None))
+    return dict(points=po, lines=lo, n_in_view_points=nv.value, n_in_view_lines=nvl.value, stats=dict(zip(_STATS, (int(s) for s in stats))),
+                assigned_points=ap[:fc.n], nmatches_points=np_.value, assigned_lines=al[:lv.n] if lv is not None else al[:0],
+                nmatches_lines=nl_.value)
+
+
+def track_test_flip(point_index=-1):
+    """Test hook: see plvs_hip_frame_track_test_flip."""
+    L.plvs_hip_frame_track_test_flip(int(point_index))
