@@ -1551,6 +1551,106 @@ int plvs_hip_frame_search_local_map(const plvs_track_camera* cam, const plvs_fra
  * device agree everywhere.  -1 = off (the default). */
 void plvs_hip_frame_track_test_flip(int point_index);
 
+/* ------------------------------------------------------ Frame glue, motion model
+ * The search of Tracking::TrackWithMotionModel (src/Tracking.cc:3615-3664) in one call with one device wait on the common
+ * path: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1774-1993) and
+ * LineMatcher::SearchByProjection(CurrentFrame, LastFrame, bLargerSearch, bMono) (src/LineMatcher.cc:837-1230) INCLUDING the
+ * projection of the last frame's map points and map lines into the current frame — Tcw * x3Dw (Sophus' quaternion action, not
+ * R p + t), Pinhole::project, LineProjection::ProjectLineWithCheck (include/LineProjection.h:144-end), the bounds tests, the
+ * bForward / bBackward decision — which plvs_hip_orb_search_by_projection_ff and plvs_hip_lines_search_by_projection_ff leave
+ * to the caller, and the retry rules of Tracking.cc:3626-3663.  Single-camera frames with a pinhole camera only (Nleft ==
+ * NlinesLeft == -1, no mpCamera2): any other request is refused with PLVS_ERR_INVALID_ARG before anything is launched.  All
+ * arrays are host memory; every float result equals the reference's bit for bit. */
+typedef struct plvs_motion_poses {
+  int32_t n_cameras;            /* 1                                                                        */
+  int32_t camera_model;         /* PLVS_CAMERA_PINHOLE                                                      */
+  int32_t mono;                 /* the reference's bMono                                                    */
+  const float* q_cw;            /* CurrentFrame.GetPose().unit_quaternion().coeffs(): x, y, z, w            */
+  const float* tcw;             /* its translation, 3 (= mtcw)                                              */
+  const float* Rcw;             /* mRcw: 9 floats as Eigen::Matrix3f holds them (the lines)                 */
+  const float* Ow;              /* mOw, 3 (= Tcw.inverse().translation())                                   */
+  const float* q_lw;            /* LastFrame.GetPose(): quaternion coefficients x, y, z, w                  */
+  const float* tlw;             /* and translation, 3                                                       */
+  float mb, mbf;                /* CurrentFrame.mb, mbf                                                     */
+  const float* bounds4;         /* mnMinX, mnMaxX, mnMinY, mnMaxY                                           */
+  const float* K4;              /* mpCamera's parameters fx, fy, cx, cy (Pinhole::project: the points)      */
+  const float* K4_linear;       /* mvLinearParameters (projectLinear: the lines); NULL = K4                 */
+} plvs_motion_poses;
+/* Last-frame key points.  valid[i] = LastFrame.mvpMapPoints[i] && !mvbOutlier[i]; pos = GetWorldPos() (3 n); octave =
+ * LastFrame.mvKeys[i].octave; angle = LastFrame.mvKeysUn[i].angle (degrees); desc = GetDescriptor() (n x 32); has_obs =
+ * Observations() > 0 (NULL = all).  Optional outputs (each may be NULL), n entries each — what a caller of
+ * plvs_hip_orb_search_by_projection_ff would have had to compute: proj_valid[i] = the point passed every test of
+ * :1812-1820; u / v / invz = uv(0), uv(1), 1.0 / x3Dc(2) as far as the reference had computed them when it left the
+ * point (not valid: -1, -1, 0; invz < 0: invz alone; out of bounds: all three). */
+typedef struct plvs_motion_points {
+  int32_t n;
+  const uint8_t* valid;
+  const float* pos;
+  const int32_t* octave;
+  const float* angle;
+  const uint8_t* desc;
+  const uint8_t* has_obs;
+  uint8_t* proj_valid;
+  float* u;
+  float* v;
+  float* invz;
+} plvs_motion_points;
+/* Last-frame key lines.  valid[i] = LastFrame.mvpMapLines[i] && !mvbLineOutlier[i]; start / end = GetWorldEndPoints() (3 n
+ * each); max_dist = mfMaxDistance, raw (the band is [0.8f, 1.2f] * mfMaxDistance, src/MapLine.cc:707-719); octave / angle of
+ * LastFrame.mvKeyLinesUn[i] (radians).  Optional outputs: proj_valid[i] = ProjectLineWithCheck returned true; proj6[6 i ..]
+ * = uS, vS, uE, vE, invSz, invEz — the layout plvs_hip_lines_search_by_projection_ff reads — as far as the function had
+ * stored them when it returned (from -1, -1, -1, -1, 0, 0: a line rejected at the end point's bounds holds all six). */
+typedef struct plvs_motion_lines {
+  int32_t n;
+  const uint8_t* valid;
+  const float* start;
+  const float* end;
+  const float* max_dist;
+  const int32_t* octave;
+  const float* angle;
+  const uint8_t* desc;
+  const uint8_t* has_obs;
+  uint8_t* proj_valid;
+  float* proj6;
+} plvs_motion_lines;
+/* With both minima 0 the call is one point search at th plus one line search with bLargerSearch = false.  With
+ * min_point_matches = 20 and min_line_matches = 10 it is Tracking.cc:3626-3663 in order: fewer point matches than the
+ * minimum -> the assignment is cleared, the search repeated at 2 * th, and the lines start with bLargerSearch = true;
+ * fewer line matches than the minimum and not yet larger -> cleared and repeated with bLargerSearch = true.  A retry
+ * re-uses the projection; the projection kernel never runs twice.  With nothing to search (no last-frame point, or a frame
+ * without key points) both point searches return 0: a positive minimum reports the repetition at 2 * th and the larger line
+ * search, whether or not there are lines, and nothing is launched for the points.  nn_ratio_points: the matcher's mfNNratio, which this
+ * point search never reads (kept for the mirror of ORBmatcher(0.9, true)); nn_ratio_lines: LineMatcher(0.9). */
+typedef struct plvs_motion_policy {
+  float th;
+  float nn_ratio_points;
+  float nn_ratio_lines;
+  int32_t check_orientation;
+  int32_t min_point_matches;
+  int32_t min_line_matches;
+} plvs_motion_policy;
+typedef struct plvs_motion_result {
+  int32_t nmatches_points;          /* the reference's return values (of the last search of each kind)      */
+  int32_t nmatches_lines;
+  int32_t forward, backward;        /* bForward, bBackward                                                  */
+  float th_used;                    /* th or 2 * th                                                         */
+  int32_t larger_line_search_used;  /* bLargerSearch of the line search whose result is returned            */
+} plvs_motion_result;
+/* F with cur_angle (CurrentFrame.mvKeysUn[i].angle) and occupied_points as in plvs_hip_orb_search_by_projection_ff; LF and
+ * occupied_lines as in plvs_hip_lines_search_by_projection_ff.  F->scale_factors covers every octave of a valid point (at
+ * most 64 levels).  lines == NULL or lines->n == 0 (line tracker off): LF == NULL is allowed, assigned_lines is not
+ * touched.  assigned_points (F->n) / assigned_lines (LF->n): as in the two entries.  occupied_* hold for the retries as well
+ * (TrackWithMotionModel clears the frame's matches before each search: NULL there).  stats (4 entries, may be NULL): window
+ * launches (1 on the common path), point retries, line retries, candidate spills (more candidates than n * 32 + 4096: the
+ * window launch repeated with the room it needs).  More than 2^18 last line x key line pairs: the line distances go through
+ * plvs_hip_hamming_pairs, one more launch and wait.  stream: a hipStream_t, NULL = the calling thread's staging stream; the
+ * call waits for it before it returns; repeated launches run on the staging stream after that wait. */
+int plvs_hip_frame_search_last_frame(const plvs_motion_poses* poses, const plvs_frame_view* F, const float* cur_angle,
+                                     const plvs_line_frame_view* LF, const plvs_motion_points* points,
+                                     const plvs_motion_lines* lines, const plvs_motion_policy* policy,
+                                     const uint8_t* occupied_points, const uint8_t* occupied_lines, int32_t* assigned_points,
+                                     int32_t* assigned_lines, plvs_motion_result* result, int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

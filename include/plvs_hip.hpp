@@ -597,6 +597,50 @@ inline void SearchLocalMap(const plvs_track_camera& cam, const plvs_frame_view& 
                                         &out.nMatchesLines, &out.nToMatchPoints, &out.nToMatchLines, out.stats, stream));
 }
 
+// ---- the last frame (src/Tracking.cc:3615-3664): the search of TrackWithMotionModel in one call — the projection of the last
+// frame's map points and lines on the device (Tcw * x3Dw as Sophus' quaternion action, Pinhole::project,
+// LineProjection::ProjectLineWithCheck), ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) and
+// LineMatcher::SearchByProjection(CurrentFrame, LastFrame, bLargerSearch, bMono) behind it, and the retry rules.  Single-camera
+// pinhole frames only.
+struct MotionModelMatches {
+  std::vector<int32_t> assignedPoints, assignedLines;   // per current key point / key line: the last-frame index, or -1
+  int nPointMatches = 0, nLineMatches = 0;
+  bool bForward = false, bBackward = false, bLargerLineSearch = false;
+  float thUsed = 0.0f;
+  std::vector<uint8_t> projValidPoints, projValidLines;  // what the two separate entries expect from their caller
+  std::vector<float> u, v, invz, lineProj;               // lineProj: uS, vS, uE, vE, invSz, invEz per line
+  int32_t stats[4] = {0, 0, 0, 0};                       // see plvs_hip_frame_search_last_frame
+};
+// points / lines: the input members filled by the caller; their optional output members are ignored — the call works on copies
+// whose output members point into `out`, and the caller's structures are left as they are.  LF / lines nullptr without the line
+// tracker.  minPointMatches = 20, minLineMatches = 10 are Tracking's; 0, 0 make it one search of each kind.
+inline void TrackWithMotionModelSearch(const plvs_motion_poses& poses, const plvs_frame_view& F, const float* curAngles,
+                                       const plvs_line_frame_view* LF, const plvs_motion_points& pointsIn, const plvs_motion_lines* linesIn,
+                                       float th, bool checkOrientation, MotionModelMatches& out, const uint8_t* occupiedPoints = nullptr,
+                                       const uint8_t* occupiedLines = nullptr, int minPointMatches = 20, int minLineMatches = 10,
+                                       float nnRatioPoints = 0.9f, float nnRatioLines = 0.9f, void* stream = nullptr) {
+  plvs_motion_points points = pointsIn;
+  plvs_motion_lines linesCopy;
+  plvs_motion_lines* lines = nullptr;
+  if (linesIn) { linesCopy = *linesIn; lines = &linesCopy; }
+  const size_t n = (size_t)(points.n > 0 ? points.n : 0), nl = (size_t)(lines && lines->n > 0 ? lines->n : 0);
+  out.projValidPoints.assign(n, 0); out.u.assign(n, -1.0f); out.v.assign(n, -1.0f); out.invz.assign(n, 0.0f);
+  points.proj_valid = out.projValidPoints.data(); points.u = out.u.data(); points.v = out.v.data(); points.invz = out.invz.data();
+  out.projValidLines.assign(nl, 0); out.lineProj.assign(6 * nl, 0.0f);
+  if (lines) { lines->proj_valid = out.projValidLines.data(); lines->proj6 = out.lineProj.data(); }
+  out.assignedPoints.assign((size_t)(F.n > 0 ? F.n : 0), -1);
+  out.assignedLines.assign((size_t)(LF && LF->n > 0 ? LF->n : 0), -1);
+  plvs_motion_policy policy;
+  policy.th = th; policy.nn_ratio_points = nnRatioPoints; policy.nn_ratio_lines = nnRatioLines;
+  policy.check_orientation = checkOrientation ? 1 : 0; policy.min_point_matches = minPointMatches; policy.min_line_matches = minLineMatches;
+  plvs_motion_result res;
+  check(plvs_hip_frame_search_last_frame(&poses, &F, curAngles, LF, &points, lines, &policy, occupiedPoints, occupiedLines,
+                                         out.assignedPoints.data(), out.assignedLines.data(), &res, out.stats, stream));
+  out.nPointMatches = res.nmatches_points; out.nLineMatches = res.nmatches_lines;
+  out.bForward = res.forward != 0; out.bBackward = res.backward != 0; out.bLargerLineSearch = res.larger_line_search_used != 0;
+  out.thUsed = res.th_used;
+}
+
 // ------------------------------------------------------------------------------------ dense stereo
 // sgm::StereoSGM (Thirdparty/libsgm/include/libsgm.h:57-110) for 8-bit images and an 8-bit disparity, the way
 // PointCloudKeyFrame::ProcessStereoLibsgm constructs it; execute() is EXECUTE_INOUT_HOST2HOST.

@@ -155,9 +155,7 @@ int plvs_hip_orb_search_by_projection_ff(const plvs_frame_view* F, const float* 
   PLVS_REQUIRE(L->valid && L->u && L->v && L->invz && L->octave && L->angle && L->desc, "null last-frame array");
   const FrameGrid grid(F);
   // ---- the queries the reference would run (:1800-1840), then their windows and distances on the device
-  struct Query { int i; int first, count; };
   std::vector<WinQuery> wq;
-  std::vector<int> wq_src;
   wq.reserve((size_t)L->n);
   for (int i = 0; i < L->n; ++i) {
     if (!L->valid[i]) continue;
@@ -168,55 +166,14 @@ int plvs_hip_orb_search_by_projection_ff(const plvs_frame_view* F, const float* 
     if (v < F->min_y || v > max_y) continue;
     const int oct = L->octave[i];
     PLVS_REQUIRE(oct >= 0, "negative octave");
-    const float radius = th * F->scale_factors[oct];   // :1826
-    const int min_level = forward ? oct : (backward ? 0 : oct - 1);
-    const int max_level = forward ? 2147483647 : (backward ? oct : oct + 1);
-    wq.push_back(WinQuery{u, v, radius, u - mbf * invzc, min_level, max_level, i, (min_level > 0 || max_level >= 0) ? 1 : 0});
+    wq.push_back(last_frame_query(u, v, invzc, oct, th, F->scale_factors[oct], mbf, forward, backward, i));
   }
-  std::vector<Query> queries;
-  std::vector<int32_t> pair_t, dist, q_at, q_n;
+  std::vector<int32_t> pair_t, dist, q_at, q_n, src(wq.size());
   int rc = window_candidates(F, grid, wq, L->desc, L->n, q_at, q_n, pair_t, dist);
   if (rc != PLVS_OK) return rc;
-  for (size_t k = 0; k < wq.size(); ++k)
-    if (q_n[k]) queries.push_back(Query{wq[k].src, q_at[k], q_n[k]});
-  std::vector<uint8_t> blocked(F->n);
-  for (int i = 0; i < F->n; ++i) blocked[i] = occupied ? occupied[i] : 0;
-  std::vector<int> hist_item, hist_bin;   // rotHist: what was pushed, in order (duplicates possible)
-  const float factor = kHistoLength / 360.0f;
-  int n = 0;
-  for (const Query& q : queries) {
-    int best = 256, best_idx = -1;
-    for (int p = q.first; p < q.first + q.count; ++p) {
-      const int i2 = pair_t[p];
-      if (blocked[i2]) continue;   // CurrentFrame.mvpMapPoints[i2] && Observations() > 0
-      if (dist[p] < best) { best = dist[p]; best_idx = i2; }
-    }
-    if (best <= kThHigh) {
-      assigned[best_idx] = q.i;
-      blocked[best_idx] = L->has_obs ? L->has_obs[q.i] : 1;
-      ++n;
-      if (check_orientation) {
-        float rot = L->angle[q.i] - cur_angle[best_idx];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)std::round(rot * factor);
-        if (bin == kHistoLength) bin = 0;
-        hist_item.push_back(best_idx);
-        hist_bin.push_back(bin);
-      }
-    }
-  }
-  if (check_orientation) {
-    int count[kHistoLength] = {0};
-    for (int b : hist_bin) ++count[b];
-    int ind1, ind2, ind3;
-    three_maxima(count, kHistoLength, ind1, ind2, ind3);
-    for (size_t k = 0; k < hist_bin.size(); ++k)
-      if (hist_bin[k] != ind1 && hist_bin[k] != ind2 && hist_bin[k] != ind3) {
-        assigned[hist_item[k]] = -1;
-        --n;
-      }
-  }
-  *nmatches = n;
+  for (size_t k = 0; k < wq.size(); ++k) src[k] = wq[k].src;
+  *nmatches = greedy_last_frame_points(F, cur_angle, src.data(), wq.size(), q_at, q_n, pair_t, dist, L->angle, L->has_obs, check_orientation,
+                                       occupied, assigned);
   return PLVS_OK;
 }
 

@@ -297,6 +297,65 @@ __host__ __device__ inline WinQuery map_point_query(float proj_x, float proj_y, 
   return WinQuery{proj_x, proj_y, rr, proj_xr, level - 1, level, src, (level - 1 > 0 || level >= 0) ? 1 : 0};
 }
 
+// The window query of one last-frame point SearchByProjection(CurrentFrame, LastFrame, th, bMono) accepts (:1822-1835): the
+// radius th * mvScaleFactors[octave], the predicted right coordinate u - mbf * invz, the level band of bForward / bBackward /
+// neither.  The projection kernel of frame_motion.hip writes the same record on the device.
+__host__ __device__ inline WinQuery last_frame_query(float u, float v, float invz, int octave, float th, float scale_factor, float mbf,
+                                                     int forward, int backward, int src) {
+  const float radius = th * scale_factor;   // :1826
+  const int min_level = forward ? octave : (backward ? 0 : octave - 1);
+  const int max_level = forward ? 2147483647 : (backward ? octave : octave + 1);
+  return WinQuery{u, v, radius, u - mbf * invz, min_level, max_level, src, (min_level > 0 || max_level >= 0) ? 1 : 0};
+}
+
+// The greedy assignment of SearchByProjection(CurrentFrame, LastFrame) in last-frame order (:1842-1990) over the candidate lists
+// of window_candidates — query k belongs to last-frame key point src[k] (ascending) —, with the rotation histogram and its cut.
+// -> the reference's return value.
+int greedy_last_frame_points(const plvs_frame_view* F, const float* cur_angle, const int32_t* src, size_t nq, const std::vector<int32_t>& q_at,
+                             const std::vector<int32_t>& q_n, const std::vector<int32_t>& pair_t, const std::vector<int32_t>& dist,
+                             const float* angle, const uint8_t* has_obs, int check_orientation, const uint8_t* occupied, int32_t* assigned) {
+  std::vector<uint8_t> blocked(F->n);
+  for (int i = 0; i < F->n; ++i) blocked[i] = occupied ? occupied[i] : 0;
+  std::vector<int> hist_item, hist_bin;   // rotHist: what was pushed, in order (duplicates possible)
+  const float factor = kHistoLength / 360.0f;
+  int n = 0;
+  for (size_t k = 0; k < nq; ++k) {
+    if (q_n[k] == 0) continue;
+    const int i = src[k];
+    int best = 256, best_idx = -1;
+    for (int p = q_at[k]; p < q_at[k] + q_n[k]; ++p) {
+      const int i2 = pair_t[p];
+      if (blocked[i2]) continue;   // CurrentFrame.mvpMapPoints[i2] && Observations() > 0
+      if (dist[p] < best) { best = dist[p]; best_idx = i2; }
+    }
+    if (best <= kThHigh) {
+      assigned[best_idx] = i;
+      blocked[best_idx] = has_obs ? has_obs[i] : 1;
+      ++n;
+      if (check_orientation) {
+        float rot = angle[i] - cur_angle[best_idx];
+        if (rot < 0.0) rot += 360.0f;
+        int bin = (int)std::round(rot * factor);
+        if (bin == kHistoLength) bin = 0;
+        hist_item.push_back(best_idx);
+        hist_bin.push_back(bin);
+      }
+    }
+  }
+  if (check_orientation) {
+    int count[kHistoLength] = {0};
+    for (int b : hist_bin) ++count[b];
+    int ind1, ind2, ind3;
+    three_maxima(count, kHistoLength, ind1, ind2, ind3);
+    for (size_t k = 0; k < hist_bin.size(); ++k)
+      if (hist_bin[k] != ind1 && hist_bin[k] != ind2 && hist_bin[k] != ind3) {
+        assigned[hist_item[k]] = -1;
+        --n;
+      }
+  }
+  return n;
+}
+
 }  // namespace
 }  // namespace orbwin
 }  // namespace plvs

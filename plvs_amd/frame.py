@@ -520,3 +520,83 @@ def search_local_map(cam, frame_view, line_view, points, lines=None, th=1.0, far
 def track_test_flip(point_index=-1):
     """Test hook: see plvs_hip_frame_track_test_flip."""
     L.plvs_hip_frame_track_test_flip(int(point_index))
+
+
+# ---------------------------------------------------------------------------------------------- the last frame (TrackWithMotionModel)
+# The search of Tracking::TrackWithMotionModel (src/Tracking.cc:3615-3664) in one call: the projection of the last frame's map
+# points and lines on the device, the two SearchByProjection(CurrentFrame, LastFrame, ...) behind it, the retry rules.
+class MotionPosesC(ctypes.Structure):       # plvs_motion_poses
+    _fields_ = [("n_cameras", ctypes.c_int32), ("camera_model", ctypes.c_int32), ("mono", ctypes.c_int32), ("q_cw", _vp), ("tcw", _vp),
+                ("Rcw", _vp), ("Ow", _vp), ("q_lw", _vp), ("tlw", _vp), ("mb", ctypes.c_float), ("mbf", ctypes.c_float), ("bounds4", _vp),
+                ("K4", _vp), ("K4_linear", _vp)]
+
+
+class MotionPointsC(ctypes.Structure):      # plvs_motion_points
+    _fields_ = [("n", ctypes.c_int32)] + [(k, _vp) for k in ("valid", "pos", "octave", "angle", "desc", "has_obs", "proj_valid", "u", "v", "invz")]
+
+
+class MotionLinesC(ctypes.Structure):       # plvs_motion_lines
+    _fields_ = [("n", ctypes.c_int32)] + [(k, _vp) for k in ("valid", "start", "end", "max_dist", "octave", "angle", "desc", "has_obs",
+                                                             "proj_valid", "proj6")]
+
+
+class MotionPolicyC(ctypes.Structure):      # plvs_motion_policy
+    _fields_ = [("th", ctypes.c_float), ("nn_ratio_points", ctypes.c_float), ("nn_ratio_lines", ctypes.c_float),
+                ("check_orientation", ctypes.c_int32), ("min_point_matches", ctypes.c_int32), ("min_line_matches", ctypes.c_int32)]
+
+
+class MotionResultC(ctypes.Structure):      # plvs_motion_result
+    _fields_ = [("nmatches_points", ctypes.c_int32), ("nmatches_lines", ctypes.c_int32), ("forward", ctypes.c_int32), ("backward", ctypes.c_int32),
+                ("th_used", ctypes.c_float), ("larger_line_search_used", ctypes.c_int32)]
+
+
+L.plvs_hip_frame_search_last_frame.argtypes = [_vp] * 14
+_MOTION_STATS = ("window_launches", "point_retries", "line_retries", "candidate_spills")
+
+
+def search_last_frame(poses, frame_view, cur_angle, line_view, points, lines=None, th=15.0, nn_ratio_points=0.9, nn_ratio_lines=0.9,
+                      check_orientation=True, min_point_matches=0, min_line_matches=0, occupied_points=None, occupied_lines=None):
+    """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) and LineMatcher::SearchByProjection(CurrentFrame,
+    LastFrame, bLargerSearch, bMono) with the projection of the last frame's map points and lines on the device; with
+    min_point_matches = 20 and min_line_matches = 10 the retry rules of Tracking::TrackWithMotionModel.  poses: dict(q_cw [x, y, z,
+    w], tcw, Rcw [9, as Eigen::Matrix3f holds mRcw], Ow, q_lw, tlw, mb, mbf, bounds4, K4, K4_linear (optional), mono, n_cameras
+    (optional), camera_model (optional)); frame_view: an orbmatcher.FrameView; cur_angle: mvKeysUn[i].angle; line_view: what
+    linematcher.line_frame_view returns, or None; points: dict(valid, pos, octave, angle, desc, has_obs (optional)) — None entries
+    reach the library as NULL —; lines: dict(valid, start, end, max_dist, octave, angle, desc, has_obs (optional)) or None.
+    -> dict(assigned_points, nmatches_points, assigned_lines, nmatches_lines, forward, backward, th_used,
+    larger_line_search_used, proj_valid_points, u, v, invz, proj_valid_lines, proj6, stats)."""
+    import numpy as np
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+    keep = [f(poses.get(k)) for k in ("q_cw", "tcw", "Rcw", "Ow", "q_lw", "tlw", "bounds4", "K4", "K4_linear")]
+    pc = MotionPosesC(int(poses.get("n_cameras", 1)), int(poses.get("camera_model", PLVS_CAMERA_PINHOLE)), int(bool(poses.get("mono", 0))),
+                      *[_lib.np_ptr(a) for a in keep[:6]], float(poses["mb"]), float(poses["mbf"]), *[_lib.np_ptr(a) for a in keep[6:]])
+    fc = frame_view.as_c()
+    ang = f(cur_angle)
+    n = len(points["valid"])
+    pin = [u8(points["valid"]), f(points["pos"]), i32(points["octave"]), f(points["angle"]), u8(points["desc"]), u8(points.get("has_obs"))]
+    pout = dict(proj_valid=np.zeros(n, np.uint8), u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), invz=np.zeros(n, np.float32))
+    ptc = MotionPointsC(n, *[_lib.np_ptr(a) for a in pin], *[_lib.np_ptr(pout[k]) for k in ("proj_valid", "u", "v", "invz")])
+    lc, lin, lout = None, None, dict(proj_valid=np.zeros(0, np.uint8), proj6=np.zeros((0, 6), np.float32))
+    if lines is not None:
+        nl = len(lines["valid"])
+        lin = [u8(lines["valid"]), f(lines["start"]), f(lines["end"]), f(lines["max_dist"]), i32(lines["octave"]), f(lines["angle"]),
+               u8(lines["desc"]), u8(lines.get("has_obs"))]
+        lout = dict(proj_valid=np.zeros(nl, np.uint8), proj6=np.zeros((nl, 6), np.float32))
+        lc = MotionLinesC(nl, *[_lib.np_ptr(a) for a in lin], _lib.np_ptr(lout["proj_valid"]), _lib.np_ptr(lout["proj6"]))
+    lv = line_view[0] if line_view is not None else None
+    occ_p, occ_l = u8(occupied_points), u8(occupied_lines)
+    ap = np.full(max(fc.n, 1), -7, np.int32)
+    al = np.full(max(lv.n if lv is not None else 0, 1), -7, np.int32)
+    pol = MotionPolicyC(float(th), float(nn_ratio_points), float(nn_ratio_lines), int(bool(check_orientation)), int(min_point_matches),
+                        int(min_line_matches))
+    res, stats = MotionResultC(), np.zeros(4, np.int32)
+    _lib.check(L.plvs_hip_frame_search_last_frame(ctypes.byref(pc), ctypes.byref(fc), _lib.np_ptr(ang), ctypes.byref(lv) if lv is not None else None,
+                                                  ctypes.byref(ptc), ctypes.byref(lc) if lc is not None else None, ctypes.byref(pol),
+                                                  _lib.np_ptr(occ_p), _lib.np_ptr(occ_l), _lib.np_ptr(ap), _lib.np_ptr(al), ctypes.byref(res),
+                                                  _lib.np_ptr(stats), None))
+    return dict(assigned_points=ap[:fc.n], nmatches_points=res.nmatches_points, assigned_lines=al[:lv.n] if lv is not None else al[:0],
+                nmatches_lines=res.nmatches_lines, forward=res.forward, backward=res.backward, th_used=res.th_used,
+                larger_line_search_used=res.larger_line_search_used, proj_valid_points=pout["proj_valid"], u=pout["u"], v=pout["v"],
+                invz=pout["invz"], proj_valid_lines=lout["proj_valid"], proj6=lout["proj6"], stats=dict(zip(_MOTION_STATS, (int(s) for s in stats))))
