@@ -1651,6 +1651,68 @@ int plvs_hip_frame_search_last_frame(const plvs_motion_poses* poses, const plvs_
                                      const uint8_t* occupied_points, const uint8_t* occupied_lines, int32_t* assigned_points,
                                      int32_t* assigned_lines, plvs_motion_result* result, int32_t* stats, void* stream);
 
+/* ------------------------------------------------- ORBmatcher::Fuse, the search stage, K key frames x M points in one call
+ * ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight = false) (src/ORBmatcher.cc:1244-1434) up to the choice of bestIdx, for every
+ * key frame LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1372-1410) would call it with: one copy in, one launch, one
+ * device wait.  Single-camera pinhole key frames only (NLeft == -1, bRight == false): any other request is refused with
+ * PLVS_ERR_INVALID_ARG before anything is launched.  The map mutation behind bestDist <= TH_LOW (:1408-1427: AddObservation,
+ * AddMapPoint, Replace) stays the caller's; INTEGRATION.md spells out how the batched candidates are replayed in the
+ * reference's order.  All arrays are host memory; every result equals the reference's bit for bit. */
+typedef struct plvs_fuse_keyframe {
+  plvs_frame_view view;            /* N, mvKeysUn x / y / octave, mvuRight (>= 0: stereo gate), mDescriptors, mnMinX / mnMinY,   */
+                                   /* mfGridElementWidthInv / HeightInv, mvScaleFactors (n_levels)                              */
+  const float* inv_level_sigma2;   /* mvInvLevelSigma2, n_levels                                                               */
+  int32_t n_levels;                /* mnScaleLevels, 1 .. 64; every octave lies in [0, n_levels)                                */
+  float log_scale_factor;          /* mfLogScaleFactor                                                                          */
+  int32_t n_cameras;               /* 1                                                                                         */
+  int32_t camera_model;            /* PLVS_CAMERA_PINHOLE                                                                       */
+  const float* K4;                 /* mpCamera's parameters fx, fy, cx, cy                                                      */
+  float mbf;
+  const float* bounds4;            /* mnMinX, mnMaxX, mnMinY, mnMaxY (IsInImage: >= min && < max); the key frame holds them as  */
+                                   /* int: integral values                                                                      */
+  const float* q_cw;               /* GetPose().unit_quaternion().coeffs(): x, y, z, w                                          */
+  const float* tcw;                /* its translation, 3                                                                        */
+  const float* Ow;                 /* GetCameraCenter(), 3                                                                      */
+} plvs_fuse_keyframe;
+/* pos = GetWorldPos() (3 m), normal = GetNormal() (3 m), min_dist / max_dist = mfMinDistance / mfMaxDistance, raw (the band is
+ * 0.8f * min .. 1.2f * max), desc = GetDescriptor() (m x 32). */
+typedef struct plvs_fuse_points {
+  int32_t m;
+  const float* pos;
+  const float* normal;
+  const float* min_dist;
+  const float* max_dist;
+  const uint8_t* desc;
+} plvs_fuse_points;
+/* reached[k * m + i]: the `continue` pair (key frame k, point i) left by */
+#define PLVS_FUSE_SKIPPED 0       /* skip[k * m + i] != 0: !pMP || isBad() || IsInKeyFrame(pKF) at the time of the call          */
+#define PLVS_FUSE_BEHIND 1        /* p3Dc(2) < 0.0f                                                                              */
+#define PLVS_FUSE_OUTSIDE 2       /* !IsInImage (a NaN or an infinity from z == +-0 included)                                    */
+#define PLVS_FUSE_TOO_NEAR 3
+#define PLVS_FUSE_TOO_FAR 4
+#define PLVS_FUSE_VIEW_ANGLE 5    /* PO.dot(Pn) < 0.5 * dist3D; dist3D == 0 (the level undefined in the reference) as well       */
+#define PLVS_FUSE_EMPTY_WINDOW 6  /* GetFeaturesInArea returned nothing                                                          */
+#define PLVS_FUSE_NO_CANDIDATE 7  /* nobody passed the level band and the chi-square gate (bestDist stayed 256)                  */
+#define PLVS_FUSE_ABOVE_TH_LOW 8  /* bestDist > TH_LOW                                                                           */
+#define PLVS_FUSE_CANDIDATE 9     /* bestDist <= TH_LOW: :1408-1427 is the caller's                                              */
+/* kfs: n_kfs key frames; skip: n_kfs x m, NULL = none.  th: [0, 1e6].  Outputs, n_kfs x m each: best_idx = the reference's
+ * bestIdx where bestDist <= TH_LOW (50), -1 otherwise; best_dist = bestDist there, -1 otherwise; reached (may be NULL) as
+ * above.  stats (3 entries, may be NULL): pairs whose level the host's logarithm had to decide (they went through
+ * plvs_hip_orb_fuse_search_host's code after the wait), pairs that reached the window (every test passed), launches (1).
+ * n_kfs == 0, m == 0, no key frame with key points or every pair skipped: nothing is launched, PLVS_OK, every pair reported.
+ * NULL best_idx / best_dist: refused.  stream: a hipStream_t, NULL = the calling thread's staging stream; the call waits
+ * for it before it returns. */
+int plvs_hip_orb_fuse_search(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
+                             int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream);
+/* The same on the host, serially, with no HIP call: for callers that re-query a handful of pairs with live descriptors
+ * (the replay) and for machines without a device.  stats[0] = 0, stats[2] = 0. */
+int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip,
+                                  float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats);
+/* Testing and measurement only, outside the stable ABI: the calling thread's later plvs_hip_orb_fuse_search calls run, with
+ * mode 1, the projection as a thread-per-pair launch chained in front of the windows (2 launches) instead of inside them;
+ * with mode 2, the staging and the copy in alone (nothing launched, the outputs untouched); 0: back to normal. */
+void plvs_hip_orb_fuse_test_chained(int mode);
+
 #ifdef __cplusplus
 }
 #endif

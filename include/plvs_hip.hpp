@@ -250,6 +250,36 @@ class ORBmatcher {
                                      mfNNratio, mbCheckOrientation ? 1 : 0, assigned.data(), &n));
     return n;
   }
+  // The search stage of Fuse(KeyFramePtr& pKF, const vector<MapPointPtr>& vpMapPoints, th, bRight = false), ORBmatcher.cc:1244,
+  // for every target key frame of LocalMapping::SearchInNeighbors in one call.  skip (keyFrames.size() x vpMapPoints.m, or
+  // null): !pMP || isBad() || IsInKeyFrame(pKF).  bestIdx / bestDist / reached: one entry per (key frame, point), see
+  // plvs_hip.h; the mutation of :1408-1427 and its replay in the reference's order are the caller's.
+  // onHost: plvs_hip_orb_fuse_search_host (no device call: the replay's re-query of a dirty point).  -> candidates found.
+  struct FuseResult {
+    std::vector<int32_t> bestIdx, bestDist;
+    std::vector<uint8_t> reached;
+    int32_t stats[3] = {0, 0, 0};
+  };
+  int FuseSearch(const std::vector<plvs_fuse_keyframe>& keyFrames, const plvs_fuse_points& vpMapPoints, const uint8_t* skip, float th,
+                 FuseResult& result, bool onHost = false, void* stream = nullptr) const {
+    const size_t pairs = keyFrames.size() * (size_t)vpMapPoints.m;
+    result.bestIdx.assign(pairs + 1, -1);   // (+ 1: the entries refuse null outputs, with nothing to report as well)
+    result.bestDist.assign(pairs + 1, -1);
+    result.reached.assign(pairs + 1, 0);
+    const int K = (int)keyFrames.size();
+    if (onHost)
+      check(plvs_hip_orb_fuse_search_host(keyFrames.data(), K, &vpMapPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                          result.reached.data(), result.stats));
+    else
+      check(plvs_hip_orb_fuse_search(keyFrames.data(), K, &vpMapPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                     result.reached.data(), result.stats, stream));
+    result.bestIdx.resize(pairs);
+    result.bestDist.resize(pairs);
+    result.reached.resize(pairs);
+    int n = 0;
+    for (size_t p = 0; p < pairs; ++p) n += result.bestIdx[p] >= 0 ? 1 : 0;
+    return n;
+  }
   float mfNNratio;
   bool mbCheckOrientation;
 };

@@ -1,0 +1,355 @@
+// The search stage of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight = false) (reference src/ORBmatcher.cc:1244-1434) as
+// LocalMapping::SearchInNeighbors calls it (src/LocalMapping.cc:1372-1410): K key frames x M map points in ONE call — one copy in,
+// one launch (two in the chained layout), one wait.  Single-camera pinhole key frames only (NLeft == -1).
+//
+// Fuse has no greedy pass: a pair's result depends on nobody else's.  A wave takes one (key frame, point) pair; the projection and
+// the tests of fuse_pair.hpp are uniform across it and a rejected pair leaves at once; an accepted pair walks its window columns in
+// 64-member strides (the CSR grid of orb_window.hpp), every lane keeping the smallest (distance, enumeration position) it has
+// seen; one cross-lane minimum, and lane 0 posts the pair's record straight into the pinned block.  No candidate list, no spill.
+//
+// The level needs the host's logarithm (track_level.hpp): the pairs predict_level marks ambiguous are evaluated once more by the
+// host entry's code after the wait, and their result is simply the host's.
+//
+// Map mutation (AddObservation, AddMapPoint, Replace) stays the caller's: INTEGRATION.md has the replay.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.hpp"
+#include "fuse_pair.hpp"
+#include "orb_window.hpp"
+
+namespace {
+
+using plvs::fusepair::Front;
+using plvs::fusepair::KfConst;
+using plvs::orbwin::FrameGrid;
+namespace fp = plvs::fusepair;
+
+constexpr int kMaxLevels = 64;
+constexpr int kPosBits = 23;   // a lane's key: distance (9 bits) above the enumeration position
+
+// one key frame in the staged block: the constants and where its arrays start (bytes from the block's start)
+struct KfDev {
+  KfConst k;
+  int n, pad;
+  unsigned long long o_mem, o_start, o_ur, o_desc, o_sf, o_sig;
+};
+
+struct FusePoints {
+  const float *pos, *normal, *min_dist, *max_dist;
+  const uint4* desc;
+  const uint8_t* skip;   // n_kfs x m, or null
+  int m, n_pairs;
+};
+
+// the record a pair posts: best_idx, and best_dist (16 bits, 0xffff = -1) | reached << 16 | ambiguous << 24
+__host__ __device__ inline int2 pack(int best_idx, int best_dist, int reached, int ambiguous) {
+  return make_int2(best_idx, (best_dist & 0xffff) | (reached << 16) | (ambiguous << 24));
+}
+
+// the chained layout's front kernel: a thread per pair, :1294-1337
+__global__ __launch_bounds__(256) void fuse_front_kernel(const KfDev* __restrict__ kfs, FusePoints P, Front* __restrict__ fronts) {
+  const int pair = blockIdx.x * 256 + threadIdx.x;
+  if (pair >= P.n_pairs) return;
+  const int k = pair / P.m, i = pair - k * P.m;
+  Front f{fp::kSkipped, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (!(P.skip && P.skip[pair])) f = fp::front(kfs[k].k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
+  fronts[pair] = f;
+}
+
+template <bool kChained>
+__global__ __launch_bounds__(256) void fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FusePoints P, float th,
+                                                          const Front* __restrict__ fronts, int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= P.n_pairs) return;
+  const int k = pair / P.m, i = pair - k * P.m;
+  Front f;
+  if (kChained) {
+    f = fronts[pair];
+  } else {
+    if (P.skip && P.skip[pair]) {
+      if (lane == 0) out[pair] = pack(-1, -1, fp::kSkipped, 0);
+      return;
+    }
+    f = fp::front(kfs[k].k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
+  }
+  if (f.reached != fp::kEmptyWindow) {
+    if (lane == 0) out[pair] = pack(-1, -1, f.reached, 0);
+    return;
+  }
+  const KfDev& D = kfs[k];
+  const float radius = th * reinterpret_cast<const float*>(base + D.o_sf)[f.level];
+  fp::Cells w;
+  if (D.n == 0 || !fp::window_cells(D.k, f.u, f.v, radius, &w)) {
+    if (lane == 0) out[pair] = pack(-1, -1, fp::kEmptyWindow, f.ambiguous);
+    return;
+  }
+  const FrameGrid::Member* members = reinterpret_cast<const FrameGrid::Member*>(base + D.o_mem);
+  const int* start = reinterpret_cast<const int*>(base + D.o_start);
+  const float* u_right = reinterpret_cast<const float*>(base + D.o_ur);
+  const uint4* desc = reinterpret_cast<const uint4*>(base + D.o_desc);
+  const float* sig = reinterpret_cast<const float*>(base + D.o_sig);
+  const uint4 qa = P.desc[2 * (size_t)i], qb = P.desc[2 * (size_t)i + 1];
+  uint32_t best = 0xffffffffu;
+  int best_idx = -1;
+  bool any = false, gated = false;
+  uint32_t pos0 = 0;   // enumeration position of the column's first member
+  for (int ix = w.c0; ix <= w.c1; ++ix) {
+    const int s = start[ix * fp::kGridRows + w.r0], e = start[ix * fp::kGridRows + w.r1 + 1];
+    for (int j = s + lane; j < e; j += 64) {
+      const FrameGrid::Member mb = members[j];
+      if (!fp::in_area(mb.x, mb.y, f.u, f.v, radius)) continue;
+      any = true;
+      if (!fp::candidate_gate(f.u, f.v, f.ur, f.level, mb.x, mb.y, mb.octave, u_right[mb.idx], sig)) continue;
+      gated = true;
+      const uint4 ta = desc[2 * (size_t)mb.idx], tb = desc[2 * (size_t)mb.idx + 1];
+      const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
+                         __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+      const uint32_t key = (d << kPosBits) | (pos0 + (uint32_t)(j - s));
+      if (key < best) { best = key; best_idx = mb.idx; }
+    }
+    pos0 += (uint32_t)(e - s);
+  }
+  // one reduction: the smallest key is the first minimum in enumeration order; keys are distinct
+  uint32_t lowest = best;
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)lowest, off);
+    lowest = o < lowest ? o : lowest;
+  }
+  const unsigned long long has_any = __ballot(any), has_gated = __ballot(gated);
+  const unsigned long long owner = __ballot(gated && best == lowest);
+  int win_idx = -1;
+  if (owner) win_idx = __shfl(best_idx, __ffsll((long long)owner) - 1);
+  if (lane == 0) {
+    int reached = fp::kEmptyWindow, idx = -1, dist = -1;
+    if (has_any) {
+      const int d = (int)(lowest >> kPosBits);
+      reached = !has_gated ? fp::kNoCandidate : (d <= fp::kThLow ? fp::kCandidate : fp::kAboveThLow);
+      if (reached == fp::kCandidate) { idx = win_idx; dist = d; }
+    }
+    out[pair] = pack(idx, dist, reached, f.ambiguous);
+  }
+}
+
+KfConst kf_const(const plvs_fuse_keyframe& kf) {
+  KfConst c;
+  for (int i = 0; i < 4; ++i) c.q[i] = kf.q_cw[i];
+  for (int i = 0; i < 3; ++i) { c.t[i] = kf.tcw[i]; c.Ow[i] = kf.Ow[i]; }
+  c.fx = kf.K4[0]; c.fy = kf.K4[1]; c.cx = kf.K4[2]; c.cy = kf.K4[3];
+  c.mbf = kf.mbf;
+  c.min_x = kf.bounds4[0]; c.max_x = kf.bounds4[1]; c.min_y = kf.bounds4[2]; c.max_y = kf.bounds4[3];
+  c.grid_min_x = kf.view.min_x; c.grid_min_y = kf.view.min_y;
+  c.grid_w_inv = kf.view.grid_w_inv; c.grid_h_inv = kf.view.grid_h_inv;
+  c.log_scale_factor = kf.log_scale_factor;
+  c.n_levels = kf.n_levels;
+  return c;
+}
+
+// the refusals of both entries: before anything is launched or written
+int check_args(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
+  PLVS_REQUIRE(n_kfs >= 0 && P && P->m >= 0, "null points / negative size");
+  PLVS_REQUIRE(best_idx && best_dist, "null output");
+  PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
+  PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
+  PLVS_REQUIRE((long long)n_kfs * P->m <= (1ll << 30), "more than 2^30 pairs");
+  PLVS_REQUIRE(P->m == 0 || (P->pos && P->normal && P->min_dist && P->max_dist && P->desc), "null map point array");
+  for (int k = 0; k < n_kfs; ++k) {
+    const plvs_fuse_keyframe& kf = kfs[k];
+    PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
+                 "single-camera pinhole key frames only (NLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
+    PLVS_REQUIRE(kf.K4 && kf.bounds4 && kf.q_cw && kf.tcw && kf.Ow, "null pose / camera array");
+    PLVS_REQUIRE(kf.n_levels >= 1 && kf.n_levels <= kMaxLevels && kf.inv_level_sigma2 && kf.view.scale_factors, "levels outside [1, 64] or null level arrays");
+    PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key point count outside [0, 2^23)");
+    if (kf.view.n > 0) {
+      PLVS_REQUIRE(kf.view.x && kf.view.y && kf.view.octave && kf.view.u_right && kf.view.desc, "null key frame array");
+      for (int i = 0; i < kf.view.n; ++i)
+        PLVS_REQUIRE(kf.view.octave[i] >= 0 && kf.view.octave[i] < kf.n_levels, "octave of a key point outside the key frame's levels");
+    }
+  }
+  return PLVS_OK;
+}
+
+// one pair on the host (the host entry; the device entry's ambiguous pairs and launch-free calls)
+fp::Result host_pair(const plvs_fuse_keyframe& kf, const KfConst& c, const FrameGrid& grid, const plvs_fuse_points* P, int i, float th) {
+  const fp::KfGrid<FrameGrid::Member> G{grid.start.data(), grid.members.data(), kf.view.u_right, kf.view.desc, kf.view.scale_factors,
+                                        kf.inv_level_sigma2};
+  return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
+}
+
+struct Outputs {
+  int32_t *best_idx, *best_dist;
+  uint8_t* reached;
+  void put(size_t pair, const fp::Result& r) const {
+    best_idx[pair] = r.best_idx;
+    best_dist[pair] = r.best_dist;
+    if (reached) reached[pair] = (uint8_t)r.reached;
+  }
+};
+
+void host_all(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th, const Outputs& out, int* windows) {
+  const int m = P->m;
+  for (int k = 0; k < n_kfs; ++k) {
+    const FrameGrid grid(&kfs[k].view);
+    const KfConst c = kf_const(kfs[k]);
+    for (int i = 0; i < m; ++i) {
+      const size_t pair = (size_t)k * m + i;
+      const fp::Result r = (skip && skip[pair]) ? fp::Result{-1, -1, fp::kSkipped} : host_pair(kfs[k], c, grid, P, i, th);
+      out.put(pair, r);
+      if (r.reached >= fp::kEmptyWindow) ++*windows;
+    }
+  }
+}
+
+struct StreamGuard {   // no call leaves with its kernel still writing into the thread's staging block
+  hipStream_t s;
+  bool armed = false;
+  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
+};
+
+// test / measurement hook.  1: the projection in a launch of its own in front of the windows; 2: the copy in alone
+thread_local int g_chained = 0;
+
+int run_device(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th, const Outputs& out,
+               int32_t* stats, hipStream_t stream, bool own_stream) {
+  const int m = P->m;
+  const size_t n_pairs = (size_t)n_kfs * m;
+  int st_host = 0, st_windows = 0, st_launches = 0;
+  auto post_stats = [&]() {
+    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = st_launches; }
+  };
+  // anything for the device?  a pair that is not skipped, in a key frame that has key points
+  bool work = false;
+  for (int k = 0; k < n_kfs && !work; ++k) {
+    if (kfs[k].view.n == 0) continue;
+    if (!skip) { work = m > 0; continue; }
+    for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
+  }
+  if (!work) {   // nothing launched: every pair is still reported (a key frame without key points: the tests, then an empty window)
+    host_all(kfs, n_kfs, P, skip, th, out, &st_windows);
+    post_stats();
+    return PLVS_OK;
+  }
+
+  // ---- one staged block: [key-frame table | points | every key frame's members, cell starts, u_right, descriptors, levels]
+  // copied in one piece, [fronts (chained layout), HBM only], [records, posted into the pinned side]
+  std::vector<FrameGrid> grids;
+  grids.reserve((size_t)n_kfs);
+  for (int k = 0; k < n_kfs; ++k) grids.emplace_back(&kfs[k].view);
+  size_t at = 0;
+  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+  const size_t o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
+  const size_t o_pos = take(sizeof(float) * 3 * (size_t)m), o_nrm = take(sizeof(float) * 3 * (size_t)m);
+  const size_t o_mind = take(sizeof(float) * (size_t)m), o_maxd = take(sizeof(float) * (size_t)m), o_pd = take((size_t)m * 32);
+  const size_t o_skip = take(skip ? n_pairs : 0);
+  std::vector<KfDev> tab((size_t)n_kfs);
+  for (int k = 0; k < n_kfs; ++k) {
+    KfDev& D = tab[k];
+    D.k = kf_const(kfs[k]);
+    D.n = kfs[k].view.n;
+    D.pad = 0;
+    D.o_mem = take(sizeof(FrameGrid::Member) * (size_t)D.n);
+    D.o_start = take(D.n ? sizeof(int) * grids[k].start.size() : 0);
+    D.o_ur = take(sizeof(float) * (size_t)D.n);
+    D.o_desc = take((size_t)D.n * 32);
+    D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_levels);
+    D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_levels);
+  }
+  const size_t in_end = at;
+  const size_t o_front = take(g_chained == 1 ? sizeof(Front) * n_pairs : 0);
+  const size_t o_out = take(sizeof(int2) * n_pairs);
+  plvs::HostStage& st = plvs::thread_stage();
+  PLVS_HIP_TRY(st.reserve(at + 16));
+  if (own_stream) stream = st.stream;
+
+  memcpy(st.pinned + o_tab, tab.data(), sizeof(KfDev) * (size_t)n_kfs);
+  memcpy(st.pinned + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
+  memcpy(st.pinned + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
+  memcpy(st.pinned + o_mind, P->min_dist, sizeof(float) * (size_t)m);
+  memcpy(st.pinned + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
+  memcpy(st.pinned + o_pd, P->desc, (size_t)m * 32);
+  if (skip) memcpy(st.pinned + o_skip, skip, n_pairs);
+  for (int k = 0; k < n_kfs; ++k) {
+    const KfDev& D = tab[k];
+    const plvs_fuse_keyframe& kf = kfs[k];
+    if (D.n) {
+      memcpy(st.pinned + D.o_mem, grids[k].members.data(), sizeof(FrameGrid::Member) * (size_t)D.n);
+      memcpy(st.pinned + D.o_start, grids[k].start.data(), sizeof(int) * grids[k].start.size());
+      memcpy(st.pinned + D.o_ur, kf.view.u_right, sizeof(float) * (size_t)D.n);
+      memcpy(st.pinned + D.o_desc, kf.view.desc, (size_t)D.n * 32);
+    }
+    memcpy(st.pinned + D.o_sf, kf.view.scale_factors, sizeof(float) * (size_t)kf.n_levels);
+    memcpy(st.pinned + D.o_sig, kf.inv_level_sigma2, sizeof(float) * (size_t)kf.n_levels);
+  }
+  StreamGuard guard{stream};
+  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
+  guard.armed = true;
+  if (g_chained == 2) {   // measurement only: the staging and the copy in, nothing launched, the outputs untouched
+    PLVS_HIP_TRY(hipStreamSynchronize(stream));
+    guard.armed = false;
+    post_stats();
+    return PLVS_OK;
+  }
+  const FusePoints FP{reinterpret_cast<const float*>(st.dev + o_pos), reinterpret_cast<const float*>(st.dev + o_nrm),
+                      reinterpret_cast<const float*>(st.dev + o_mind), reinterpret_cast<const float*>(st.dev + o_maxd),
+                      reinterpret_cast<const uint4*>(st.dev + o_pd), skip ? reinterpret_cast<const uint8_t*>(st.dev + o_skip) : nullptr,
+                      m, (int)n_pairs};
+  const KfDev* dtab = reinterpret_cast<const KfDev*>(st.dev + o_tab);
+  int2* rec = reinterpret_cast<int2*>(st.pinned + o_out);
+  if (g_chained == 1) {
+    Front* fronts = reinterpret_cast<Front*>(st.dev + o_front);
+    hipLaunchKernelGGL(fuse_front_kernel, dim3(plvs::ceil_div(n_pairs, 256)), dim3(256), 0, stream, dtab, FP, fronts);
+    PLVS_KERNEL_CHECK();
+    ++st_launches;
+    hipLaunchKernelGGL(fuse_window_kernel<true>, dim3(plvs::ceil_div(n_pairs, 4)), dim3(256), 0, stream, st.dev, dtab, FP, th, fronts, rec);
+  } else {
+    hipLaunchKernelGGL(fuse_window_kernel<false>, dim3(plvs::ceil_div(n_pairs, 4)), dim3(256), 0, stream, st.dev, dtab, FP, th, nullptr, rec);
+  }
+  PLVS_KERNEL_CHECK();
+  ++st_launches;
+  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
+  guard.armed = false;
+
+  for (int k = 0; k < n_kfs; ++k)
+    for (int i = 0; i < m; ++i) {
+      const size_t pair = (size_t)k * m + i;
+      const int2 r = rec[pair];
+      fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
+      if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, by the host entry's code
+        res = host_pair(kfs[k], tab[k].k, grids[k], P, i, th);
+        ++st_host;
+      }
+      out.put(pair, res);
+      if (res.reached >= fp::kEmptyWindow) ++st_windows;
+    }
+  post_stats();
+  return PLVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plvs_hip_orb_fuse_search(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
+                             int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream) {
+  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  if (n_kfs == 0 || P->m == 0) return PLVS_OK;
+  return run_device(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats, static_cast<hipStream_t>(stream), stream == nullptr);
+}
+
+int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
+                                  int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
+  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  int windows = 0;
+  if (n_kfs > 0 && P->m > 0) host_all(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, &windows);
+  if (stats) { stats[0] = 0; stats[1] = windows; stats[2] = 0; }
+  return PLVS_OK;
+}
+
+void plvs_hip_orb_fuse_test_chained(int mode) { g_chained = (mode == 1 || mode == 2) ? mode : 0; }
+
+}  // extern "C"

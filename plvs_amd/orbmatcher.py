@@ -187,3 +187,94 @@ def _search_bow(self, kf_featvec, kf_desc, kf_valid, kf_angle, f_featvec, f_desc
 
 
 ORBmatcher.SearchByBoW = _search_bow
+
+
+# ---- ORBmatcher::Fuse, the search stage: K key frames x M map points in one call (include/plvs_hip.h)
+FUSE_REACHED = ("skipped", "behind", "outside", "too_near", "too_far", "view_angle", "empty_window", "no_candidate",
+                "above_th_low", "candidate")
+CAMERA_PINHOLE = 0
+
+
+class _FuseKeyFrameC(ctypes.Structure):
+    _fields_ = [("view", _FrameViewC), ("inv_level_sigma2", _vp), ("n_levels", ctypes.c_int32), ("log_scale_factor", _f),
+                ("n_cameras", ctypes.c_int32), ("camera_model", ctypes.c_int32), ("K4", _vp), ("mbf", _f), ("bounds4", _vp),
+                ("q_cw", _vp), ("tcw", _vp), ("Ow", _vp)]
+
+
+class _FusePointsC(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int32), ("pos", _vp), ("normal", _vp), ("min_dist", _vp), ("max_dist", _vp), ("desc", _vp)]
+
+
+@dataclass
+class FuseKeyFrame:
+    """What Fuse reads of one pKF (NLeft == -1)."""
+    view: FrameView               # mvKeysUn, mvuRight, mDescriptors, the grid constants, mvScaleFactors
+    inv_level_sigma2: np.ndarray  # mvInvLevelSigma2
+    log_scale_factor: float       # mfLogScaleFactor
+    K4: np.ndarray                # fx, fy, cx, cy
+    mbf: float
+    bounds4: np.ndarray           # mnMinX, mnMaxX, mnMinY, mnMaxY
+    q_cw: np.ndarray              # GetPose(): quaternion x, y, z, w
+    tcw: np.ndarray
+    Ow: np.ndarray                # GetCameraCenter()
+    n_cameras: int = 1
+    camera_model: int = CAMERA_PINHOLE
+
+    def as_c(self):
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        self._keep = [f32(self.inv_level_sigma2), f32(self.K4), f32(self.bounds4), f32(self.q_cw), f32(self.tcw), f32(self.Ow)]
+        k = self._keep
+        return _FuseKeyFrameC(self.view.as_c(), _lib.np_ptr(k[0]), len(k[0]), self.log_scale_factor, self.n_cameras,
+                              self.camera_model, _lib.np_ptr(k[1]), self.mbf, _lib.np_ptr(k[2]), _lib.np_ptr(k[3]),
+                              _lib.np_ptr(k[4]), _lib.np_ptr(k[5]))
+
+
+@dataclass
+class FusePoints:
+    pos: np.ndarray        # GetWorldPos() [m,3]
+    normal: np.ndarray     # GetNormal() [m,3]
+    min_dist: np.ndarray   # mfMinDistance
+    max_dist: np.ndarray   # mfMaxDistance
+    desc: np.ndarray       # GetDescriptor() [m,32]
+
+    def as_c(self):
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        self._keep = [f32(self.pos).reshape(-1, 3), f32(self.normal).reshape(-1, 3), f32(self.min_dist), f32(self.max_dist),
+                      np.ascontiguousarray(self.desc, np.uint8).reshape(-1, 32)]
+        k = self._keep
+        return _FusePointsC(len(k[2]), *[_lib.np_ptr(a) for a in k])
+
+
+def _fuse_search(self, key_frames, points, th=3.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """The search stage of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1244-1408) for every key frame of
+    `key_frames` at once.  skip [K,M]: !pMP || isBad() || IsInKeyFrame(pKF).  host=True: plvs_hip_orb_fuse_search_host (no
+    HIP call).  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [3])."""
+    kfs = (_FuseKeyFrameC * max(len(key_frames), 1))(*[kf.as_c() for kf in key_frames])
+    pc = points.as_c()
+    K, M = len(key_frames), pc.m
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+    best_idx = np.full((K, M), -7, np.int32) if outputs else None
+    best_dist = np.full((K, M), -7, np.int32) if outputs else None
+    reached = np.full((K, M), 255, np.uint8) if want_reached else None
+    stats = np.full(3, -1, np.int32)
+    args = [kfs if K else None, K, ctypes.byref(pc), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
+            _lib.np_ptr(reached), _lib.np_ptr(stats)]
+    if host:
+        f = _lib.lib.plvs_hip_orb_fuse_search_host
+        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]
+    else:
+        f = _lib.lib.plvs_hip_orb_fuse_search
+        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]
+        args.append(stream)
+    _lib.check(f(*args))
+    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+
+
+ORBmatcher.FuseSearch = _fuse_search
+
+
+def fuse_test_chained(on):
+    """Test / measurement hook: see plvs_hip_orb_fuse_test_chained."""
+    _lib.lib.plvs_hip_orb_fuse_test_chained.argtypes = [_i]
+    _lib.lib.plvs_hip_orb_fuse_test_chained.restype = None
+    _lib.lib.plvs_hip_orb_fuse_test_chained(int(on))
