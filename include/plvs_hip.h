@@ -1713,6 +1713,87 @@ int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, cons
  * with mode 2, the staging and the copy in alone (nothing launched, the outputs untouched); 0: back to normal. */
 void plvs_hip_orb_fuse_test_chained(int mode);
 
+/* ------------------------------------------------- LineMatcher::Fuse, the search stage, K key frames x M lines in one call
+ * LineMatcher::Fuse(pKF, vpMapLines, th, bRight = false) (src/LineMatcher.cc:2043-2276) up to the choice of bestIdx, for every
+ * key frame LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1434-1470) would call it with: one copy in, one launch, one
+ * device wait.  Single-camera pinhole key frames only (NlinesLeft == -1, no mpCamera2, bRight == false): any other request is
+ * refused with PLVS_ERR_INVALID_ARG before anything is launched.  The map mutation behind bestDist <= TH_LOW (:2279-2306:
+ * Replace, AddObservation, AddMapLine) stays the caller's; LineMatcher::TH_LOW is 60.  All arrays are host memory. */
+typedef struct plvs_line_fuse_keyframe {
+  plvs_line_frame_view view;       /* Nlines, mvKeyLinesUn, mLineDescriptors, mvuRightLineStart / End (NULL = empty), mbf,        */
+                                   /* mvLineScaleFactors, mvLineInvLevelSigma2 (n_levels each); max_diag = the FRAME's float      */
+                                   /* mnMaxDiag the key frame was made from: the grid (PosLineInGrid) and mfLineGridElementDInv   */
+                                   /* come from it, the key frame's own int mnMaxDiag is its truncation                           */
+  float line_log_scale_factor;     /* mfLineLogScaleFactor                                                                        */
+  int32_t n_line_levels;           /* mnLineScaleLevels, 1 .. 64, == view.n_levels; every octave lies in [0, n_line_levels)       */
+  int32_t n_cameras;               /* 1                                                                                           */
+  int32_t camera_model;            /* PLVS_CAMERA_PINHOLE                                                                         */
+  const float* K4;                 /* mpCamera's linear parameters fx, fy, cx, cy (projectLinear)                                 */
+  const float* bounds4;            /* mnMinX, mnMaxX, mnMinY, mnMaxY (ProjectLineWithCheck: < min || > max); int in the key frame */
+  const float* Rcw;                /* GetPose().rotationMatrix() as Eigen::Matrix3f lays it out: 9, column-major                  */
+  const float* tcw;                /* its translation, 3                                                                          */
+  const float* Ow;                 /* GetCameraCenter(), 3                                                                        */
+} plvs_line_fuse_keyframe;
+/* start / end = GetWorldEndPoints() (3 m each), normal = GetNormal() (3 m), max_dist = mfMaxDistance, raw (the band is
+ * 0.8f * max .. 1.2f * max, src/MapLine.cc:707-719), desc = GetDescriptor() (m x 32). */
+typedef struct plvs_fuse_lines {
+  int32_t m;
+  const float* start;
+  const float* end;
+  const float* normal;
+  const float* max_dist;
+  const uint8_t* desc;
+} plvs_fuse_lines;
+/* reached[k * m + i]: the `continue` pair (key frame k, line i) left by — of Fuse, or the `return false` of
+ * LineProjection::ProjectLineWithCheck (include/LineProjection.h:144-264) */
+#define PLVS_LINE_FUSE_SKIPPED 0         /* skip[k * m + i] != 0: !pML || isBad() || IsInKeyFrame(pKF) at the time of the call   */
+#define PLVS_LINE_FUSE_MIDDLE_BEHIND 1   /* p3DMcZ < 0.0f                                                                        */
+#define PLVS_LINE_FUSE_MIDDLE_OUTSIDE 2  /* uM / vM outside mnMinX .. mnMaxY (a NaN passes)                                      */
+#define PLVS_LINE_FUSE_TOO_NEAR 3        /* distMiddlePoint < 0.8f * mfMaxDistance                                               */
+#define PLVS_LINE_FUSE_TOO_FAR 4         /* distMiddlePoint > 1.2f * mfMaxDistance                                               */
+#define PLVS_LINE_FUSE_END_BEHIND 5      /* p3DScZ < 0.0f or p3DEcZ < 0.0f                                                       */
+#define PLVS_LINE_FUSE_END_OUTSIDE 6     /* the start's or the end's projection outside the bounds                               */
+#define PLVS_LINE_FUSE_VIEW_ANGLE 7      /* PO.dot(Pn) < 0.5 * distMiddlePoint                                                   */
+#define PLVS_LINE_FUSE_DEGENERATE 8      /* undefined in the reference: distMiddlePoint == 0 (no level), or projected end points */
+                                         /* that coincide in f32 (theta a NaN, the cell an int cast of it); never a candidate    */
+#define PLVS_LINE_FUSE_EMPTY_WINDOW 9    /* GetLineFeaturesInArea returned nothing                                               */
+#define PLVS_LINE_FUSE_NO_CANDIDATE 10   /* nobody passed the level band and the gates (bestDist stayed 256)                     */
+#define PLVS_LINE_FUSE_ABOVE_TH_LOW 11   /* bestDist > TH_LOW (60)                                                               */
+#define PLVS_LINE_FUSE_CANDIDATE 12      /* bestDist <= TH_LOW: :2279-2306 is the caller's                                       */
+/* kfs: n_kfs key frames; skip: n_kfs x m, NULL = none.  th: [0, 1e6].  Outputs, n_kfs x m each: best_idx = the reference's
+ * bestIdx where bestDist <= TH_LOW, -1 otherwise; best_dist = bestDist there, -1 otherwise; reached (may be NULL) as above.
+ * stats (3 entries, may be NULL): pairs the host decided — the level needs its logarithm or theta its arctangent, they went
+ * through plvs_hip_line_fuse_search_host's code after the wait —, pairs that reached the window (every test passed),
+ * launches (1).  n_kfs == 0, m == 0, no key frame with key lines or every pair skipped: nothing is launched, PLVS_OK, every pair
+ * reported.  A pair whose theta interval is wider than pi (deltaTheta above pi / 2: the reference prints an error and leaves
+ * the process): PLVS_ERR_INVALID_ARG with that reason, no output written.  NULL best_idx / best_dist: refused.  stream: a
+ * hipStream_t, NULL = the calling thread's staging stream; the call waits for it before it returns. */
+int plvs_hip_line_fuse_search(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip,
+                              float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream);
+/* The same on the host, serially, with no HIP call: for callers that re-query a handful of pairs with live descriptors
+ * (the replay) and for machines without a device.  stats[0] = 0, stats[2] = 0. */
+int plvs_hip_line_fuse_search_host(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip,
+                                   float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats);
+
+/* ------------------------------------------------- both halves of SearchInNeighbors' search in one call, after ONE wait
+ * plvs_hip_orb_fuse_search and plvs_hip_line_fuse_search on the arguments of both (src/LocalMapping.cc:1372-1410 and :1434-1470,
+ * the forward direction; the back direction, :1410 / :1469, is one more call with the current key frame alone): the calling
+ * thread's staging block holds both kinds' inputs — both parts are sized first and the block reserved once —, one host-to-device
+ * copy, the two kernels back to back on the same stream, one device wait, then each kind's host pass.  The two kinds read
+ * disjoint data.  Every output equals the separate entry's.  points == NULL or lines == NULL: that kind is absent, its
+ * arguments are not looked at and the call is the other entry (both NULL: refused).  Both kinds' refusals come before anything
+ * is launched or written; a theta interval wider than pi, found after the wait, refuses the call with no LINE output written
+ * (the point outputs are then already in place).  point_stats / line_stats: as stats of the two entries (3 entries each, may be
+ * NULL).  stats (2 entries, may be NULL): launches of the call (2 with both kinds on the device), device waits (1; 0 when
+ * nothing was launched). */
+int plvs_hip_fuse_search_points_and_lines(const plvs_fuse_keyframe* point_kfs, int n_point_kfs, const plvs_fuse_points* points,
+                                          const uint8_t* skip_points, float th_points, int32_t* point_best_idx,
+                                          int32_t* point_best_dist, uint8_t* point_reached, int32_t* point_stats,
+                                          const plvs_line_fuse_keyframe* line_kfs, int n_line_kfs, const plvs_fuse_lines* lines,
+                                          const uint8_t* skip_lines, float th_lines, int32_t* line_best_idx,
+                                          int32_t* line_best_dist, uint8_t* line_reached, int32_t* line_stats, int32_t* stats,
+                                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

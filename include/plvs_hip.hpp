@@ -355,9 +355,69 @@ class LineMatcher {
     }
     return n;
   }
+  // The search stage of Fuse(KeyFramePtr& pKF, const vector<MapLinePtr>& vpMapLines, th, bRight = false), LineMatcher.cc:2043,
+  // for every target key frame of LocalMapping::SearchInNeighbors in one call.  skip (keyFrames.size() x vpMapLines.m, or
+  // null): !pML || isBad() || IsInKeyFrame(pKF).  bestIdx / bestDist / reached: one entry per (key frame, line), see
+  // plvs_hip.h; the mutation of :2279-2306 and its replay in the reference's order are the caller's.
+  // onHost: plvs_hip_line_fuse_search_host (no device call: the replay's re-query of a dirty line).  -> candidates found.
+  struct FuseResult {
+    std::vector<int32_t> bestIdx, bestDist;
+    std::vector<uint8_t> reached;
+    int32_t stats[3] = {0, 0, 0};
+    void prepare(size_t pairs) {   // (+ 1: the entries refuse null outputs, with nothing to report as well)
+      bestIdx.assign(pairs + 1, -1);
+      bestDist.assign(pairs + 1, -1);
+      reached.assign(pairs + 1, 0);
+    }
+    int finish(size_t pairs) {
+      bestIdx.resize(pairs);
+      bestDist.resize(pairs);
+      reached.resize(pairs);
+      int n = 0;
+      for (size_t p = 0; p < pairs; ++p) n += bestIdx[p] >= 0 ? 1 : 0;
+      return n;
+    }
+  };
+  int FuseSearch(const std::vector<plvs_line_fuse_keyframe>& keyFrames, const plvs_fuse_lines& vpMapLines, const uint8_t* skip, float th,
+                 FuseResult& result, bool onHost = false, void* stream = nullptr) const {
+    const size_t pairs = keyFrames.size() * (size_t)vpMapLines.m;
+    result.prepare(pairs);
+    const int K = (int)keyFrames.size();
+    if (onHost)
+      check(plvs_hip_line_fuse_search_host(keyFrames.data(), K, &vpMapLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                           result.reached.data(), result.stats));
+    else
+      check(plvs_hip_line_fuse_search(keyFrames.data(), K, &vpMapLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                      result.reached.data(), result.stats, stream));
+    return result.finish(pairs);
+  }
   float mfNNratio;
   bool mbCheckOrientation;
 };
+
+// Both halves of LocalMapping::SearchInNeighbors' search (ORBmatcher::FuseSearch and LineMatcher::FuseSearch) in one call with
+// ONE device wait: plvs_hip_fuse_search_points_and_lines.  stats: launches, waits.  -> candidates found, points + lines.
+inline int FuseSearchPointsAndLines(const std::vector<plvs_fuse_keyframe>& pointKeyFrames, const plvs_fuse_points& vpMapPoints,
+                                    const uint8_t* skipPoints, float thPoints, ORBmatcher::FuseResult& points,
+                                    const std::vector<plvs_line_fuse_keyframe>& lineKeyFrames, const plvs_fuse_lines& vpMapLines,
+                                    const uint8_t* skipLines, float thLines, LineMatcher::FuseResult& lines, int32_t stats[2] = nullptr,
+                                    void* stream = nullptr) {
+  const size_t pp = pointKeyFrames.size() * (size_t)vpMapPoints.m, lp = lineKeyFrames.size() * (size_t)vpMapLines.m;
+  points.bestIdx.assign(pp + 1, -1);
+  points.bestDist.assign(pp + 1, -1);
+  points.reached.assign(pp + 1, 0);
+  lines.prepare(lp);
+  check(plvs_hip_fuse_search_points_and_lines(pointKeyFrames.data(), (int)pointKeyFrames.size(), &vpMapPoints, skipPoints, thPoints,
+                                              points.bestIdx.data(), points.bestDist.data(), points.reached.data(), points.stats,
+                                              lineKeyFrames.data(), (int)lineKeyFrames.size(), &vpMapLines, skipLines, thLines,
+                                              lines.bestIdx.data(), lines.bestDist.data(), lines.reached.data(), lines.stats, stats, stream));
+  points.bestIdx.resize(pp);
+  points.bestDist.resize(pp);
+  points.reached.resize(pp);
+  int n = lines.finish(lp);
+  for (size_t p = 0; p < pp; ++p) n += points.bestIdx[p] >= 0 ? 1 : 0;
+  return n;
+}
 
 // Frame::ComputeStereoMatches: mvuRight / mvDepth of the left keypoints (-1 = none).
 inline void ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& mvKeys,

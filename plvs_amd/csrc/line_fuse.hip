@@ -1,0 +1,381 @@
+// The search stage of LineMatcher::Fuse(pKF, vpMapLines, th, bRight = false) (reference src/LineMatcher.cc:2043-2276) as
+// LocalMapping::SearchInNeighbors calls it (src/LocalMapping.cc:1434-1470): K key frames x M map lines in ONE call — one copy in,
+// one launch, one wait.  Single-camera pinhole key frames only (NlinesLeft == -1, no mpCamera2).
+//
+// A pair's result depends on nobody else's.  A wave takes one (key frame, line) pair; the projection and the tests of
+// line_fuse_pair.hpp are uniform across it and a rejected pair leaves at once; an accepted pair walks the one or two sub-windows
+// of KeyFrame::GetLineFeaturesInArea on the (theta, d) grid — the rows of a column are one contiguous CSR range — in 64-member
+// strides, every lane keeping the smallest (distance, enumeration position) it has seen; one cross-lane minimum, and lane 0 posts
+// the pair's record straight into the pinned block.  No candidate list, no spill.
+//
+// The level needs the host's logarithm (track_level.hpp) and theta the host's arctangent (line_fuse_pair.hpp): the pairs either
+// rule marks ambiguous are evaluated once more by the host entry's code after the wait, and their result is simply the host's.
+//
+// Map mutation (AddObservation, AddMapLine, Replace) stays the caller's: INTEGRATION.md has the replay.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.hpp"
+#include "fuse_jobs.hpp"
+#include "line_fuse_pair.hpp"
+
+namespace {
+
+namespace lf = plvs::linefuse;
+using lf::Front;
+using lf::KfConst;
+using lf::Member;
+
+constexpr int kMaxLevels = 64;
+constexpr int kPosBits = 23;   // a lane's key: distance (9 bits) above the enumeration position
+
+// one key frame in the staged block: the constants and where its arrays start (bytes from the block's start)
+struct KfDev {
+  KfConst k;
+  int n_members, pad;
+  unsigned long long o_mem, o_start, o_desc, o_sf, o_sig;
+};
+
+struct FuseLines {
+  const float *start, *end, *normal, *max_dist;
+  const uint4* desc;
+  const uint8_t* skip;   // n_kfs x m, or null
+  int m, n_pairs;
+};
+
+// the record a pair posts: best_idx, and best_dist (16 bits, 0xffff = -1) | reached << 16 | ambiguous << 24
+__host__ __device__ inline int2 pack(int best_idx, int best_dist, int reached, int ambiguous) {
+  return make_int2(best_idx, (best_dist & 0xffff) | (reached << 16) | (ambiguous << 24));
+}
+
+__global__ __launch_bounds__(256) void line_fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FuseLines L, float th,
+                                                               int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= L.n_pairs) return;
+  const int k = pair / L.m, i = pair - k * L.m;
+  if (L.skip && L.skip[pair]) {
+    if (lane == 0) out[pair] = pack(-1, -1, lf::kSkipped, 0);
+    return;
+  }
+  const KfDev& D = kfs[k];
+  const Front f = lf::front(D.k, L.start + 3 * (size_t)i, L.end + 3 * (size_t)i, L.normal + 3 * (size_t)i, L.max_dist[i]);
+  if (f.reached != lf::kEmptyWindow) {
+    if (lane == 0) out[pair] = pack(-1, -1, f.reached, 0);
+    return;
+  }
+  // :2124-2127 and the head of GetLineFeaturesInArea, uniform across the wave
+  const float scale = reinterpret_cast<const float*>(base + D.o_sf)[f.level];
+  const float dtheta = (float)(10 * lf::kPi / 180.f) * scale;
+  const float dd = th * 100.0f * scale;
+  const float theta = lf::theta_device(f.rep);
+  const lf::ThetaPlan plan = lf::theta_plan(D.k, theta, dtheta);
+  const int ambiguous = (f.ambiguous || plan.nested || lf::theta_ambiguous(D.k, theta, dtheta, plan)) ? 1 : 0;
+  if (ambiguous || plan.full || D.n_members == 0) {   // (the host decides; the refusal; nothing to walk)
+    if (lane == 0) out[pair] = pack(-1, -1, plan.full ? lf::kFullTheta : lf::kEmptyWindow, ambiguous);
+    return;
+  }
+  const Member* members = reinterpret_cast<const Member*>(base + D.o_mem);
+  const int* start = reinterpret_cast<const int*>(base + D.o_start);
+  const uint4* desc = reinterpret_cast<const uint4*>(base + D.o_desc);
+  const float* sig = reinterpret_cast<const float*>(base + D.o_sig);
+  const uint4 qa = L.desc[2 * (size_t)i], qb = L.desc[2 * (size_t)i + 1];
+  const lf::Rep rr = lf::right_rep(D.k, f);
+  const float dmin = f.rep.d - dd, dmax = f.rep.d + dd;
+  uint32_t best = 0xffffffffu;
+  int best_idx = -1;
+  bool gated = false;
+  uint32_t pos0 = 0;   // enumeration position of the range's first member; it runs on across the sub-windows
+  for (int s = 0; s < plan.n; ++s) {
+    const lf::Cells c = lf::leaf_cells(D.k, lf::plan_leaf(plan, s, dmin, dmax));
+    if (!c.ok) continue;
+    for (int ix = c.c0; ix <= c.c1; ++ix) {   // c0 >= 0, c1 <= kCols - 1, 0 <= r0, r1 <= kRows - 1: inside the kCols * kRows + 1 starts
+      const int a = start[ix * lf::kRows + c.r0], e = start[ix * lf::kRows + c.r1 + 1];
+      for (int j = a + lane; j < e; j += 64) {
+        const Member mb = members[j];
+        if (!lf::candidate_gate(f.rep, rr, f.level, mb, sig)) continue;
+        gated = true;
+        const uint4 ta = desc[2 * (size_t)mb.idx], tb = desc[2 * (size_t)mb.idx + 1];
+        const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
+                           __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+        const uint32_t key = (d << kPosBits) | (pos0 + (uint32_t)(j - a));
+        if (key < best) { best = key; best_idx = mb.idx; }
+      }
+      if (e > a) pos0 += (uint32_t)(e - a);
+    }
+  }
+  // one reduction: the smallest key is the first minimum in enumeration order; keys are distinct
+  uint32_t lowest = best;
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)lowest, off);
+    lowest = o < lowest ? o : lowest;
+  }
+  const unsigned long long has_gated = __ballot(gated);
+  const unsigned long long owner = __ballot(gated && best == lowest);
+  int win_idx = -1;
+  if (owner) win_idx = __shfl(best_idx, __ffsll((long long)owner) - 1);
+  if (lane == 0) {
+    int reached = lf::kEmptyWindow, idx = -1, dist = -1;
+    if (pos0 > 0) {   // vIndices is not empty
+      const int d = (int)(lowest >> kPosBits);
+      reached = !has_gated ? lf::kNoCandidate : (d <= lf::kThLow ? lf::kCandidate : lf::kAboveThLow);
+      if (reached == lf::kCandidate) { idx = win_idx; dist = d; }
+    }
+    out[pair] = pack(idx, dist, reached, 0);
+  }
+}
+
+KfConst kf_const(const plvs_line_fuse_keyframe& kf) {
+  KfConst c;
+  for (int i = 0; i < 9; ++i) c.R[i] = kf.Rcw[i];
+  for (int i = 0; i < 3; ++i) { c.t[i] = kf.tcw[i]; c.Ow[i] = kf.Ow[i]; }
+  c.fx = kf.K4[0]; c.fy = kf.K4[1]; c.cx = kf.K4[2]; c.cy = kf.K4[3];
+  c.mbf = kf.view.bf;
+  c.min_x = kf.bounds4[0]; c.max_x = kf.bounds4[1]; c.min_y = kf.bounds4[2]; c.max_y = kf.bounds4[3];
+  c.diag = (float)(int)kf.view.max_diag;                             // KeyFrame::mnMaxDiag is an int (src/KeyFrame.cc:144)
+  c.theta_inv = (float)lf::kRows / (float)M_PI;                      // mfLineGridElementThetaInv, src/Frame.cc:264
+  c.d_inv = (float)lf::kCols / (2.0f * kf.view.max_diag);            // mfLineGridElementDInv, :265
+  c.log_scale_factor = kf.line_log_scale_factor;
+  c.n_levels = kf.n_line_levels;
+  return c;
+}
+
+void make_grid(const plvs_line_fuse_keyframe& kf, const KfConst& c, lf::Grid* g) {
+  const plvs_keyline* kl = kf.view.keylines_un;
+  lf::build_grid(kf.view.n, [kl](int i) { return lf::KeyLineIn{kl[i].startPointX, kl[i].startPointY, kl[i].endPointX, kl[i].endPointY, kl[i].octave}; },
+                 kf.view.u_right_start, kf.view.u_right_end, kf.view.max_diag, c.theta_inv, c.d_inv, 0, g);
+}
+
+// the refusals of every entry: before anything is launched or written
+int check_args(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
+  PLVS_REQUIRE(n_kfs >= 0 && L && L->m >= 0, "null lines / negative size");
+  PLVS_REQUIRE(best_idx && best_dist, "null output");
+  PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
+  PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
+  PLVS_REQUIRE((long long)n_kfs * L->m <= (1ll << 30), "more than 2^30 pairs");
+  PLVS_REQUIRE(L->m == 0 || (L->start && L->end && L->normal && L->max_dist && L->desc), "null map line array");
+  for (int k = 0; k < n_kfs; ++k) {
+    const plvs_line_fuse_keyframe& kf = kfs[k];
+    PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
+                 "single-camera pinhole key frames only (NlinesLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
+    PLVS_REQUIRE(kf.K4 && kf.bounds4 && kf.Rcw && kf.tcw && kf.Ow, "null pose / camera array");
+    PLVS_REQUIRE(kf.n_line_levels >= 1 && kf.n_line_levels <= kMaxLevels && kf.n_line_levels == kf.view.n_levels && kf.view.line_scale_factors &&
+                     kf.view.line_inv_level_sigma2,
+                 "line levels outside [1, 64], different from the view's, or null level arrays");
+    PLVS_REQUIRE(kf.view.max_diag > 0.0f, "mnMaxDiag not positive");
+    PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key line count outside [0, 2^23)");
+    PLVS_REQUIRE((kf.view.u_right_start == nullptr) == (kf.view.u_right_end == nullptr), "one of mvuRightLineStart / End without the other");
+    if (kf.view.n > 0) {
+      PLVS_REQUIRE(kf.view.keylines_un && kf.view.descriptors, "null key frame array");
+      for (int i = 0; i < kf.view.n; ++i)
+        PLVS_REQUIRE(kf.view.keylines_un[i].octave >= 0 && kf.view.keylines_un[i].octave < kf.n_line_levels,
+                     "octave of a key line outside the key frame's levels");
+    }
+  }
+  return PLVS_OK;
+}
+
+lf::Result host_pair(const plvs_line_fuse_keyframe& kf, const KfConst& c, const lf::Grid& grid, const plvs_fuse_lines* L, int i, float th) {
+  const lf::KfGrid G{grid.start.data(), grid.members.data(), kf.view.descriptors, kf.view.line_scale_factors, kf.view.line_inv_level_sigma2};
+  return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
+                       th, 0, 0);
+}
+
+const char* const kFullThetaMessage =
+    "GetLineFeaturesInArea: search over the full theta interval (deltaTheta above pi / 2: the reference terminates here)";
+
+// One call's line search as a part of the staging block (fuse_jobs.hpp)
+struct LinePart : plvs::fusejob::Part {
+  const plvs_line_fuse_keyframe* kfs;
+  int n_kfs;
+  const plvs_fuse_lines* L;
+  const uint8_t* skip;
+  float th;
+  int32_t *best_idx, *best_dist;
+  uint8_t* reached;
+  int32_t* stats;
+
+  std::vector<lf::Grid> grids;
+  std::vector<KfDev> tab;
+  std::vector<lf::Result> results;
+  size_t o_tab = 0, o_start = 0, o_end = 0, o_nrm = 0, o_maxd = 0, o_desc = 0, o_skip = 0;   // from the part's inputs
+  size_t in_at = 0, out_at = 0;                                                              // the part's places in the block
+  int st_host = 0;
+
+  LinePart(const plvs_line_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_, float th_, int32_t* best_idx_,
+           int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
+      : kfs(kfs_), n_kfs(n_kfs_), L(L_), skip(skip_), th(th_), best_idx(best_idx_), best_dist(best_dist_), reached(reached_), stats(stats_) {}
+
+  size_t n_pairs() const { return (size_t)n_kfs * L->m; }
+
+  void prepare() override {
+    const int m = L->m;
+    grids.resize((size_t)n_kfs);
+    tab.resize((size_t)n_kfs);
+    bool any_lines = false;
+    for (int k = 0; k < n_kfs; ++k) {
+      tab[k].k = kf_const(kfs[k]);
+      make_grid(kfs[k], tab[k].k, &grids[k]);
+      tab[k].n_members = (int)grids[k].members.size();
+      tab[k].pad = 0;
+      any_lines = any_lines || kfs[k].view.n > 0;
+    }
+    // anything for the device?  a pair that is not skipped, and a key frame that has key lines
+    bool work = false;
+    if (any_lines && m > 0) {
+      if (!skip) work = true;
+      for (size_t p = 0; !work && p < n_pairs(); ++p) work = !skip[p];
+    }
+    device = work;
+    if (!device) return;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
+    o_start = take(sizeof(float) * 3 * (size_t)m); o_end = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
+    o_maxd = take(sizeof(float) * (size_t)m); o_desc = take((size_t)m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    for (int k = 0; k < n_kfs; ++k) {
+      KfDev& D = tab[k];
+      D.o_mem = take(sizeof(Member) * (size_t)D.n_members);
+      D.o_start = take(D.n_members ? sizeof(int) * grids[k].start.size() : 0);
+      D.o_desc = take(D.n_members ? (size_t)kfs[k].view.n * 32 : 0);
+      D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_line_levels);
+      D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_line_levels);
+    }
+    in_bytes = at;
+    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
+  }
+
+  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
+    in_at = in_at_;
+    out_at = out_at_;
+    const int m = L->m;
+    char* p = pinned + in_at;
+    std::vector<KfDev> abs_tab = tab;   // the kernel reads a key frame's arrays at offsets from the BLOCK's start
+    for (KfDev& D : abs_tab) { D.o_mem += in_at; D.o_start += in_at; D.o_desc += in_at; D.o_sf += in_at; D.o_sig += in_at; }
+    memcpy(p + o_tab, abs_tab.data(), sizeof(KfDev) * (size_t)n_kfs);
+    memcpy(p + o_start, L->start, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_end, L->end, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_nrm, L->normal, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_maxd, L->max_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_desc, L->desc, (size_t)m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+    for (int k = 0; k < n_kfs; ++k) {
+      const KfDev& D = tab[k];
+      const plvs_line_fuse_keyframe& kf = kfs[k];
+      if (D.n_members) {
+        memcpy(p + D.o_mem, grids[k].members.data(), sizeof(Member) * (size_t)D.n_members);
+        memcpy(p + D.o_start, grids[k].start.data(), sizeof(int) * grids[k].start.size());
+        memcpy(p + D.o_desc, kf.view.descriptors, (size_t)kf.view.n * 32);
+      }
+      memcpy(p + D.o_sf, kf.view.line_scale_factors, sizeof(float) * (size_t)kf.n_line_levels);
+      memcpy(p + D.o_sig, kf.view.line_inv_level_sigma2, sizeof(float) * (size_t)kf.n_line_levels);
+    }
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FuseLines FL{reinterpret_cast<const float*>(d + o_start), reinterpret_cast<const float*>(d + o_end),
+                       reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
+                       reinterpret_cast<const uint4*>(d + o_desc), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                       L->m, (int)n_pairs()};
+    hipLaunchKernelGGL(line_fuse_window_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream, dev,
+                       reinterpret_cast<const KfDev*>(d + o_tab), FL, th, reinterpret_cast<int2*>(pinned + out_at));
+    PLVS_KERNEL_CHECK();
+    ++launches;
+    return PLVS_OK;
+  }
+
+  void host_all() override {
+    const int m = L->m;
+    results.resize(n_pairs());
+    for (int k = 0; k < n_kfs; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        results[pair] = (skip && skip[pair]) ? lf::Result{-1, -1, lf::kSkipped} : host_pair(kfs[k], tab[k].k, grids[k], L, i, th);
+      }
+  }
+
+  void collect(const char* pinned) override {
+    const int m = L->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    results.resize(n_pairs());
+    lf::Result* res_out = results.data();
+    int host = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const int2 r = rec[pair];
+        lf::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
+        if ((r.y >> 24) & 1) {   // the level or theta is the host's to decide: the pair once more, by the host entry's code
+          res = host_pair(kfs[k], tab[k].k, grids[k], L, i, th);
+          ++host;
+        }
+        res_out[pair] = res;
+      }
+    st_host += host;
+  }
+
+  // nothing is written when a pair asks for the full theta interval
+  int refused() override {
+    for (const lf::Result& r : results)
+      if (r.reached == lf::kFullTheta) {
+        plvs::set_error("invalid argument: %s", kFullThetaMessage);
+        return PLVS_ERR_INVALID_ARG;
+      }
+    return PLVS_OK;
+  }
+
+  void post() override {
+    int windows = 0;
+    for (size_t p = 0; p < results.size(); ++p) {
+      best_idx[p] = results[p].best_idx;
+      best_dist[p] = results[p].best_dist;
+      if (reached) reached[p] = (uint8_t)results[p].reached;
+      if (results[p].reached >= lf::kEmptyWindow) ++windows;
+    }
+    if (stats) { stats[0] = st_host; stats[1] = windows; stats[2] = launches; }
+  }
+};
+
+}  // namespace
+
+int plvs::fusejob::make_line_part(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
+                                  int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {
+  out->reset();
+  const int rc = check_args(kfs, n_kfs, L, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  if (n_kfs > 0 && L->m > 0) out->reset(new LinePart(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
+  return PLVS_OK;
+}
+
+extern "C" {
+
+int plvs_hip_line_fuse_search(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
+                              int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream) {
+  std::unique_ptr<plvs::fusejob::Part> part;
+  const int rc = plvs::fusejob::make_line_part(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  if (!part) return PLVS_OK;
+  return plvs::fusejob::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+}
+
+int plvs_hip_line_fuse_search_host(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
+                                   int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
+  std::unique_ptr<plvs::fusejob::Part> part;
+  const int rc = plvs::fusejob::make_line_part(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  if (!part) return PLVS_OK;
+  part->prepare();
+  part->device = false;
+  part->host_all();
+  const int refused = part->refused();
+  if (refused != PLVS_OK) return refused;
+  part->post();
+  return PLVS_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fuse_jobs.hpp"
 #include "fuse_pair.hpp"
 #include "orb_window.hpp"
 
@@ -202,142 +203,172 @@ void host_all(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* 
   }
 }
 
-struct StreamGuard {   // no call leaves with its kernel still writing into the thread's staging block
-  hipStream_t s;
-  bool armed = false;
-  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
-};
-
 // test / measurement hook.  1: the projection in a launch of its own in front of the windows; 2: the copy in alone
 thread_local int g_chained = 0;
 
-int run_device(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th, const Outputs& out,
-               int32_t* stats, hipStream_t stream, bool own_stream) {
-  const int m = P->m;
-  const size_t n_pairs = (size_t)n_kfs * m;
-  int st_host = 0, st_windows = 0, st_launches = 0;
-  auto post_stats = [&]() {
-    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = st_launches; }
-  };
-  // anything for the device?  a pair that is not skipped, in a key frame that has key points
-  bool work = false;
-  for (int k = 0; k < n_kfs && !work; ++k) {
-    if (kfs[k].view.n == 0) continue;
-    if (!skip) { work = m > 0; continue; }
-    for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
-  }
-  if (!work) {   // nothing launched: every pair is still reported (a key frame without key points: the tests, then an empty window)
-    host_all(kfs, n_kfs, P, skip, th, out, &st_windows);
-    post_stats();
-    return PLVS_OK;
-  }
+// One call's point search as a part of the staging block (fuse_jobs.hpp):
+// [key-frame table | points | every key frame's members, cell starts, u_right, descriptors, levels] copied in one piece,
+// [fronts (chained layout), HBM only], [records, posted into the pinned side]
+struct PointPart : plvs::fusejob::Part {
+  const plvs_fuse_keyframe* kfs;
+  int n_kfs;
+  const plvs_fuse_points* P;
+  const uint8_t* skip;
+  float th;
+  Outputs out;
+  int32_t* stats;
+  int chained;
 
-  // ---- one staged block: [key-frame table | points | every key frame's members, cell starts, u_right, descriptors, levels]
-  // copied in one piece, [fronts (chained layout), HBM only], [records, posted into the pinned side]
   std::vector<FrameGrid> grids;
-  grids.reserve((size_t)n_kfs);
-  for (int k = 0; k < n_kfs; ++k) grids.emplace_back(&kfs[k].view);
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
-  const size_t o_pos = take(sizeof(float) * 3 * (size_t)m), o_nrm = take(sizeof(float) * 3 * (size_t)m);
-  const size_t o_mind = take(sizeof(float) * (size_t)m), o_maxd = take(sizeof(float) * (size_t)m), o_pd = take((size_t)m * 32);
-  const size_t o_skip = take(skip ? n_pairs : 0);
-  std::vector<KfDev> tab((size_t)n_kfs);
-  for (int k = 0; k < n_kfs; ++k) {
-    KfDev& D = tab[k];
-    D.k = kf_const(kfs[k]);
-    D.n = kfs[k].view.n;
-    D.pad = 0;
-    D.o_mem = take(sizeof(FrameGrid::Member) * (size_t)D.n);
-    D.o_start = take(D.n ? sizeof(int) * grids[k].start.size() : 0);
-    D.o_ur = take(sizeof(float) * (size_t)D.n);
-    D.o_desc = take((size_t)D.n * 32);
-    D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_levels);
-    D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_levels);
-  }
-  const size_t in_end = at;
-  const size_t o_front = take(g_chained == 1 ? sizeof(Front) * n_pairs : 0);
-  const size_t o_out = take(sizeof(int2) * n_pairs);
-  plvs::HostStage& st = plvs::thread_stage();
-  PLVS_HIP_TRY(st.reserve(at + 16));
-  if (own_stream) stream = st.stream;
+  std::vector<KfDev> tab;
+  size_t o_tab = 0, o_pos = 0, o_nrm = 0, o_mind = 0, o_maxd = 0, o_pd = 0, o_skip = 0;   // from the part's inputs
+  size_t in_at = 0, scratch_at = 0, out_at = 0;                                           // the part's places in the block
+  int st_host = 0, st_windows = 0;
 
-  memcpy(st.pinned + o_tab, tab.data(), sizeof(KfDev) * (size_t)n_kfs);
-  memcpy(st.pinned + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
-  memcpy(st.pinned + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
-  memcpy(st.pinned + o_mind, P->min_dist, sizeof(float) * (size_t)m);
-  memcpy(st.pinned + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
-  memcpy(st.pinned + o_pd, P->desc, (size_t)m * 32);
-  if (skip) memcpy(st.pinned + o_skip, skip, n_pairs);
-  for (int k = 0; k < n_kfs; ++k) {
-    const KfDev& D = tab[k];
-    const plvs_fuse_keyframe& kf = kfs[k];
-    if (D.n) {
-      memcpy(st.pinned + D.o_mem, grids[k].members.data(), sizeof(FrameGrid::Member) * (size_t)D.n);
-      memcpy(st.pinned + D.o_start, grids[k].start.data(), sizeof(int) * grids[k].start.size());
-      memcpy(st.pinned + D.o_ur, kf.view.u_right, sizeof(float) * (size_t)D.n);
-      memcpy(st.pinned + D.o_desc, kf.view.desc, (size_t)D.n * 32);
+  PointPart(const plvs_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_, float th_, const Outputs& out_,
+            int32_t* stats_)
+      : kfs(kfs_), n_kfs(n_kfs_), P(P_), skip(skip_), th(th_), out(out_), stats(stats_), chained(g_chained) {}
+
+  size_t n_pairs() const { return (size_t)n_kfs * P->m; }
+
+  void prepare() override {
+    const int m = P->m;
+    // anything for the device?  a pair that is not skipped, in a key frame that has key points
+    bool work = false;
+    for (int k = 0; k < n_kfs && !work; ++k) {
+      if (kfs[k].view.n == 0) continue;
+      if (!skip) { work = m > 0; continue; }
+      for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
     }
-    memcpy(st.pinned + D.o_sf, kf.view.scale_factors, sizeof(float) * (size_t)kf.n_levels);
-    memcpy(st.pinned + D.o_sig, kf.inv_level_sigma2, sizeof(float) * (size_t)kf.n_levels);
+    device = work;
+    if (!device) return;
+    grids.reserve((size_t)n_kfs);
+    for (int k = 0; k < n_kfs; ++k) grids.emplace_back(&kfs[k].view);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
+    o_pos = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
+    o_mind = take(sizeof(float) * (size_t)m); o_maxd = take(sizeof(float) * (size_t)m); o_pd = take((size_t)m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    tab.resize((size_t)n_kfs);
+    for (int k = 0; k < n_kfs; ++k) {
+      KfDev& D = tab[k];
+      D.k = kf_const(kfs[k]);
+      D.n = kfs[k].view.n;
+      D.pad = 0;
+      D.o_mem = take(sizeof(FrameGrid::Member) * (size_t)D.n);
+      D.o_start = take(D.n ? sizeof(int) * grids[k].start.size() : 0);
+      D.o_ur = take(sizeof(float) * (size_t)D.n);
+      D.o_desc = take((size_t)D.n * 32);
+      D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_levels);
+      D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_levels);
+    }
+    in_bytes = at;
+    scratch_bytes = chained == 1 ? ((sizeof(Front) * n_pairs() + 15) & ~(size_t)15) : 0;
+    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
   }
-  StreamGuard guard{stream};
-  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
-  guard.armed = true;
-  if (g_chained == 2) {   // measurement only: the staging and the copy in, nothing launched, the outputs untouched
-    PLVS_HIP_TRY(hipStreamSynchronize(stream));
-    guard.armed = false;
-    post_stats();
+
+  void fill(char* pinned, size_t in_at_, size_t scratch_at_, size_t out_at_) override {
+    in_at = in_at_;
+    scratch_at = scratch_at_;
+    out_at = out_at_;
+    const int m = P->m;
+    char* p = pinned + in_at;
+    std::vector<KfDev> abs_tab = tab;   // the kernel reads a key frame's arrays at offsets from the BLOCK's start
+    for (KfDev& D : abs_tab) { D.o_mem += in_at; D.o_start += in_at; D.o_ur += in_at; D.o_desc += in_at; D.o_sf += in_at; D.o_sig += in_at; }
+    memcpy(p + o_tab, abs_tab.data(), sizeof(KfDev) * (size_t)n_kfs);
+    memcpy(p + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_mind, P->min_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_pd, P->desc, (size_t)m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+    for (int k = 0; k < n_kfs; ++k) {
+      const KfDev& D = tab[k];
+      const plvs_fuse_keyframe& kf = kfs[k];
+      if (D.n) {
+        memcpy(p + D.o_mem, grids[k].members.data(), sizeof(FrameGrid::Member) * (size_t)D.n);
+        memcpy(p + D.o_start, grids[k].start.data(), sizeof(int) * grids[k].start.size());
+        memcpy(p + D.o_ur, kf.view.u_right, sizeof(float) * (size_t)D.n);
+        memcpy(p + D.o_desc, kf.view.desc, (size_t)D.n * 32);
+      }
+      memcpy(p + D.o_sf, kf.view.scale_factors, sizeof(float) * (size_t)kf.n_levels);
+      memcpy(p + D.o_sig, kf.inv_level_sigma2, sizeof(float) * (size_t)kf.n_levels);
+    }
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FusePoints FP{reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm),
+                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const float*>(d + o_maxd),
+                        reinterpret_cast<const uint4*>(d + o_pd), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                        P->m, (int)n_pairs()};
+    const KfDev* dtab = reinterpret_cast<const KfDev*>(d + o_tab);
+    int2* rec = reinterpret_cast<int2*>(pinned + out_at);
+    if (chained == 1) {
+      Front* fronts = reinterpret_cast<Front*>(dev + scratch_at);
+      hipLaunchKernelGGL(fuse_front_kernel, dim3(plvs::ceil_div(n_pairs(), 256)), dim3(256), 0, stream, dtab, FP, fronts);
+      PLVS_KERNEL_CHECK();
+      ++launches;
+      hipLaunchKernelGGL(fuse_window_kernel<true>, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream, dev, dtab, FP, th, fronts, rec);
+    } else {
+      hipLaunchKernelGGL(fuse_window_kernel<false>, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream, dev, dtab, FP, th, nullptr, rec);
+    }
+    PLVS_KERNEL_CHECK();
+    ++launches;
     return PLVS_OK;
   }
-  const FusePoints FP{reinterpret_cast<const float*>(st.dev + o_pos), reinterpret_cast<const float*>(st.dev + o_nrm),
-                      reinterpret_cast<const float*>(st.dev + o_mind), reinterpret_cast<const float*>(st.dev + o_maxd),
-                      reinterpret_cast<const uint4*>(st.dev + o_pd), skip ? reinterpret_cast<const uint8_t*>(st.dev + o_skip) : nullptr,
-                      m, (int)n_pairs};
-  const KfDev* dtab = reinterpret_cast<const KfDev*>(st.dev + o_tab);
-  int2* rec = reinterpret_cast<int2*>(st.pinned + o_out);
-  if (g_chained == 1) {
-    Front* fronts = reinterpret_cast<Front*>(st.dev + o_front);
-    hipLaunchKernelGGL(fuse_front_kernel, dim3(plvs::ceil_div(n_pairs, 256)), dim3(256), 0, stream, dtab, FP, fronts);
-    PLVS_KERNEL_CHECK();
-    ++st_launches;
-    hipLaunchKernelGGL(fuse_window_kernel<true>, dim3(plvs::ceil_div(n_pairs, 4)), dim3(256), 0, stream, st.dev, dtab, FP, th, fronts, rec);
-  } else {
-    hipLaunchKernelGGL(fuse_window_kernel<false>, dim3(plvs::ceil_div(n_pairs, 4)), dim3(256), 0, stream, st.dev, dtab, FP, th, nullptr, rec);
-  }
-  PLVS_KERNEL_CHECK();
-  ++st_launches;
-  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
-  guard.armed = false;
 
-  for (int k = 0; k < n_kfs; ++k)
-    for (int i = 0; i < m; ++i) {
-      const size_t pair = (size_t)k * m + i;
-      const int2 r = rec[pair];
-      fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
-      if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, by the host entry's code
-        res = host_pair(kfs[k], tab[k].k, grids[k], P, i, th);
-        ++st_host;
+  // nothing launched: every pair is still reported (a key frame without key points: the tests, then an empty window)
+  void host_all() override { ::host_all(kfs, n_kfs, P, skip, th, out, &st_windows); }
+
+  void collect(const char* pinned) override {
+    const int m = P->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    const Outputs o = out;            // (locals: the stores through the output pointers may alias this object's members)
+    int host = 0, windows = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const int2 r = rec[pair];
+        fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
+        if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, by the host entry's code
+          res = host_pair(kfs[k], tab[k].k, grids[k], P, i, th);
+          ++host;
+        }
+        o.put(pair, res);
+        if (res.reached >= fp::kEmptyWindow) ++windows;
       }
-      out.put(pair, res);
-      if (res.reached >= fp::kEmptyWindow) ++st_windows;
-    }
-  post_stats();
-  return PLVS_OK;
-}
+    st_host += host;
+    st_windows += windows;
+  }
+
+  void post() override {
+    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = launches; }
+  }
+};
 
 }  // namespace
+
+int plvs::fusejob::make_point_part(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
+                                   int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {
+  out->reset();
+  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  if (n_kfs > 0 && P->m > 0) out->reset(new PointPart(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
+  return PLVS_OK;
+}
 
 extern "C" {
 
 int plvs_hip_orb_fuse_search(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
                              int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream) {
-  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
+  std::unique_ptr<plvs::fusejob::Part> part;
+  const int rc = plvs::fusejob::make_point_part(kfs, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, &part);
   if (rc != PLVS_OK) return rc;
   if (stats) stats[0] = stats[1] = stats[2] = 0;
-  if (n_kfs == 0 || P->m == 0) return PLVS_OK;
-  return run_device(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats, static_cast<hipStream_t>(stream), stream == nullptr);
+  if (!part) return PLVS_OK;
+  return plvs::fusejob::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, g_chained == 2, nullptr, nullptr);
 }
 
 int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,

@@ -3,6 +3,7 @@
 functions read: LBD descriptors [n,32] u8, mvKeyLinesUn[i].angle (radians), .octave, and the validity of
 the map line attached to each query line."""
 import ctypes
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -127,3 +128,119 @@ class LineMatcher:
         matches = np.zeros(k, np.dtype([("queryIdx", np.int32), ("trainIdx", np.int32), ("distance", np.float32)]))
         matches["queryIdx"], matches["trainIdx"], matches["distance"] = mq[:k], mt[:k], md[:k]
         return n.value, matches, mv[:k].astype(bool)
+
+
+# ---- LineMatcher::Fuse, the search stage: K key frames x M map lines in one call (include/plvs_hip.h)
+LINE_FUSE_REACHED = ("skipped", "middle_behind", "middle_outside", "too_near", "too_far", "end_behind", "end_outside", "view_angle",
+                     "degenerate", "empty_window", "no_candidate", "above_th_low", "candidate")
+CAMERA_PINHOLE = 0
+
+
+class _LineFuseKeyFrameC(ctypes.Structure):
+    _fields_ = [("view", LineFrameView), ("line_log_scale_factor", _f), ("n_line_levels", ctypes.c_int32),
+                ("n_cameras", ctypes.c_int32), ("camera_model", ctypes.c_int32), ("K4", _vp), ("bounds4", _vp), ("Rcw", _vp),
+                ("tcw", _vp), ("Ow", _vp)]
+
+
+class _FuseLinesC(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int32), ("start", _vp), ("end", _vp), ("normal", _vp), ("max_dist", _vp), ("desc", _vp)]
+
+
+@dataclass
+class LineFuseKeyFrame:
+    """What LineMatcher::Fuse reads of one pKF (NlinesLeft == -1)."""
+    view: tuple                   # line_frame_view(...): mvKeyLinesUn, mLineDescriptors, mvuRightLineStart / End, mbf, the level
+                                  # tables, the Frame's float mnMaxDiag
+    line_log_scale_factor: float  # mfLineLogScaleFactor
+    K4: np.ndarray                # linear parameters fx, fy, cx, cy
+    bounds4: np.ndarray           # mnMinX, mnMaxX, mnMinY, mnMaxY
+    Rcw: np.ndarray               # GetPose().rotationMatrix() in Eigen's layout: 9, column-major
+    tcw: np.ndarray
+    Ow: np.ndarray                # GetCameraCenter()
+    n_cameras: int = 1
+    camera_model: int = CAMERA_PINHOLE
+
+    def as_c(self):
+        self._keep = [_f32(self.K4), _f32(self.bounds4), _f32(self.Rcw).reshape(9), _f32(self.tcw), _f32(self.Ow)]
+        k = self._keep
+        view = self.view[0]
+        return _LineFuseKeyFrameC(view, self.line_log_scale_factor, view.n_levels, self.n_cameras, self.camera_model,
+                                  *[_lib.np_ptr(a) for a in k])
+
+
+@dataclass
+class FuseLines:
+    start: np.ndarray      # GetWorldEndPoints() [m,3] each
+    end: np.ndarray
+    normal: np.ndarray     # GetNormal() [m,3]
+    max_dist: np.ndarray   # mfMaxDistance
+    desc: np.ndarray       # GetDescriptor() [m,32]
+
+    def as_c(self):
+        self._keep = [_f32(self.start).reshape(-1, 3), _f32(self.end).reshape(-1, 3), _f32(self.normal).reshape(-1, 3),
+                      _f32(self.max_dist), _u8(self.desc).reshape(-1, 32)]
+        k = self._keep
+        return _FuseLinesC(len(k[3]), *[_lib.np_ptr(a) for a in k])
+
+
+def _fuse_outputs(K, M, outputs, want_reached):
+    return (np.full((K, M), -7, np.int32) if outputs else None, np.full((K, M), -7, np.int32) if outputs else None,
+            np.full((K, M), 255, np.uint8) if want_reached else None, np.full(3, -1, np.int32))
+
+
+def _line_fuse_search(self, key_frames, lines, th=3.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """The search stage of LineMatcher::Fuse(pKF, vpMapLines, th) (src/LineMatcher.cc:2043-2276) for every key frame of
+    `key_frames` at once.  skip [K,M]: !pML || isBad() || IsInKeyFrame(pKF).  host=True: plvs_hip_line_fuse_search_host (no
+    HIP call).  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [3])."""
+    kfs = (_LineFuseKeyFrameC * max(len(key_frames), 1))(*[kf.as_c() for kf in key_frames])
+    lc = lines.as_c()
+    K, M = len(key_frames), lc.m
+    sk = None if skip is None else _u8(skip).reshape(K, M)
+    best_idx, best_dist, reached, stats = _fuse_outputs(K, M, outputs, want_reached)
+    args = [kfs if K else None, K, ctypes.byref(lc), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
+            _lib.np_ptr(reached), _lib.np_ptr(stats)]
+    if host:
+        f = _lib.lib.plvs_hip_line_fuse_search_host
+        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]
+    else:
+        f = _lib.lib.plvs_hip_line_fuse_search
+        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]
+        args.append(stream)
+    _lib.check(f(*args))
+    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+
+
+LineMatcher.FuseSearch = _line_fuse_search
+
+
+def FuseSearchPointsAndLines(point_key_frames=None, points=None, th_points=3.0, skip_points=None, line_key_frames=None, lines=None,
+                             th_lines=3.0, skip_lines=None, stream=None):
+    """Both halves of LocalMapping::SearchInNeighbors' search in one call with ONE device wait
+    (plvs_hip_fuse_search_points_and_lines): ORBmatcher.FuseSearch on (point_key_frames, points) and LineMatcher.FuseSearch on
+    (line_key_frames, lines).  points=None or lines=None: that kind is absent.
+    -> (points' dict or None, lines' dict or None, stats [2]: launches, waits)."""
+    from .orbmatcher import _FuseKeyFrameC
+    pk = lk = pc = lc = None
+    p_out = l_out = (None, None, None, None)
+    PK = LK = 0
+    psk = lsk = None
+    if points is not None:
+        PK = len(point_key_frames)
+        pk = (_FuseKeyFrameC * max(PK, 1))(*[kf.as_c() for kf in point_key_frames])
+        pc = points.as_c()
+        psk = None if skip_points is None else _u8(skip_points).reshape(PK, pc.m)
+        p_out = _fuse_outputs(PK, pc.m, True, True)
+    if lines is not None:
+        LK = len(line_key_frames)
+        lk = (_LineFuseKeyFrameC * max(LK, 1))(*[kf.as_c() for kf in line_key_frames])
+        lc = lines.as_c()
+        lsk = None if skip_lines is None else _u8(skip_lines).reshape(LK, lc.m)
+        l_out = _fuse_outputs(LK, lc.m, True, True)
+    stats = np.full(2, -1, np.int32)
+    f = _lib.lib.plvs_hip_fuse_search_points_and_lines
+    f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]
+    _lib.check(f(pk if PK else None, PK, None if pc is None else ctypes.byref(pc), _lib.np_ptr(psk), th_points, *[_lib.np_ptr(a) for a in p_out],
+                 lk if LK else None, LK, None if lc is None else ctypes.byref(lc), _lib.np_ptr(lsk), th_lines, *[_lib.np_ptr(a) for a in l_out],
+                 _lib.np_ptr(stats), stream))
+    as_dict = lambda o: dict(best_idx=o[0], best_dist=o[1], reached=o[2], stats=o[3])
+    return (None if points is None else as_dict(p_out)), (None if lines is None else as_dict(l_out)), stats
