@@ -1794,6 +1794,64 @@ int plvs_hip_fuse_search_points_and_lines(const plvs_fuse_keyframe* point_kfs, i
                                           int32_t* line_best_dist, uint8_t* line_reached, int32_t* line_stats, int32_t* stats,
                                           void* stream);
 
+/* ------------------------------------------------- key frames resident in HBM: a handle, and the three Fuse searches over handles
+ * What the searches above read of a key frame is fixed by the KeyFrame constructor, except the pose (bundle adjustment) and which
+ * features carry a map point (`skip`): a handle holds the fixed part — key points / key lines, octaves, right coordinates,
+ * descriptors, the grids, the level tables, the camera, the bounds — uploaded ONCE, and a call carries only the poses, the map
+ * points or lines, and skip.  Every result equals the non-resident entry's bit for bit. */
+typedef struct plvs_keyframe plvs_keyframe;   /* opaque */
+#define PLVS_KEYFRAME_HOST_ONLY 1u            /* no HIP call, ever: machines without a device; only the _kf_host entries take it */
+/* points / lines: the key frame as the non-resident entries take it; either may be NULL (no point side / no line side), both
+ * NULL is refused.  Checked per side exactly as those entries check a key frame (single-camera pinhole, levels in [1, 64], every
+ * octave inside the levels, n < 2^23, null arrays), before any HIP call or allocation.  The pose pointers of the two structs
+ * (q_cw, Rcw, tcw, Ow) are not read and may be NULL.  Deep copy: after the call returns every array passed may be freed or
+ * overwritten.  The handle keeps a host copy (with both grids, built here on the host) and, without PLVS_KEYFRAME_HOST_ONLY, the
+ * same bytes in ONE device allocation on the current device: one reserve of the calling thread's staging block, one copy, one
+ * wait.  A handle is immutable: any number of threads may search with it at once.  Destroying a handle while another thread's
+ * call uses it is the caller's error. */
+int plvs_hip_keyframe_create(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, uint32_t flags,
+                             plvs_keyframe** out);
+int plvs_hip_keyframe_destroy(plvs_keyframe* kf);   /* NULL: PLVS_OK */
+/* info (6 entries): key points (-1: no point side), key lines (-1: no line side), device bytes (0: host only), host bytes, flags,
+ * device id (-1: host only) */
+int plvs_hip_keyframe_info(const plvs_keyframe* kf, int64_t* info);
+/* What changes after creation: GetPose() / GetCameraCenter() at the time of the call. */
+typedef struct plvs_keyframe_pose {
+  float q_cw[4];   /* unit_quaternion().coeffs(): x, y, z, w — the point search projects by the quaternion's action            */
+  float Rcw[9];    /* rotationMatrix() as Eigen::Matrix3f lays it out, column-major — the line search projects by the matrix   */
+  float tcw[3];
+  float Ow[3];
+} plvs_keyframe_pose;
+/* plvs_hip_orb_fuse_search / plvs_hip_line_fuse_search / plvs_hip_fuse_search_points_and_lines with key frame k = (kfs[k],
+ * poses[k]); the same handle may be listed more than once, with different poses.  The combined entry takes ONE key-frame list
+ * for both kinds.  The call's one host-to-device copy holds the per-call table (pose, constants and device pointers of each
+ * listed key frame), the map points or lines, and skip — nothing of a key frame.  Outputs, skip, th, stream, the launch-free
+ * shapes and the theta refusal: as the non-resident entries.  stats of the single-kind entries and point_stats / line_stats: 4
+ * entries (may be NULL), the non-resident entry's three and [3] = the bytes this kind put into the call's copy in (0: nothing
+ * launched).  stats of the combined entry: 3 entries (may be NULL), launches, device waits, bytes of the copy in.  Refused, before
+ * anything is launched or written, besides what the non-resident entries refuse: a NULL handle, a handle without the side the
+ * call needs, a PLVS_KEYFRAME_HOST_ONLY handle (before any HIP call), a handle created on another device than the current one. */
+int plvs_hip_orb_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
+                                const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached,
+                                int32_t* stats, void* stream);
+int plvs_hip_line_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
+                                 const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached,
+                                 int32_t* stats, void* stream);
+int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
+                                             const plvs_fuse_points* points, const uint8_t* skip_points, float th_points,
+                                             int32_t* point_best_idx, int32_t* point_best_dist, uint8_t* point_reached,
+                                             int32_t* point_stats, const plvs_fuse_lines* lines, const uint8_t* skip_lines,
+                                             float th_lines, int32_t* line_best_idx, int32_t* line_best_dist,
+                                             uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream);
+/* The same on the host copy, serially, with no HIP call (PLVS_KEYFRAME_HOST_ONLY handles and others alike): the replay's re-query,
+ * machines without a device.  stats[0] = stats[2] = stats[3] = 0. */
+int plvs_hip_orb_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
+                                     const plvs_fuse_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                     uint8_t* reached, int32_t* stats);
+int plvs_hip_line_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
+                                      const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                      uint8_t* reached, int32_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -419,6 +419,122 @@ inline int FuseSearchPointsAndLines(const std::vector<plvs_fuse_keyframe>& point
   return n;
 }
 
+// A key frame resident in HBM (plvs_keyframe): what the Fuse searches read of a KeyFrame that its constructor fixes, copied once.
+// Create it where the KeyFrame constructor ends, let it go with the key frame (or on SetBadFlag); the pose travels with each call
+// (nothing to do on SetPose).  Move-only; immutable, so any number of threads may search with it; destroying it while another
+// thread's call uses it is the caller's error.  hostOnly: no device call, ever (the onHost searches alone take such a handle).
+class KeyFrameHandle {
+ public:
+  KeyFrameHandle() = default;
+  KeyFrameHandle(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, bool hostOnly = false) {
+    check(plvs_hip_keyframe_create(points, lines, hostOnly ? PLVS_KEYFRAME_HOST_ONLY : 0u, &h_));
+  }
+  ~KeyFrameHandle() { reset(); }
+  KeyFrameHandle(KeyFrameHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  KeyFrameHandle& operator=(KeyFrameHandle&& o) noexcept {
+    if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+    return *this;
+  }
+  KeyFrameHandle(const KeyFrameHandle&) = delete;
+  KeyFrameHandle& operator=(const KeyFrameHandle&) = delete;
+  void reset() {
+    if (h_) (void)plvs_hip_keyframe_destroy(h_);
+    h_ = nullptr;
+  }
+  const plvs_keyframe* get() const { return h_; }
+  explicit operator bool() const { return h_ != nullptr; }
+  // key points (-1: none), key lines (-1: none), device bytes, host bytes, flags, device id
+  struct Info { int64_t nPoints, nLines, deviceBytes, hostBytes, flags, device; };
+  Info info() const {
+    int64_t v[6];
+    check(plvs_hip_keyframe_info(h_, v));
+    return Info{v[0], v[1], v[2], v[3], v[4], v[5]};
+  }
+
+ private:
+  plvs_keyframe* h_ = nullptr;
+};
+
+namespace detail {
+inline std::vector<const plvs_keyframe*> raw_handles(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_pose>& poses) {
+  if (keyFrames.size() != poses.size()) throw std::invalid_argument("FuseSearch: one pose per key frame handle");
+  std::vector<const plvs_keyframe*> raw(keyFrames.size() + 1, nullptr);
+  for (size_t k = 0; k < keyFrames.size(); ++k) raw[k] = keyFrames[k] ? keyFrames[k]->get() : nullptr;
+  return raw;
+}
+}  // namespace detail
+
+// ORBmatcher::FuseSearch / LineMatcher::FuseSearch / FuseSearchPointsAndLines over resident key frames: key frame k =
+// (keyFrames[k], poses[k]); the same handle may be listed more than once.  copyInBytes (may be null): the bytes of the call's one
+// host-to-device copy — the per-call table, the map points or lines, skip.  Results as the non-resident overloads'.
+inline int FuseSearch(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_pose>& poses,
+                      const plvs_fuse_points& vpMapPoints, const uint8_t* skip, float th, ORBmatcher::FuseResult& result, bool onHost = false,
+                      void* stream = nullptr, int32_t* copyInBytes = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpMapPoints.m;
+  result.bestIdx.assign(pairs + 1, -1);
+  result.bestDist.assign(pairs + 1, -1);
+  result.reached.assign(pairs + 1, 0);
+  int32_t st[4] = {0, 0, 0, 0};
+  if (onHost)
+    check(plvs_hip_orb_fuse_search_kf_host(raw.data(), poses.data(), K, &vpMapPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                           result.reached.data(), st));
+  else
+    check(plvs_hip_orb_fuse_search_kf(raw.data(), poses.data(), K, &vpMapPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                      result.reached.data(), st, stream));
+  for (int s = 0; s < 3; ++s) result.stats[s] = st[s];
+  if (copyInBytes) *copyInBytes = st[3];
+  result.bestIdx.resize(pairs);
+  result.bestDist.resize(pairs);
+  result.reached.resize(pairs);
+  int n = 0;
+  for (size_t p = 0; p < pairs; ++p) n += result.bestIdx[p] >= 0 ? 1 : 0;
+  return n;
+}
+inline int FuseSearch(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_pose>& poses,
+                      const plvs_fuse_lines& vpMapLines, const uint8_t* skip, float th, LineMatcher::FuseResult& result, bool onHost = false,
+                      void* stream = nullptr, int32_t* copyInBytes = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpMapLines.m;
+  result.prepare(pairs);
+  int32_t st[4] = {0, 0, 0, 0};
+  if (onHost)
+    check(plvs_hip_line_fuse_search_kf_host(raw.data(), poses.data(), K, &vpMapLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                            result.reached.data(), st));
+  else
+    check(plvs_hip_line_fuse_search_kf(raw.data(), poses.data(), K, &vpMapLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                       result.reached.data(), st, stream));
+  for (int s = 0; s < 3; ++s) result.stats[s] = st[s];
+  if (copyInBytes) *copyInBytes = st[3];
+  return result.finish(pairs);
+}
+// stats (3 entries, may be null): launches, waits, bytes of the copy in
+inline int FuseSearchPointsAndLines(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_pose>& poses,
+                                    const plvs_fuse_points& vpMapPoints, const uint8_t* skipPoints, float thPoints,
+                                    ORBmatcher::FuseResult& points, const plvs_fuse_lines& vpMapLines, const uint8_t* skipLines, float thLines,
+                                    LineMatcher::FuseResult& lines, int32_t stats[3] = nullptr, void* stream = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const size_t pp = keyFrames.size() * (size_t)vpMapPoints.m, lp = keyFrames.size() * (size_t)vpMapLines.m;
+  points.bestIdx.assign(pp + 1, -1);
+  points.bestDist.assign(pp + 1, -1);
+  points.reached.assign(pp + 1, 0);
+  lines.prepare(lp);
+  int32_t ps[4] = {0, 0, 0, 0}, ls[4] = {0, 0, 0, 0};
+  check(plvs_hip_fuse_search_points_and_lines_kf(raw.data(), poses.data(), (int)keyFrames.size(), &vpMapPoints, skipPoints, thPoints,
+                                                 points.bestIdx.data(), points.bestDist.data(), points.reached.data(), ps, &vpMapLines,
+                                                 skipLines, thLines, lines.bestIdx.data(), lines.bestDist.data(), lines.reached.data(), ls,
+                                                 stats, stream));
+  for (int s = 0; s < 3; ++s) { points.stats[s] = ps[s]; lines.stats[s] = ls[s]; }
+  points.bestIdx.resize(pp);
+  points.bestDist.resize(pp);
+  points.reached.resize(pp);
+  int n = lines.finish(lp);
+  for (size_t p = 0; p < pp; ++p) n += points.bestIdx[p] >= 0 ? 1 : 0;
+  return n;
+}
+
 // Frame::ComputeStereoMatches: mvuRight / mvDepth of the left keypoints (-1 = none).
 inline void ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& mvKeys,
                                  const std::vector<uint8_t>& mDescriptors, const std::vector<KeyPoint>& mvKeysRight,

@@ -16,10 +16,11 @@ struct StreamGuard {   // no call leaves with its kernels still writing into the
 };
 }  // namespace
 
-int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_only, int* launches, int* waits) {
+int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_only, int* launches, int* waits, size_t* copied) {
   Part* parts[2] = {a, b};
   if (launches) *launches = 0;
   if (waits) *waits = 0;
+  if (copied) *copied = 0;
   size_t in_total = 0, scratch_total = 0, out_total = 0;
   bool device = false;
   for (Part* p : parts) {
@@ -46,6 +47,7 @@ int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_o
     StreamGuard guard{stream};
     PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_total, hipMemcpyHostToDevice, stream));
     guard.armed = true;
+    if (copied) *copied = in_total;
     if (!copy_only)
       for (Part* p : parts) {
         if (!p || !p->device) continue;
@@ -69,6 +71,16 @@ int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_o
   }
   for (Part* p : parts)
     if (p) p->post();
+  return PLVS_OK;
+}
+
+int run_part_on_host(Part* p) {
+  p->prepare();
+  p->device = false;
+  p->host_all();
+  const int rc = p->refused();
+  if (rc != PLVS_OK) return rc;
+  p->post();
   return PLVS_OK;
 }
 

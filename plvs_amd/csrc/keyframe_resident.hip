@@ -1,0 +1,154 @@
+// Key frames resident in HBM (keyframe_handle.hpp): the handle's life cycle, and the three Fuse searches of
+// LocalMapping::SearchInNeighbors over handles.  A handle is created where the KeyFrame constructor ends — one reserve of the
+// calling thread's staging block, one copy, one wait — and from then on a search carries the poses, the map points or lines and
+// `skip`: the per-call grid build, staging and copy of every target key frame (76 % of the point call) are gone.  The
+// kernels are orb_fuse.hip's and line_fuse.hip's resident ones, the call is fuse_both.hip's run_parts: one reserve, one copy in, one
+// launch per kind, one wait.
+#include "fuse_jobs.hpp"
+#include "keyframe_handle.hpp"
+
+namespace fj = plvs::fusejob;
+
+int plvs::fusejob::check_handles(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, int side, bool host_entry) {
+  PLVS_REQUIRE(n_kfs == 0 || poses, "null poses");
+  for (int k = 0; k < n_kfs; ++k) {
+    PLVS_REQUIRE(kfs[k], "null key-frame handle in the list");
+    PLVS_REQUIRE(!(side & 1) || kfs[k]->pt.present, "a key-frame handle without a point side in a point search");
+    PLVS_REQUIRE(!(side & 2) || kfs[k]->ln.present, "a key-frame handle without a line side in a line search");
+  }
+  if (host_entry) return PLVS_OK;
+  for (int k = 0; k < n_kfs; ++k)
+    PLVS_REQUIRE(!(kfs[k]->flags & PLVS_KEYFRAME_HOST_ONLY), "a PLVS_KEYFRAME_HOST_ONLY handle in a device entry (the _kf_host entries take it)");
+  if (n_kfs == 0) return PLVS_OK;
+  int device = -1;
+  PLVS_HIP_TRY(hipGetDevice(&device));
+  for (int k = 0; k < n_kfs; ++k) PLVS_REQUIRE(kfs[k]->device == device, "a key-frame handle created on another device than the current one");
+  return PLVS_OK;
+}
+
+extern "C" {
+
+int plvs_hip_keyframe_create(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, uint32_t flags, plvs_keyframe** out) {
+  PLVS_REQUIRE(out, "null out");
+  *out = nullptr;
+  PLVS_REQUIRE((flags & ~PLVS_KEYFRAME_HOST_ONLY) == 0, "unknown flag");
+  PLVS_REQUIRE(points || lines, "neither a point side nor a line side");
+  if (points) {
+    const int rc = plvs::kfhandle::check_point_keyframe(*points, false);
+    if (rc != PLVS_OK) return rc;
+  }
+  if (lines) {
+    const int rc = plvs::kfhandle::check_line_keyframe(*lines, false);
+    if (rc != PLVS_OK) return rc;
+  }
+  std::unique_ptr<plvs_keyframe> h(new plvs_keyframe);
+  h->flags = flags;
+  if (points) plvs::kfhandle::stage_points(*points, h.get());
+  if (lines) plvs::kfhandle::stage_lines(*lines, h.get());
+  if (!(flags & PLVS_KEYFRAME_HOST_ONLY)) {
+    const size_t bytes = h->host.size();
+    PLVS_HIP_TRY(hipGetDevice(&h->device));
+    plvs::HostStage& st = plvs::thread_stage();
+    PLVS_HIP_TRY(st.reserve(bytes));
+    memcpy(st.pinned, h->host.data(), bytes);
+    PLVS_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->dev), bytes));
+    hipError_t e = hipMemcpyAsync(h->dev, st.pinned, bytes, hipMemcpyHostToDevice, st.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(st.stream);
+    if (e != hipSuccess) {
+      (void)hipFree(h->dev);
+      plvs::set_error("plvs_hip_keyframe_create: the copy in failed: %s", hipGetErrorString(e));
+      return PLVS_ERR_HIP;
+    }
+  }
+  *out = h.release();
+  return PLVS_OK;
+}
+
+int plvs_hip_keyframe_destroy(plvs_keyframe* kf) {
+  if (!kf) return PLVS_OK;
+  hipError_t e = hipSuccess;
+  if (kf->dev) e = hipFree(kf->dev);
+  delete kf;
+  PLVS_HIP_TRY(e);
+  return PLVS_OK;
+}
+
+int plvs_hip_keyframe_info(const plvs_keyframe* kf, int64_t* info) {
+  PLVS_REQUIRE(kf && info, "null handle / info");
+  info[0] = kf->pt.present ? kf->pt.n : -1;
+  info[1] = kf->ln.present ? kf->ln.n : -1;
+  info[2] = kf->dev ? (int64_t)kf->host.size() : 0;
+  info[3] = (int64_t)kf->host.size();
+  info[4] = kf->flags;
+  info[5] = kf->device;
+  return PLVS_OK;
+}
+
+int plvs_hip_orb_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
+                                const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
+                                void* stream) {
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, false, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!part) return PLVS_OK;
+  return fj::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+}
+
+int plvs_hip_line_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
+                                 const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
+                                 void* stream) {
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, false, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!part) return PLVS_OK;
+  return fj::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+}
+
+int plvs_hip_orb_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
+                                     const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, true, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  return part ? fj::run_part_on_host(part.get()) : PLVS_OK;
+}
+
+int plvs_hip_line_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
+                                      const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, true, &part);
+  if (rc != PLVS_OK) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  return part ? fj::run_part_on_host(part.get()) : PLVS_OK;
+}
+
+int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
+                                             const plvs_fuse_points* P, const uint8_t* skip_points, float th_points, int32_t* point_best_idx,
+                                             int32_t* point_best_dist, uint8_t* point_reached, int32_t* point_stats, const plvs_fuse_lines* L,
+                                             const uint8_t* skip_lines, float th_lines, int32_t* line_best_idx, int32_t* line_best_dist,
+                                             uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream) {
+  PLVS_REQUIRE(P || L, "neither points nor lines");
+  std::unique_ptr<fj::Part> points, lines;
+  if (P) {   // both kinds' refusals before anything is launched or written
+    const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip_points, th_points, point_best_idx, point_best_dist, point_reached,
+                                          point_stats, false, &points);
+    if (rc != PLVS_OK) return rc;
+  }
+  if (L) {
+    const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip_lines, th_lines, line_best_idx, line_best_dist, line_reached, line_stats,
+                                         false, &lines);
+    if (rc != PLVS_OK) return rc;
+  }
+  if (P && point_stats) point_stats[0] = point_stats[1] = point_stats[2] = point_stats[3] = 0;
+  if (L && line_stats) line_stats[0] = line_stats[1] = line_stats[2] = line_stats[3] = 0;
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  int launches = 0, waits = 0;
+  size_t copied = 0;
+  const int rc = fj::run_parts(points.get(), lines.get(), static_cast<hipStream_t>(stream), stream == nullptr, false, &launches, &waits, &copied);
+  if (stats) { stats[0] = launches; stats[1] = waits; stats[2] = (int32_t)copied; }
+  return rc;
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "fuse_jobs.hpp"
+#include "keyframe_handle.hpp"
 #include "line_fuse_pair.hpp"
 
 namespace {
@@ -49,46 +50,55 @@ __host__ __device__ inline int2 pack(int best_idx, int best_dist, int reached, i
   return make_int2(best_idx, (best_dist & 0xffff) | (reached << 16) | (ambiguous << 24));
 }
 
-__global__ __launch_bounds__(256) void line_fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FuseLines L, float th,
-                                                               int2* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pair >= L.n_pairs) return;
-  const int k = pair / L.m, i = pair - k * L.m;
-  if (L.skip && L.skip[pair]) {
-    if (lane == 0) out[pair] = pack(-1, -1, lf::kSkipped, 0);
-    return;
-  }
-  const KfDev& D = kfs[k];
-  const Front f = lf::front(D.k, L.start + 3 * (size_t)i, L.end + 3 * (size_t)i, L.normal + 3 * (size_t)i, L.max_dist[i]);
+// where the walk finds one key frame's arrays: resolved from the staged block's offsets (KfDev) or the handle's pointers (KfRes)
+struct KfArrays {
+  const Member* members;
+  const int* start;
+  const uint4* desc;
+  const float *sf, *sig;
+  int n_members;
+};
+
+// one key frame of a resident call's table: the call's pose inside the handle's constants, and pointers into the handle's allocation
+struct KfRes {
+  KfConst k;
+  KfArrays a;
+};
+static_assert(sizeof(KfRes) == 168, "the per-call table entry: stats[3] of the resident entries is documented and tested from it");
+
+// One wave, one pair past front(): theta's plan and its ambiguity, the walk of the one or two sub-windows in 64-member strides, the
+// gates, the (distance, enumeration position) key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and
+// the resident kernel both call it.
+__device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, const FuseLines& L, int i, const Front& f, float th, int lane,
+                                          int2* __restrict__ rec) {
   if (f.reached != lf::kEmptyWindow) {
-    if (lane == 0) out[pair] = pack(-1, -1, f.reached, 0);
+    if (lane == 0) *rec = pack(-1, -1, f.reached, 0);
     return;
   }
   // :2124-2127 and the head of GetLineFeaturesInArea, uniform across the wave
-  const float scale = reinterpret_cast<const float*>(base + D.o_sf)[f.level];
+  const float scale = A.sf[f.level];
   const float dtheta = (float)(10 * lf::kPi / 180.f) * scale;
   const float dd = th * 100.0f * scale;
   const float theta = lf::theta_device(f.rep);
-  const lf::ThetaPlan plan = lf::theta_plan(D.k, theta, dtheta);
-  const int ambiguous = (f.ambiguous || plan.nested || lf::theta_ambiguous(D.k, theta, dtheta, plan)) ? 1 : 0;
-  if (ambiguous || plan.full || D.n_members == 0) {   // (the host decides; the refusal; nothing to walk)
-    if (lane == 0) out[pair] = pack(-1, -1, plan.full ? lf::kFullTheta : lf::kEmptyWindow, ambiguous);
+  const lf::ThetaPlan plan = lf::theta_plan(K, theta, dtheta);
+  const int ambiguous = (f.ambiguous || plan.nested || lf::theta_ambiguous(K, theta, dtheta, plan)) ? 1 : 0;
+  if (ambiguous || plan.full || A.n_members == 0) {   // (the host decides; the refusal; nothing to walk)
+    if (lane == 0) *rec = pack(-1, -1, plan.full ? lf::kFullTheta : lf::kEmptyWindow, ambiguous);
     return;
   }
-  const Member* members = reinterpret_cast<const Member*>(base + D.o_mem);
-  const int* start = reinterpret_cast<const int*>(base + D.o_start);
-  const uint4* desc = reinterpret_cast<const uint4*>(base + D.o_desc);
-  const float* sig = reinterpret_cast<const float*>(base + D.o_sig);
+  const Member* members = A.members;
+  const int* start = A.start;
+  const uint4* desc = A.desc;
+  const float* sig = A.sig;
   const uint4 qa = L.desc[2 * (size_t)i], qb = L.desc[2 * (size_t)i + 1];
-  const lf::Rep rr = lf::right_rep(D.k, f);
+  const lf::Rep rr = lf::right_rep(K, f);
   const float dmin = f.rep.d - dd, dmax = f.rep.d + dd;
   uint32_t best = 0xffffffffu;
   int best_idx = -1;
   bool gated = false;
   uint32_t pos0 = 0;   // enumeration position of the range's first member; it runs on across the sub-windows
   for (int s = 0; s < plan.n; ++s) {
-    const lf::Cells c = lf::leaf_cells(D.k, lf::plan_leaf(plan, s, dmin, dmax));
+    const lf::Cells c = lf::leaf_cells(K, lf::plan_leaf(plan, s, dmin, dmax));
     if (!c.ok) continue;
     for (int ix = c.c0; ix <= c.c1; ++ix) {   // c0 >= 0, c1 <= kCols - 1, 0 <= r0, r1 <= kRows - 1: inside the kCols * kRows + 1 starts
       const int a = start[ix * lf::kRows + c.r0], e = start[ix * lf::kRows + c.r1 + 1];
@@ -122,14 +132,50 @@ __global__ __launch_bounds__(256) void line_fuse_window_kernel(const char* __res
       reached = !has_gated ? lf::kNoCandidate : (d <= lf::kThLow ? lf::kCandidate : lf::kAboveThLow);
       if (reached == lf::kCandidate) { idx = win_idx; dist = d; }
     }
-    out[pair] = pack(idx, dist, reached, 0);
+    *rec = pack(idx, dist, reached, 0);
   }
 }
 
-KfConst kf_const(const plvs_line_fuse_keyframe& kf) {
+__global__ __launch_bounds__(256) void line_fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FuseLines L, float th,
+                                                               int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= L.n_pairs) return;
+  const int k = pair / L.m, i = pair - k * L.m;
+  if (L.skip && L.skip[pair]) {
+    if (lane == 0) out[pair] = pack(-1, -1, lf::kSkipped, 0);
+    return;
+  }
+  const KfDev& D = kfs[k];
+  const Front f = lf::front(D.k, L.start + 3 * (size_t)i, L.end + 3 * (size_t)i, L.normal + 3 * (size_t)i, L.max_dist[i]);
+  const KfArrays A{reinterpret_cast<const Member*>(base + D.o_mem), reinterpret_cast<const int*>(base + D.o_start),
+                   reinterpret_cast<const uint4*>(base + D.o_desc), reinterpret_cast<const float*>(base + D.o_sf),
+                   reinterpret_cast<const float*>(base + D.o_sig), D.n_members};
+  walk_pair(D.k, A, L, i, f, th, lane, out + pair);
+}
+
+// The resident layout: the table holds pointers into the handles' own allocations (keyframe_handle.hpp), nothing of a key frame is in
+// the call's block.  The pair index is the wave's: taken through readfirstlane, so the compiler knows it uniform and the pair's table
+// entry — pose, constants, pointers — is read by scalar loads and stays in scalar registers.
+__global__ __launch_bounds__(256) void line_fuse_window_resident_kernel(const KfRes* __restrict__ kfs, FuseLines L, float th, int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (pair >= L.n_pairs) return;
+  const int k = pair / L.m, i = pair - k * L.m;
+  if (L.skip && L.skip[pair]) {
+    if (lane == 0) out[pair] = pack(-1, -1, lf::kSkipped, 0);
+    return;
+  }
+  const KfRes& D = kfs[k];
+  const Front f = lf::front(D.k, L.start + 3 * (size_t)i, L.end + 3 * (size_t)i, L.normal + 3 * (size_t)i, L.max_dist[i]);
+  walk_pair(D.k, D.a, L, i, f, th, lane, out + pair);
+}
+
+// pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there: with_pose())
+KfConst kf_const(const plvs_line_fuse_keyframe& kf, bool pose = true) {
   KfConst c;
-  for (int i = 0; i < 9; ++i) c.R[i] = kf.Rcw[i];
-  for (int i = 0; i < 3; ++i) { c.t[i] = kf.tcw[i]; c.Ow[i] = kf.Ow[i]; }
+  for (int i = 0; i < 9; ++i) c.R[i] = pose ? kf.Rcw[i] : 0.0f;
+  for (int i = 0; i < 3; ++i) { c.t[i] = pose ? kf.tcw[i] : 0.0f; c.Ow[i] = pose ? kf.Ow[i] : 0.0f; }
   c.fx = kf.K4[0]; c.fy = kf.K4[1]; c.cx = kf.K4[2]; c.cy = kf.K4[3];
   c.mbf = kf.view.bf;
   c.min_x = kf.bounds4[0]; c.max_x = kf.bounds4[1]; c.min_y = kf.bounds4[2]; c.max_y = kf.bounds4[3];
@@ -147,31 +193,23 @@ void make_grid(const plvs_line_fuse_keyframe& kf, const KfConst& c, lf::Grid* g)
                  kf.view.u_right_start, kf.view.u_right_end, kf.view.max_diag, c.theta_inv, c.d_inv, 0, g);
 }
 
-// the refusals of every entry: before anything is launched or written
-int check_args(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
+// the refusals of every entry that are not a key frame's: before anything is launched or written
+int check_call(const void* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
   PLVS_REQUIRE(n_kfs >= 0 && L && L->m >= 0, "null lines / negative size");
   PLVS_REQUIRE(best_idx && best_dist, "null output");
   PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
   PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
   PLVS_REQUIRE((long long)n_kfs * L->m <= (1ll << 30), "more than 2^30 pairs");
   PLVS_REQUIRE(L->m == 0 || (L->start && L->end && L->normal && L->max_dist && L->desc), "null map line array");
+  return PLVS_OK;
+}
+
+int check_args(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
+  const int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
   for (int k = 0; k < n_kfs; ++k) {
-    const plvs_line_fuse_keyframe& kf = kfs[k];
-    PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
-                 "single-camera pinhole key frames only (NlinesLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
-    PLVS_REQUIRE(kf.K4 && kf.bounds4 && kf.Rcw && kf.tcw && kf.Ow, "null pose / camera array");
-    PLVS_REQUIRE(kf.n_line_levels >= 1 && kf.n_line_levels <= kMaxLevels && kf.n_line_levels == kf.view.n_levels && kf.view.line_scale_factors &&
-                     kf.view.line_inv_level_sigma2,
-                 "line levels outside [1, 64], different from the view's, or null level arrays");
-    PLVS_REQUIRE(kf.view.max_diag > 0.0f, "mnMaxDiag not positive");
-    PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key line count outside [0, 2^23)");
-    PLVS_REQUIRE((kf.view.u_right_start == nullptr) == (kf.view.u_right_end == nullptr), "one of mvuRightLineStart / End without the other");
-    if (kf.view.n > 0) {
-      PLVS_REQUIRE(kf.view.keylines_un && kf.view.descriptors, "null key frame array");
-      for (int i = 0; i < kf.view.n; ++i)
-        PLVS_REQUIRE(kf.view.keylines_un[i].octave >= 0 && kf.view.keylines_un[i].octave < kf.n_line_levels,
-                     "octave of a key line outside the key frame's levels");
-    }
+    const int rk = plvs::kfhandle::check_line_keyframe(kfs[k], true);
+    if (rk != PLVS_OK) return rk;
   }
   return PLVS_OK;
 }
@@ -184,6 +222,28 @@ lf::Result host_pair(const plvs_line_fuse_keyframe& kf, const KfConst& c, const 
 
 const char* const kFullThetaMessage =
     "GetLineFeaturesInArea: search over the full theta interval (deltaTheta above pi / 2: the reference terminates here)";
+
+// nothing is written when a pair asks for the full theta interval
+int refused_full_theta(const std::vector<lf::Result>& results) {
+  for (const lf::Result& r : results)
+    if (r.reached == lf::kFullTheta) {
+      plvs::set_error("invalid argument: %s", kFullThetaMessage);
+      return PLVS_ERR_INVALID_ARG;
+    }
+  return PLVS_OK;
+}
+
+// the outputs from the results; -> pairs that reached the window
+int post_results(const std::vector<lf::Result>& results, int32_t* best_idx, int32_t* best_dist, uint8_t* reached) {
+  int windows = 0;
+  for (size_t p = 0; p < results.size(); ++p) {
+    best_idx[p] = results[p].best_idx;
+    best_dist[p] = results[p].best_dist;
+    if (reached) reached[p] = (uint8_t)results[p].reached;
+    if (results[p].reached >= lf::kEmptyWindow) ++windows;
+  }
+  return windows;
+}
 
 // One call's line search as a part of the staging block (fuse_jobs.hpp)
 struct LinePart : plvs::fusejob::Part {
@@ -317,29 +377,201 @@ struct LinePart : plvs::fusejob::Part {
     st_host += host;
   }
 
-  // nothing is written when a pair asks for the full theta interval
-  int refused() override {
-    for (const lf::Result& r : results)
-      if (r.reached == lf::kFullTheta) {
-        plvs::set_error("invalid argument: %s", kFullThetaMessage);
-        return PLVS_ERR_INVALID_ARG;
-      }
-    return PLVS_OK;
-  }
+  int refused() override { return refused_full_theta(results); }
 
   void post() override {
-    int windows = 0;
-    for (size_t p = 0; p < results.size(); ++p) {
-      best_idx[p] = results[p].best_idx;
-      best_dist[p] = results[p].best_dist;
-      if (reached) reached[p] = (uint8_t)results[p].reached;
-      if (results[p].reached >= lf::kEmptyWindow) ++windows;
-    }
+    const int windows = post_results(results, best_idx, best_dist, reached);
     if (stats) { stats[0] = st_host; stats[1] = windows; stats[2] = launches; }
   }
 };
 
+// ---------------------------------------------------------------------------------------------------- resident key frames
+KfConst with_pose(const KfConst& resident, const plvs_keyframe_pose& pose) {
+  KfConst c = resident;
+  for (int i = 0; i < 9; ++i) c.R[i] = pose.Rcw[i];
+  for (int i = 0; i < 3; ++i) { c.t[i] = pose.tcw[i]; c.Ow[i] = pose.Ow[i]; }
+  return c;
+}
+
+KfArrays arrays_at(const char* block, const plvs_keyframe::Lines& s) {
+  return KfArrays{reinterpret_cast<const Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
+                  reinterpret_cast<const uint4*>(block + s.o_desc), reinterpret_cast<const float*>(block + s.o_sf),
+                  reinterpret_cast<const float*>(block + s.o_sig), s.n_members};
+}
+
+lf::Result host_pair(const plvs_keyframe& h, const KfConst& c, const plvs_fuse_lines* L, int i, float th) {
+  const KfArrays a = arrays_at(h.host.data(), h.ln);
+  const lf::KfGrid G{a.start, a.members, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig};
+  return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
+                       th, 0, 0);
+}
+
+// One call's line search over resident key frames as a part of the staging block (fuse_jobs.hpp):
+// [key-frame table: pose, constants, pointers into the handles' allocations | lines | skip] copied in one piece,
+// [records, posted into the pinned side].  Nothing of a key frame is built, staged or copied.
+struct LinePartKf : plvs::fusejob::Part {
+  const plvs_keyframe* const* kfs;
+  const plvs_keyframe_pose* poses;
+  int n_kfs;
+  const plvs_fuse_lines* L;
+  const uint8_t* skip;
+  float th;
+  int32_t *best_idx, *best_dist;
+  uint8_t* reached;
+  int32_t* stats;
+
+  std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
+  std::vector<lf::Result> results;
+  size_t o_tab = 0, o_start = 0, o_end = 0, o_nrm = 0, o_maxd = 0, o_desc = 0, o_skip = 0;
+  size_t in_at = 0, out_at = 0;
+  int st_host = 0;
+
+  LinePartKf(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_,
+             float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
+      : kfs(kfs_), poses(poses_), n_kfs(n_kfs_), L(L_), skip(skip_), th(th_), best_idx(best_idx_), best_dist(best_dist_), reached(reached_),
+        stats(stats_) {}
+
+  size_t n_pairs() const { return (size_t)n_kfs * L->m; }
+
+  void prepare() override {
+    const int m = L->m;
+    consts.resize((size_t)n_kfs);
+    bool any_lines = false;
+    for (int k = 0; k < n_kfs; ++k) {
+      consts[k] = with_pose(kfs[k]->ln.c, poses[k]);
+      any_lines = any_lines || kfs[k]->ln.n > 0;
+    }
+    bool work = false;   // a pair that is not skipped, and a key frame that has key lines
+    if (any_lines && m > 0) {
+      if (!skip) work = true;
+      for (size_t p = 0; !work && p < n_pairs(); ++p) work = !skip[p];
+    }
+    device = work;
+    if (!device) return;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    o_tab = take(sizeof(KfRes) * (size_t)n_kfs);
+    o_start = take(sizeof(float) * 3 * (size_t)m); o_end = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
+    o_maxd = take(sizeof(float) * (size_t)m); o_desc = take((size_t)m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    in_bytes = at;
+    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
+  }
+
+  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
+    in_at = in_at_;
+    out_at = out_at_;
+    const int m = L->m;
+    char* p = pinned + in_at;
+    KfRes* tab = reinterpret_cast<KfRes*>(p + o_tab);
+    for (int k = 0; k < n_kfs; ++k) tab[k] = KfRes{consts[k], arrays_at(kfs[k]->dev, kfs[k]->ln)};
+    memcpy(p + o_start, L->start, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_end, L->end, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_nrm, L->normal, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_maxd, L->max_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_desc, L->desc, (size_t)m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FuseLines FL{reinterpret_cast<const float*>(d + o_start), reinterpret_cast<const float*>(d + o_end),
+                       reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
+                       reinterpret_cast<const uint4*>(d + o_desc), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                       L->m, (int)n_pairs()};
+    hipLaunchKernelGGL(line_fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
+                       reinterpret_cast<const KfRes*>(d + o_tab), FL, th, reinterpret_cast<int2*>(pinned + out_at));
+    PLVS_KERNEL_CHECK();
+    ++launches;
+    return PLVS_OK;
+  }
+
+  void host_all() override {
+    const int m = L->m;
+    results.resize(n_pairs());
+    for (int k = 0; k < n_kfs; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        results[pair] = (skip && skip[pair]) ? lf::Result{-1, -1, lf::kSkipped} : host_pair(*kfs[k], consts[k], L, i, th);
+      }
+  }
+
+  void collect(const char* pinned) override {
+    const int m = L->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    results.resize(n_pairs());
+    lf::Result* res_out = results.data();
+    int host = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const int2 r = rec[pair];
+        lf::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
+        if ((r.y >> 24) & 1) {   // the level or theta is the host's to decide: the pair once more, on the handle's host copy
+          res = host_pair(*kfs[k], consts[k], L, i, th);
+          ++host;
+        }
+        res_out[pair] = res;
+      }
+    st_host += host;
+  }
+
+  int refused() override { return refused_full_theta(results); }
+
+  void post() override {
+    const int windows = post_results(results, best_idx, best_dist, reached);
+    if (stats) { stats[0] = st_host; stats[1] = windows; stats[2] = launches; stats[3] = plvs::fusejob::copy_in_stat(*this); }
+  }
+};
+
 }  // namespace
+
+int plvs::kfhandle::check_line_keyframe(const plvs_line_fuse_keyframe& kf, bool need_pose) {
+  PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
+               "single-camera pinhole key frames only (NlinesLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
+  PLVS_REQUIRE(kf.K4 && kf.bounds4 && (!need_pose || (kf.Rcw && kf.tcw && kf.Ow)), "null pose / camera array");
+  PLVS_REQUIRE(kf.n_line_levels >= 1 && kf.n_line_levels <= kMaxLevels && kf.n_line_levels == kf.view.n_levels && kf.view.line_scale_factors &&
+                   kf.view.line_inv_level_sigma2,
+               "line levels outside [1, 64], different from the view's, or null level arrays");
+  PLVS_REQUIRE(kf.view.max_diag > 0.0f, "mnMaxDiag not positive");
+  PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key line count outside [0, 2^23)");
+  PLVS_REQUIRE((kf.view.u_right_start == nullptr) == (kf.view.u_right_end == nullptr), "one of mvuRightLineStart / End without the other");
+  if (kf.view.n > 0) {
+    PLVS_REQUIRE(kf.view.keylines_un && kf.view.descriptors, "null key frame array");
+    for (int i = 0; i < kf.view.n; ++i)
+      PLVS_REQUIRE(kf.view.keylines_un[i].octave >= 0 && kf.view.keylines_un[i].octave < kf.n_line_levels,
+                   "octave of a key line outside the key frame's levels");
+  }
+  return PLVS_OK;
+}
+
+void plvs::kfhandle::stage_lines(const plvs_line_fuse_keyframe& kf, plvs_keyframe* h) {
+  plvs_keyframe::Lines& s = h->ln;
+  s.present = true;
+  s.c = kf_const(kf, false);
+  lf::Grid grid;
+  make_grid(kf, s.c, &grid);
+  s.n = kf.view.n;
+  s.n_members = (int)grid.members.size();
+  s.n_levels = kf.n_line_levels;
+  s.o_mem = put(&h->host, grid.members.data(), sizeof(Member) * grid.members.size());
+  s.o_start = put(&h->host, grid.start.data(), sizeof(int) * grid.start.size());
+  s.o_desc = put(&h->host, kf.view.descriptors, (size_t)kf.view.n * 32);
+  s.o_sf = put(&h->host, kf.view.line_scale_factors, sizeof(float) * (size_t)kf.n_line_levels);
+  s.o_sig = put(&h->host, kf.view.line_inv_level_sigma2, sizeof(float) * (size_t)kf.n_line_levels);
+}
+
+int plvs::fusejob::make_line_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
+                                     const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
+                                     bool host_entry, std::unique_ptr<Part>* out) {
+  out->reset();
+  int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  rc = check_handles(kfs, poses, n_kfs, 2, host_entry);
+  if (rc != PLVS_OK) return rc;
+  if (n_kfs > 0 && L->m > 0) out->reset(new LinePartKf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
+  return PLVS_OK;
+}
 
 int plvs::fusejob::make_line_part(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
                                   int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {
@@ -368,14 +600,7 @@ int plvs_hip_line_fuse_search_host(const plvs_line_fuse_keyframe* kfs, int n_kfs
   const int rc = plvs::fusejob::make_line_part(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, &part);
   if (rc != PLVS_OK) return rc;
   if (stats) stats[0] = stats[1] = stats[2] = 0;
-  if (!part) return PLVS_OK;
-  part->prepare();
-  part->device = false;
-  part->host_all();
-  const int refused = part->refused();
-  if (refused != PLVS_OK) return refused;
-  part->post();
-  return PLVS_OK;
+  return part ? plvs::fusejob::run_part_on_host(part.get()) : PLVS_OK;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "fuse_jobs.hpp"
 #include "fuse_pair.hpp"
+#include "keyframe_handle.hpp"
 #include "orb_window.hpp"
 
 namespace {
@@ -59,39 +60,42 @@ __global__ __launch_bounds__(256) void fuse_front_kernel(const KfDev* __restrict
   fronts[pair] = f;
 }
 
-template <bool kChained>
-__global__ __launch_bounds__(256) void fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FusePoints P, float th,
-                                                          const Front* __restrict__ fronts, int2* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pair >= P.n_pairs) return;
-  const int k = pair / P.m, i = pair - k * P.m;
-  Front f;
-  if (kChained) {
-    f = fronts[pair];
-  } else {
-    if (P.skip && P.skip[pair]) {
-      if (lane == 0) out[pair] = pack(-1, -1, fp::kSkipped, 0);
-      return;
-    }
-    f = fp::front(kfs[k].k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
-  }
+// where the walk finds one key frame's arrays: resolved from the staged block's offsets (KfDev) or the handle's pointers (KfRes)
+struct KfArrays {
+  const FrameGrid::Member* members;
+  const int* start;
+  const float* u_right;
+  const uint4* desc;
+  const float *sf, *sig;
+  int n;
+};
+
+// one key frame of a resident call's table: the call's pose inside the handle's constants, and pointers into the handle's allocation
+struct KfRes {
+  KfConst k;
+  KfArrays a;
+};
+static_assert(sizeof(KfRes) == 160, "the per-call table entry: stats[3] of the resident entries is documented and tested from it");
+
+// One wave, one pair past the tests of front(): the window walk in 64-member strides, the gates, the (distance, enumeration position)
+// key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and the resident kernel both call it.
+__device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, const FusePoints& P, int i, const Front& f, float th, int lane,
+                                          int2* __restrict__ rec) {
   if (f.reached != fp::kEmptyWindow) {
-    if (lane == 0) out[pair] = pack(-1, -1, f.reached, 0);
+    if (lane == 0) *rec = pack(-1, -1, f.reached, 0);
     return;
   }
-  const KfDev& D = kfs[k];
-  const float radius = th * reinterpret_cast<const float*>(base + D.o_sf)[f.level];
+  const float radius = th * A.sf[f.level];
   fp::Cells w;
-  if (D.n == 0 || !fp::window_cells(D.k, f.u, f.v, radius, &w)) {
-    if (lane == 0) out[pair] = pack(-1, -1, fp::kEmptyWindow, f.ambiguous);
+  if (A.n == 0 || !fp::window_cells(K, f.u, f.v, radius, &w)) {
+    if (lane == 0) *rec = pack(-1, -1, fp::kEmptyWindow, f.ambiguous);
     return;
   }
-  const FrameGrid::Member* members = reinterpret_cast<const FrameGrid::Member*>(base + D.o_mem);
-  const int* start = reinterpret_cast<const int*>(base + D.o_start);
-  const float* u_right = reinterpret_cast<const float*>(base + D.o_ur);
-  const uint4* desc = reinterpret_cast<const uint4*>(base + D.o_desc);
-  const float* sig = reinterpret_cast<const float*>(base + D.o_sig);
+  const FrameGrid::Member* members = A.members;
+  const int* start = A.start;
+  const float* u_right = A.u_right;
+  const uint4* desc = A.desc;
+  const float* sig = A.sig;
   const uint4 qa = P.desc[2 * (size_t)i], qb = P.desc[2 * (size_t)i + 1];
   uint32_t best = 0xffffffffu;
   int best_idx = -1;
@@ -130,14 +134,56 @@ __global__ __launch_bounds__(256) void fuse_window_kernel(const char* __restrict
       reached = !has_gated ? fp::kNoCandidate : (d <= fp::kThLow ? fp::kCandidate : fp::kAboveThLow);
       if (reached == fp::kCandidate) { idx = win_idx; dist = d; }
     }
-    out[pair] = pack(idx, dist, reached, f.ambiguous);
+    *rec = pack(idx, dist, reached, f.ambiguous);
   }
 }
 
-KfConst kf_const(const plvs_fuse_keyframe& kf) {
+template <bool kChained>
+__global__ __launch_bounds__(256) void fuse_window_kernel(const char* __restrict__ base, const KfDev* __restrict__ kfs, FusePoints P, float th,
+                                                          const Front* __restrict__ fronts, int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= P.n_pairs) return;
+  const int k = pair / P.m, i = pair - k * P.m;
+  Front f;
+  if (kChained) {
+    f = fronts[pair];
+  } else {
+    if (P.skip && P.skip[pair]) {
+      if (lane == 0) out[pair] = pack(-1, -1, fp::kSkipped, 0);
+      return;
+    }
+    f = fp::front(kfs[k].k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
+  }
+  const KfDev& D = kfs[k];
+  const KfArrays A{reinterpret_cast<const FrameGrid::Member*>(base + D.o_mem), reinterpret_cast<const int*>(base + D.o_start),
+                   reinterpret_cast<const float*>(base + D.o_ur), reinterpret_cast<const uint4*>(base + D.o_desc),
+                   reinterpret_cast<const float*>(base + D.o_sf), reinterpret_cast<const float*>(base + D.o_sig), D.n};
+  walk_pair(D.k, A, P, i, f, th, lane, out + pair);
+}
+
+// The resident layout: the table holds pointers into the handles' own allocations (keyframe_handle.hpp), nothing of a key frame is in
+// the call's block.  The pair index is the wave's: taken through readfirstlane, so the compiler knows it uniform and the pair's table
+// entry — pose, constants, pointers — is read by scalar loads and stays in scalar registers.
+__global__ __launch_bounds__(256) void fuse_window_resident_kernel(const KfRes* __restrict__ kfs, FusePoints P, float th, int2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int pair = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (pair >= P.n_pairs) return;
+  const int k = pair / P.m, i = pair - k * P.m;
+  if (P.skip && P.skip[pair]) {
+    if (lane == 0) out[pair] = pack(-1, -1, fp::kSkipped, 0);
+    return;
+  }
+  const KfRes& D = kfs[k];
+  const Front f = fp::front(D.k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
+  walk_pair(D.k, D.a, P, i, f, th, lane, out + pair);
+}
+
+// with_pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there: with_pose())
+KfConst kf_const(const plvs_fuse_keyframe& kf, bool pose = true) {
   KfConst c;
-  for (int i = 0; i < 4; ++i) c.q[i] = kf.q_cw[i];
-  for (int i = 0; i < 3; ++i) { c.t[i] = kf.tcw[i]; c.Ow[i] = kf.Ow[i]; }
+  for (int i = 0; i < 4; ++i) c.q[i] = pose ? kf.q_cw[i] : 0.0f;
+  for (int i = 0; i < 3; ++i) { c.t[i] = pose ? kf.tcw[i] : 0.0f; c.Ow[i] = pose ? kf.Ow[i] : 0.0f; }
   c.fx = kf.K4[0]; c.fy = kf.K4[1]; c.cx = kf.K4[2]; c.cy = kf.K4[3];
   c.mbf = kf.mbf;
   c.min_x = kf.bounds4[0]; c.max_x = kf.bounds4[1]; c.min_y = kf.bounds4[2]; c.max_y = kf.bounds4[3];
@@ -148,26 +194,23 @@ KfConst kf_const(const plvs_fuse_keyframe& kf) {
   return c;
 }
 
-// the refusals of both entries: before anything is launched or written
-int check_args(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
+// the refusals of every entry that are not a key frame's: before anything is launched or written
+int check_call(const void* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
   PLVS_REQUIRE(n_kfs >= 0 && P && P->m >= 0, "null points / negative size");
   PLVS_REQUIRE(best_idx && best_dist, "null output");
   PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
   PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
   PLVS_REQUIRE((long long)n_kfs * P->m <= (1ll << 30), "more than 2^30 pairs");
   PLVS_REQUIRE(P->m == 0 || (P->pos && P->normal && P->min_dist && P->max_dist && P->desc), "null map point array");
+  return PLVS_OK;
+}
+
+int check_args(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
+  const int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
   for (int k = 0; k < n_kfs; ++k) {
-    const plvs_fuse_keyframe& kf = kfs[k];
-    PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
-                 "single-camera pinhole key frames only (NLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
-    PLVS_REQUIRE(kf.K4 && kf.bounds4 && kf.q_cw && kf.tcw && kf.Ow, "null pose / camera array");
-    PLVS_REQUIRE(kf.n_levels >= 1 && kf.n_levels <= kMaxLevels && kf.inv_level_sigma2 && kf.view.scale_factors, "levels outside [1, 64] or null level arrays");
-    PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key point count outside [0, 2^23)");
-    if (kf.view.n > 0) {
-      PLVS_REQUIRE(kf.view.x && kf.view.y && kf.view.octave && kf.view.u_right && kf.view.desc, "null key frame array");
-      for (int i = 0; i < kf.view.n; ++i)
-        PLVS_REQUIRE(kf.view.octave[i] >= 0 && kf.view.octave[i] < kf.n_levels, "octave of a key point outside the key frame's levels");
-    }
+    const int rk = plvs::kfhandle::check_point_keyframe(kfs[k], true);
+    if (rk != PLVS_OK) return rk;
   }
   return PLVS_OK;
 }
@@ -348,7 +391,180 @@ struct PointPart : plvs::fusejob::Part {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------- resident key frames
+KfConst with_pose(const KfConst& resident, const plvs_keyframe_pose& pose) {
+  KfConst c = resident;
+  for (int i = 0; i < 4; ++i) c.q[i] = pose.q_cw[i];
+  for (int i = 0; i < 3; ++i) { c.t[i] = pose.tcw[i]; c.Ow[i] = pose.Ow[i]; }
+  return c;
+}
+
+KfArrays arrays_at(const char* block, const plvs_keyframe::Points& s) {
+  return KfArrays{reinterpret_cast<const FrameGrid::Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
+                  reinterpret_cast<const float*>(block + s.o_ur), reinterpret_cast<const uint4*>(block + s.o_desc),
+                  reinterpret_cast<const float*>(block + s.o_sf), reinterpret_cast<const float*>(block + s.o_sig), s.n};
+}
+
+fp::Result host_pair(const plvs_keyframe& h, const KfConst& c, const plvs_fuse_points* P, int i, float th) {
+  const KfArrays a = arrays_at(h.host.data(), h.pt);
+  const fp::KfGrid<FrameGrid::Member> G{a.start, a.members, a.u_right, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig};
+  return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
+}
+
+// One call's point search over resident key frames as a part of the staging block (fuse_jobs.hpp):
+// [key-frame table: pose, constants, pointers into the handles' allocations | points | skip] copied in one piece,
+// [records, posted into the pinned side].  Nothing of a key frame is built, staged or copied.
+struct PointPartKf : plvs::fusejob::Part {
+  const plvs_keyframe* const* kfs;
+  const plvs_keyframe_pose* poses;
+  int n_kfs;
+  const plvs_fuse_points* P;
+  const uint8_t* skip;
+  float th;
+  Outputs out;
+  int32_t* stats;
+
+  std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
+  size_t o_tab = 0, o_pos = 0, o_nrm = 0, o_mind = 0, o_maxd = 0, o_pd = 0, o_skip = 0;
+  size_t in_at = 0, out_at = 0;
+  int st_host = 0, st_windows = 0;
+
+  PointPartKf(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_,
+              float th_, const Outputs& out_, int32_t* stats_)
+      : kfs(kfs_), poses(poses_), n_kfs(n_kfs_), P(P_), skip(skip_), th(th_), out(out_), stats(stats_) {}
+
+  size_t n_pairs() const { return (size_t)n_kfs * P->m; }
+
+  void prepare() override {
+    const int m = P->m;
+    consts.resize((size_t)n_kfs);
+    for (int k = 0; k < n_kfs; ++k) consts[k] = with_pose(kfs[k]->pt.c, poses[k]);
+    bool work = false;   // a pair that is not skipped, in a key frame that has key points
+    for (int k = 0; k < n_kfs && !work; ++k) {
+      if (kfs[k]->pt.n == 0) continue;
+      if (!skip) { work = m > 0; continue; }
+      for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
+    }
+    device = work;
+    if (!device) return;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
+    o_tab = take(sizeof(KfRes) * (size_t)n_kfs);
+    o_pos = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
+    o_mind = take(sizeof(float) * (size_t)m); o_maxd = take(sizeof(float) * (size_t)m); o_pd = take((size_t)m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    in_bytes = at;
+    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
+  }
+
+  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
+    in_at = in_at_;
+    out_at = out_at_;
+    const int m = P->m;
+    char* p = pinned + in_at;
+    KfRes* tab = reinterpret_cast<KfRes*>(p + o_tab);
+    for (int k = 0; k < n_kfs; ++k) tab[k] = KfRes{consts[k], arrays_at(kfs[k]->dev, kfs[k]->pt)};
+    memcpy(p + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
+    memcpy(p + o_mind, P->min_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
+    memcpy(p + o_pd, P->desc, (size_t)m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FusePoints FP{reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm),
+                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const float*>(d + o_maxd),
+                        reinterpret_cast<const uint4*>(d + o_pd), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                        P->m, (int)n_pairs()};
+    hipLaunchKernelGGL(fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
+                       reinterpret_cast<const KfRes*>(d + o_tab), FP, th, reinterpret_cast<int2*>(pinned + out_at));
+    PLVS_KERNEL_CHECK();
+    ++launches;
+    return PLVS_OK;
+  }
+
+  void host_all() override {
+    const int m = P->m;
+    for (int k = 0; k < n_kfs; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const fp::Result r = (skip && skip[pair]) ? fp::Result{-1, -1, fp::kSkipped} : host_pair(*kfs[k], consts[k], P, i, th);
+        out.put(pair, r);
+        if (r.reached >= fp::kEmptyWindow) ++st_windows;
+      }
+  }
+
+  void collect(const char* pinned) override {
+    const int m = P->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    const Outputs o = out;
+    int host = 0, windows = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const int2 r = rec[pair];
+        fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
+        if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, on the handle's host copy
+          res = host_pair(*kfs[k], consts[k], P, i, th);
+          ++host;
+        }
+        o.put(pair, res);
+        if (res.reached >= fp::kEmptyWindow) ++windows;
+      }
+    st_host += host;
+    st_windows += windows;
+  }
+
+  void post() override {
+    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = launches; stats[3] = plvs::fusejob::copy_in_stat(*this); }
+  }
+};
+
 }  // namespace
+
+int plvs::kfhandle::check_point_keyframe(const plvs_fuse_keyframe& kf, bool need_pose) {
+  PLVS_REQUIRE(kf.n_cameras == 1 && kf.camera_model == PLVS_CAMERA_PINHOLE,
+               "single-camera pinhole key frames only (NLeft == -1, bRight == false): the fisheye / two-camera branches stay with the reference");
+  PLVS_REQUIRE(kf.K4 && kf.bounds4 && (!need_pose || (kf.q_cw && kf.tcw && kf.Ow)), "null pose / camera array");
+  PLVS_REQUIRE(kf.n_levels >= 1 && kf.n_levels <= kMaxLevels && kf.inv_level_sigma2 && kf.view.scale_factors, "levels outside [1, 64] or null level arrays");
+  PLVS_REQUIRE(kf.view.n >= 0 && kf.view.n < (1 << kPosBits), "key point count outside [0, 2^23)");
+  if (kf.view.n > 0) {
+    PLVS_REQUIRE(kf.view.x && kf.view.y && kf.view.octave && kf.view.u_right && kf.view.desc, "null key frame array");
+    for (int i = 0; i < kf.view.n; ++i)
+      PLVS_REQUIRE(kf.view.octave[i] >= 0 && kf.view.octave[i] < kf.n_levels, "octave of a key point outside the key frame's levels");
+  }
+  return PLVS_OK;
+}
+
+void plvs::kfhandle::stage_points(const plvs_fuse_keyframe& kf, plvs_keyframe* h) {
+  plvs_keyframe::Points& s = h->pt;
+  const FrameGrid grid(&kf.view);
+  const size_t n = (size_t)kf.view.n;
+  s.present = true;
+  s.c = kf_const(kf, false);
+  s.n = kf.view.n;
+  s.n_levels = kf.n_levels;
+  s.o_mem = put(&h->host, grid.members.data(), sizeof(FrameGrid::Member) * n);
+  s.o_start = put(&h->host, grid.start.data(), sizeof(int) * grid.start.size());
+  s.o_ur = put(&h->host, kf.view.u_right, sizeof(float) * n);
+  s.o_desc = put(&h->host, kf.view.desc, n * 32);
+  s.o_sf = put(&h->host, kf.view.scale_factors, sizeof(float) * (size_t)kf.n_levels);
+  s.o_sig = put(&h->host, kf.inv_level_sigma2, sizeof(float) * (size_t)kf.n_levels);
+}
+
+int plvs::fusejob::make_point_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
+                                      const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
+                                      bool host_entry, std::unique_ptr<Part>* out) {
+  out->reset();
+  int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc != PLVS_OK) return rc;
+  rc = check_handles(kfs, poses, n_kfs, 1, host_entry);
+  if (rc != PLVS_OK) return rc;
+  if (n_kfs > 0 && P->m > 0) out->reset(new PointPartKf(kfs, poses, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
+  return PLVS_OK;
+}
 
 int plvs::fusejob::make_point_part(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
                                    int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {

@@ -1,0 +1,157 @@
+"""Key frames resident in HBM (include/plvs_hip.h: plvs_keyframe) and the Fuse searches of LocalMapping::SearchInNeighbors over them.
+
+    kf = ResidentKeyFrame(points=FuseKeyFrame(...), lines=LineFuseKeyFrame(...))     # once, where the KeyFrame constructor ends
+    out = fuse_search_kf([kf, ...], [KeyFramePose(q_cw, Rcw, tcw, Ow), ...], points, th, skip)
+    kf.close()                                                                       # with the key frame, or on SetBadFlag
+
+A handle holds what the constructor fixes; the pose travels with each call.  Outputs are those of ORBmatcher.FuseSearch /
+LineMatcher.FuseSearch / FuseSearchPointsAndLines, with one more entry in stats: the bytes of the call's copy in."""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .linematcher import FuseLines, LineFuseKeyFrame, _fuse_outputs  # noqa: F401
+from .orbmatcher import FuseKeyFrame, FusePoints  # noqa: F401
+
+_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+HOST_ONLY = 1
+INFO = ("n_points", "n_lines", "device_bytes", "host_bytes", "flags", "device")
+
+
+class _PoseC(ctypes.Structure):
+    _fields_ = [("q_cw", _f * 4), ("Rcw", _f * 9), ("tcw", _f * 3), ("Ow", _f * 3)]
+
+
+@dataclass
+class KeyFramePose:
+    """GetPose() / GetCameraCenter() at the time of the call."""
+    q_cw: np.ndarray      # unit_quaternion().coeffs(): x, y, z, w (the point search's projection); None: zeros
+    Rcw: np.ndarray       # rotationMatrix() in Eigen's layout: 9, column-major (the line search's); None: zeros
+    tcw: np.ndarray
+    Ow: np.ndarray
+
+    def as_c(self):
+        f = lambda a, n: (_f * n)(*(np.zeros(n, np.float32) if a is None else np.asarray(a, np.float32).reshape(n)).tolist())
+        return _PoseC(f(self.q_cw, 4), f(self.Rcw, 9), f(self.tcw, 3), f(self.Ow, 3))
+
+
+def pose_of(points=None, lines=None):
+    """The pose a FuseKeyFrame and / or a LineFuseKeyFrame of the same key frame carry."""
+    src = points if points is not None else lines
+    return KeyFramePose(None if points is None else points.q_cw, None if lines is None else lines.Rcw, src.tcw, src.Ow)
+
+
+class ResidentKeyFrame:
+    """plvs_hip_keyframe_create: a deep copy of `points` and / or `lines` (their pose fields are not read), with both grids, on the
+    host and — unless host_only — in one device allocation."""
+
+    def __init__(self, points=None, lines=None, host_only=False):
+        self._h = _vp()
+        pc = None if points is None else points.as_c()
+        lc = None if lines is None else lines.as_c()
+        if pc is not None:
+            pc.q_cw = pc.tcw = pc.Ow = None      # the pose is the call's: create does not read these
+        if lc is not None:
+            lc.Rcw = lc.tcw = lc.Ow = None
+        f = _lib.lib.plvs_hip_keyframe_create
+        f.argtypes = [_vp, _vp, ctypes.c_uint32, _vp]
+        _lib.check(f(None if pc is None else ctypes.byref(pc), None if lc is None else ctypes.byref(lc), HOST_ONLY if host_only else 0,
+                     ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("the key frame handle is closed")
+        return self._h.value
+
+    def info(self):
+        out = np.zeros(6, np.int64)
+        f = _lib.lib.plvs_hip_keyframe_info
+        f.argtypes = [_vp, _vp]
+        _lib.check(f(self.handle, _lib.np_ptr(out)))
+        return dict(zip(INFO, out.tolist()))
+
+    def close(self):
+        if self._h:
+            f = _lib.lib.plvs_hip_keyframe_destroy
+            f.argtypes = [_vp]
+            h, self._h = self._h, _vp()
+            _lib.check(f(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _lists(key_frames, poses):
+    K = len(key_frames)
+    assert len(poses) == K
+    hs = (_vp * max(K, 1))(*[None if kf is None else kf.handle for kf in key_frames])
+    ps = (_PoseC * max(K, 1))(*[p.as_c() for p in poses])
+    return K, hs, ps
+
+
+def _stats4(out):
+    return out[:3] + (np.full(4, -1, np.int32),)
+
+
+def _single(name, key_frames, poses, items, th, skip, host, stream, want_reached, outputs):
+    K, hs, ps = _lists(key_frames, poses)
+    ic = items.as_c()
+    M = ic.m
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+    best_idx, best_dist, reached, stats = _stats4(_fuse_outputs(K, M, outputs, want_reached))
+    args = [hs if K else None, ps if K else None, K, ctypes.byref(ic), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
+            _lib.np_ptr(reached), _lib.np_ptr(stats)]
+    f = getattr(_lib.lib, name + ("_host" if host else ""))
+    f.argtypes = [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp] + ([] if host else [_vp])
+    if not host:
+        args.append(stream)
+    _lib.check(f(*args))
+    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+
+
+def fuse_search_kf(key_frames, poses, points, th=3.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """ORBmatcher.FuseSearch over resident key frames (plvs_hip_orb_fuse_search_kf / _kf_host): key frame k = (key_frames[k],
+    poses[k]).  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [4])."""
+    return _single("plvs_hip_orb_fuse_search_kf", key_frames, poses, points, th, skip, host, stream, want_reached, outputs)
+
+
+def line_fuse_search_kf(key_frames, poses, lines, th=3.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """LineMatcher.FuseSearch over resident key frames (plvs_hip_line_fuse_search_kf / _kf_host)."""
+    return _single("plvs_hip_line_fuse_search_kf", key_frames, poses, lines, th, skip, host, stream, want_reached, outputs)
+
+
+def fuse_search_points_and_lines_kf(key_frames, poses, points=None, th_points=3.0, skip_points=None, lines=None, th_lines=3.0,
+                                    skip_lines=None, stream=None):
+    """FuseSearchPointsAndLines over ONE list of resident key frames (plvs_hip_fuse_search_points_and_lines_kf).
+    -> (points' dict or None, lines' dict or None, stats [3]: launches, waits, bytes of the copy in)."""
+    K, hs, ps = _lists(key_frames, poses)
+    pc = lc = psk = lsk = None
+    p_out = l_out = (None, None, None, None)
+    if points is not None:
+        pc = points.as_c()
+        psk = None if skip_points is None else np.ascontiguousarray(skip_points, np.uint8).reshape(K, pc.m)
+        p_out = _stats4(_fuse_outputs(K, pc.m, True, True))
+    if lines is not None:
+        lc = lines.as_c()
+        lsk = None if skip_lines is None else np.ascontiguousarray(skip_lines, np.uint8).reshape(K, lc.m)
+        l_out = _stats4(_fuse_outputs(K, lc.m, True, True))
+    stats = np.full(3, -1, np.int32)
+    f = _lib.lib.plvs_hip_fuse_search_points_and_lines_kf
+    f.argtypes = [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]
+    _lib.check(f(hs if K else None, ps if K else None, K, None if pc is None else ctypes.byref(pc), _lib.np_ptr(psk), th_points,
+                 *[_lib.np_ptr(a) for a in p_out], None if lc is None else ctypes.byref(lc), _lib.np_ptr(lsk), th_lines,
+                 *[_lib.np_ptr(a) for a in l_out], _lib.np_ptr(stats), stream))
+    as_dict = lambda o: dict(best_idx=o[0], best_dist=o[1], reached=o[2], stats=o[3])
+    return (None if points is None else as_dict(p_out)), (None if lines is None else as_dict(l_out)), stats
