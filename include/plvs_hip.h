@@ -1265,7 +1265,12 @@ int plvs_hip_tsdf_voxblox_destroy(plvs_tsdf_voxblox* h);
 int plvs_hip_tsdf_voxblox_clear(plvs_tsdf_voxblox* h);
 /* xyz: n x 3 f32 camera-frame points (must be finite: PLVS's generator only
  * emits valid depths; PLVS_ERR_INVALID_ARG otherwise); rgba: n x 4 u8, the
- * r,g,b,a members of the pcl point; Twc 3x4 row-major. */
+ * r,g,b,a members of the pcl point; Twc 3x4 row-major.
+ * A map holds blocks with ids in [-2^19, 2^19) on every axis (voxel indices below 2^23 in magnitude: 419 km at 5 cm).
+ * Inside that range the results are the reference's bit for bit; a ray that enters a block outside it fails the call
+ * with PLVS_ERR_CAPACITY ("block id outside [-2^19, 2^19)"), as a full block pool does: the handle is then in a failed
+ * state — every integrate returns PLVS_ERR_INVALID_ARG — until plvs_hip_tsdf_voxblox_clear.  (The reference forms a voxel's
+ * centre in double, core/common.h:179-184; the kernels in float, which is the same number only for such indices.) */
 int plvs_hip_tsdf_voxblox_integrate(plvs_tsdf_voxblox* h, const float* xyz, const uint8_t* rgba,
                                     int n, const float* Twc);
 int plvs_hip_tsdf_voxblox_integrate_batch_dev(plvs_tsdf_voxblox* h, const float* d_xyz,
@@ -1334,7 +1339,12 @@ int plvs_hip_tsdf_voxblox_fast_rounds(plvs_tsdf_voxblox* h, int* rounds);
  * std::unordered_map<AnyIndex, ..., AnyIndexHash> filled in the mixed visiting order.  That order is produced on the
  * host by filling the same container (libstdc++'s, with the reference's hash) in the same sequence — it is the one
  * host step; validity / end voxel per point, the fold of each bundle, the rays and the voxel updates run on the
- * device.  Host pointers; synchronous.  Same arguments as plvs_hip_tsdf_voxblox_integrate. */
+ * device.  Host pointers; synchronous.  Same arguments as plvs_hip_tsdf_voxblox_integrate.
+ * A bundle's merged point is the mean of its points weighted by 1 / z^2 (weight 0 for |z| <= 1e-6): a bundle made only of
+ * weight-0 points has the merged point 0 / 0, which the reference casts a ray to all the same (voxel index (int)NaN).  Here
+ * such a cloud — finite though every point is — fails the call with PLVS_ERR_INVALID_ARG ("non-finite point in the cloud")
+ * before any voxel is changed; the handle is nevertheless left in the failed state of a failed integrate and needs
+ * plvs_hip_tsdf_voxblox_clear.  A depth camera delivers no such point. */
 int plvs_hip_tsdf_voxblox_integrate_merged(plvs_tsdf_voxblox* h, const float* xyz, const uint8_t* rgba, int n,
                                            const float* Twc);
 

@@ -199,8 +199,12 @@ static uint32_t blend(uint32_t c1, float w1, uint32_t c2, float w2) {
 static void update_voxel(const oracle_voxblox* o, const float origin[3], const float pG[3],
                          const int32_t g[3], uint32_t color, float weight, float* distance,
                          float* vweight, uint32_t* vcolor) {
-  const float center[3] = {((float)g[0] + 0.5f) * o->voxel_size, ((float)g[1] + 0.5f) * o->voxel_size,
-                           ((float)g[2] + 0.5f) * o->voxel_size};
+  /* getCenterPointFromGridIndex (common.h:179-184): (static_cast<FloatingPoint>(idx) + 0.5) * grid_size — the 0.5 is a
+   * double literal, so sum and product are binary64 and the Point takes ONE rounding to float.  Equal to the all-float
+   * form while (float)g + 0.5 is exact (|g| < 2^23); from there on it is not (tests/test_oracle_pinned_voxblox_edges.py). */
+  const float center[3] = {(float)(((double)(float)g[0] + 0.5) * (double)o->voxel_size),
+                           (float)(((double)(float)g[1] + 0.5) * (double)o->voxel_size),
+                           (float)(((double)(float)g[2] + 0.5) * (double)o->voxel_size)};
   /* computeDistance (:240-253) */
   const float vvo[3] = {center[0] - origin[0], center[1] - origin[1], center[2] - origin[2]};
   const float vpo[3] = {pG[0] - origin[0], pG[1] - origin[1], pG[2] - origin[2]};

@@ -175,7 +175,7 @@ int plvs_hip_tsdf_voxblox_upload_block(plvs_tsdf_voxblox* h, int bx, int by, int
   if (rc != PLVS_OK) return rc;
   if (h->h_ctr->err) {
     h->poisoned = true;
-    plvs::set_error("upload_block: %s", (h->h_ctr->err & kErrPoolFull) ? "block pool full (raise max_blocks)" : "block id out of range");
+    plvs::set_error("upload_block: %s", (h->h_ctr->err & kErrPoolFull) ? "block pool full (raise max_blocks)" : "block id outside [-2^19, 2^19)");
     return PLVS_ERR_CAPACITY;
   }
   const int slot = (int)h->h_ctr->total_visits;

@@ -237,7 +237,20 @@ PLVS_HD bool block_of(const Params& P, const int g[3], int b[3], int* vid) {
   return true;
 }
 
-// The order-independent part of updateTsdfVoxel: sdf and the (drop-off) weight.
+// Block ids a voxblox map accepts: [-2^19, 2^19) on every axis, half of what the directory can pack.  The reference forms
+// a voxel's centre as (static_cast<FloatingPoint>(idx) + 0.5) * grid_size with a DOUBLE 0.5 (common.h:179-184): sum and
+// product in binary64, one rounding to float.  visit_operands forms it in binary32.  For |idx| < 2^23 — every voxel of a
+// block in this range — (float)idx + 0.5 is exact in binary32, the product of two floats is exact in binary64, and both
+// forms round the same exact number once: the same float.  From |idx| = 2^23 on they differ, so the integrates refuse
+// such blocks (kErrCoordRange) instead of diverging.
+constexpr int kBlockIdLimit = 1 << 19;
+PLVS_HD bool block_id_in_range(int x, int y, int z) {
+  return ((((uint32_t)x + (uint32_t)kBlockIdLimit) | ((uint32_t)y + (uint32_t)kBlockIdLimit) |
+           ((uint32_t)z + (uint32_t)kBlockIdLimit)) >> 20) == 0u;
+}
+
+// The order-independent part of updateTsdfVoxel: sdf and the (drop-off) weight.  The centre in binary32: the reference's
+// float for every voxel of an accepted block (kBlockIdLimit).
 PLVS_HD void visit_operands(const Params& P, const float* origin, const float* pG, const int g[3],
                             float weight, float* sdf_out, float* uw_out) {
   const float c0 = ((float)g[0] + 0.5f) * P.voxel_size, c1 = ((float)g[1] + 0.5f) * P.voxel_size,

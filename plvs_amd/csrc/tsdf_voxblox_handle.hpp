@@ -144,7 +144,7 @@ static int vb_read_counters(plvs_tsdf_voxblox* h, hipStream_t s) {
 static int vb_fail(plvs_tsdf_voxblox* h, const char* call, uint32_t err, bool poison = true) {
   if (poison) h->poisoned = true;
   plvs::set_error("tsdf_voxblox %s: %s%s%s%s", call, (err & kErrPoolFull) ? "block pool full (raise max_blocks) " : "",
-                  (err & kErrCoordRange) ? "block id outside +-2^20 " : "",
+                  (err & kErrCoordRange) ? "block id outside [-2^19, 2^19) " : "",
                   (err & kErrNonFinite) ? "non-finite point in the cloud " : "",
                   (err & kErrDirectoryMiss) ? "a record for a block of another rank " : "");
   return (err & kErrNonFinite) ? PLVS_ERR_INVALID_ARG : PLVS_ERR_CAPACITY;

@@ -105,9 +105,12 @@ __global__ __launch_bounds__(256) void vb_ray_pass(
               lslot = dir_find(dir, b[0], b[1], b[2]);
               if (lslot < 0) atomicOr(&ctr->err, kErrDirectoryMiss);
             } else {
-              dir_insert(dir, b[0], b[1], b[2], &ctr->num_blocks, &ctr->err);
-              if (((g[0] - b[0] * 16) | (g[1] - b[1] * 16) | (g[2] - b[2] * 16)) & ~15)
-                atomicOr(&ctr->err, kErrCoordRange);  // float block lookup left the integer grid
+              // the float block lookup left the integer grid, or the block lies where the binary32 voxel centre is no
+              // longer the reference's (kBlockIdLimit): refused before it takes a slot
+              if ((((g[0] - b[0] * 16) | (g[1] - b[1] * 16) | (g[2] - b[2] * 16)) & ~15) || !block_id_in_range(b[0], b[1], b[2]))
+                atomicOr(&ctr->err, kErrCoordRange);
+              else
+                dir_insert(dir, b[0], b[1], b[2], &ctr->num_blocks, &ctr->err);
             }
           }
           if (ok && kFill) {
@@ -189,7 +192,14 @@ __global__ __launch_bounds__(kExpandThreads) void vb_expand(
       const float weight = fabsf(pz) > 1e-6f ? 1.0f / (pz * pz) : 0.0f;
       visit_operands(P, pose.t, pG, g, weight, &sdf, &uw);
     }
-    // uw >= 0: its sign bit marks the LAST record of the voxel run
+    // The sign bit of the stored weight marks the LAST record of the voxel run, so the weight's own sign is cleared
+    // first.  uw is never negative, but it can be -0.0: a point with |z| <= 1e-6 has weight 0, and behind the drop-off's
+    // zero crossing 0 * (negative) / (positive) is -0.0, which std::max(uw, 0) keeps.  The sign of such a zero moves to
+    // sdf: updateTsdfVoxel uses uw's sign only in the product sdf * uw (a weight sum or a blend factor takes +0.0 and
+    // -0.0 alike, W being +0.0 or positive) and sdf, beside that product, only as fabsf(sdf); (-sdf) * +0.0 is
+    // sdf * -0.0 bit for bit, so the folds give the reference's words — the sign of a zero distance included.
+    if (__float_as_uint(uw) == 0x80000000u) sdf = -sdf;
+    uw = fabsf(uw);
     rec[r] = make_float2(sdf, (key != next) ? -uw : uw);
     rec_c[r] = rgba[p];
   }
@@ -550,7 +560,7 @@ __global__ __launch_bounds__(kChainThreads) void vb_chain_chunks(
           w1n = w_prev / nw;
           w2n = uw / nw;
         }
-        s_opd[grp][g] = make_float4(skip ? -w_prev : w_prev, sdf * uw, y, nw);
+        s_opd[grp][g] = make_float4(skip ? -fabsf(w_prev) : fabsf(w_prev), sdf * uw, y, nw);   // (an uploaded weight can be -0.0)
         s_opc[grp][g] = make_float4(w1n, w2n, __uint_as_float(col), blend ? 1.0f : 0.0f);
       }
       __builtin_amdgcn_wave_barrier();
@@ -681,6 +691,11 @@ __global__ void vb_gather_slot_ids(const uint32_t* __restrict__ slots, int n,
 // One block id -> its pool slot, created if absent (plvs_hip_tsdf_voxblox_upload_block).
 __global__ void vb_block_slot_of(Directory dir, int x, int y, int z, VCounters* __restrict__ ctr, int32_t* __restrict__ slot_out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (!block_id_in_range(x, y, z)) {   // (a block no integrate would accept)
+    atomicOr(&ctr->err, kErrCoordRange);
+    *slot_out = -1;
+    return;
+  }
   dir_insert(dir, x, y, z, &ctr->num_blocks, &ctr->err);
   *slot_out = dir_find(dir, x, y, z);
 }

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void vb_shard_ray_pass(Params P, const float* 
           ray_step(&ray, g);
           if (!block_of(P, g, b, &vid)) continue;   // (P.shard_count = 1 here: never)
           unsigned long long key = 0;
-          const bool in_range = pack_block(b[0], b[1], b[2], &key) &&
+          const bool in_range = pack_block(b[0], b[1], b[2], &key) && block_id_in_range(b[0], b[1], b[2]) &&
                                 ((((g[0] - b[0] * 16) | (g[1] - b[1] * 16) | (g[2] - b[2] * 16)) & ~15) == 0);
           if (!kFill && !in_range) atomicOr(&ctr->err, kErrCoordRange);
           if (kFill) {

@@ -487,7 +487,7 @@ class TsdfVoxblox:
     """Thin RAII wrapper of the plvs_hip_tsdf_voxblox_* C ABI."""
 
     def __init__(self, voxel_size, use_carving=False, max_blocks=None, shard_rank=0, shard_count=1,
-                 max_ray_length=None, max_weight=None):
+                 max_ray_length=None, max_weight=None, truncation=None, min_ray_length=None):
         p = VoxbloxParams()
         _lib.check(_L.plvs_hip_tsdf_voxblox_default_params(ctypes.c_float(voxel_size), int(use_carving), ctypes.byref(p)))
         if max_blocks is not None:
@@ -496,6 +496,10 @@ class TsdfVoxblox:
             p.max_ray_length = float(max_ray_length)
         if max_weight is not None:          # TsdfIntegratorBase::Config::max_weight (10000 unless the caller says otherwise)
             p.max_weight = float(max_weight)
+        if truncation is not None:          # default_truncation_distance (0.1 in PointCloudMapVoxblox.cc:57)
+            p.truncation = float(truncation)
+        if min_ray_length is not None:
+            p.min_ray_length = float(min_ray_length)
         p.shard_rank, p.shard_count = int(shard_rank), int(shard_count)
         self.shard_rank, self.shard_count = int(shard_rank), int(shard_count)
         self.params = p

@@ -219,6 +219,35 @@ void hostvbx_integrate(HostVMap* m, const float* xyz, const uint8_t* rgba, int n
     }
   }
 }
+// The visits of one cloud as vb_expand sees them, in sequence order, without touching the map: the global voxel index
+// (g_out, 3 per visit) and visit_operands' (sdf, uw) (ops_out, 2 per visit) of the first `cap` visits.  Returns the number
+// of visits.  For tests that need to know what a cloud feeds the fold (a weight of -0.0, the lengths of the voxel runs).
+long long hostvbx_visit_log(HostVMap* m, const float* xyz, int n, const float* Twc, int32_t* g_out, float* ops_out, long long cap) {
+  namespace vbx = plvs::vbx;
+  vbx::PoseRt pose;
+  for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) pose.R[3 * i + j] = Twc[4 * i + j]; pose.t[i] = Twc[4 * i + 3]; }
+  vbx::quat_from_matrix(pose.R, pose.q);
+  long long v = 0;
+  for (int seq = 0; seq < n; ++seq) {
+    const int p = (int)vbx::mixed_index((uint32_t)seq, (uint32_t)n);
+    vbx::Ray ray;
+    if (!vbx::make_ray(m->P, pose, xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2], &ray)) continue;
+    for (int s = 0; s <= ray.steps; ++s) {
+      int g[3], b[3], vid;
+      vbx::ray_step(&ray, g);
+      if (!vbx::block_of(m->P, g, b, &vid)) continue;
+      const int gg[3] = {b[0] * 16 + (vid & 15), b[1] * 16 + ((vid >> 4) & 15), b[2] * 16 + (vid >> 8)};
+      float sdf, uw;
+      vbx::visit_operands(m->P, pose.t, ray.pG, gg, ray.weight, &sdf, &uw);
+      if (v < cap) {
+        g_out[3 * v] = gg[0]; g_out[3 * v + 1] = gg[1]; g_out[3 * v + 2] = gg[2];
+        ops_out[2 * v] = sdf; ops_out[2 * v + 1] = uw;
+      }
+      ++v;
+    }
+  }
+  return v;
+}
 long long hostvbx_last_visits(HostVMap* m) { return m->visits; }
 int hostvbx_num_chunks(HostVMap* m) { return (int)m->blocks.size(); }
 void hostvbx_chunk_ids(HostVMap* m, int32_t* ids) {

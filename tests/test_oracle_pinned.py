@@ -194,7 +194,9 @@ def _vlibs():
 @needs_vref
 def test_voxblox_raycaster_restatement_equals_the_reference_source():
     """RayCaster's constructor (ray end points for normal and clearing rays, carving on and off), setupRayCaster
-    and nextRayIndex of integrator_utils.cc against vb_ray_setup / vb_ray_next of oracle/tsdf_voxblox.c."""
+    and nextRayIndex of integrator_utils.cc against vb_ray_setup / vb_ray_next of oracle/tsdf_voxblox.c — at the
+    truncation distances and ray limits of tests/voxblox_edge_scenario.py too (one below the smallest voxel), and from
+    origins up to 30 km out, where a float coordinate resolves 2 mm."""
     ref, ora, f3 = _vlibs()
     rng = np.random.default_rng(99)
     cap = 4096
@@ -202,6 +204,8 @@ def test_voxblox_raycaster_restatement_equals_the_reference_source():
     total = 0
     for i in range(30000):
         origin = rng.uniform(-5, 5, 3).astype(np.float32)
+        if i % 3 == 0:
+            origin = (rng.uniform(-1, 1, 3) * 10.0 ** rng.uniform(1, np.log10(3e4), 3)).astype(np.float32)
         d = rng.normal(size=3)
         d /= np.linalg.norm(d)
         if i % 7 == 0:                               # axis-aligned rays: two t_to_next_boundary are infinite
@@ -214,10 +218,11 @@ def test_voxblox_raycaster_restatement_equals_the_reference_source():
         vs = float(rng.choice([0.02, 0.05, 0.1]))
         vsi = np.float32(1.0 / vs)                   # static_cast<FloatingPoint>(1.0 / voxel_size)
         clearing, carving = int(rng.integers(0, 2)), int(rng.integers(0, 2))
-        na = ref.ref_voxblox_raycast(f3(*origin), f3(*point), clearing, carving, 5.0, vsi, 0.1, a.ctypes.data, cap)
-        nb = ora.oracle_voxblox_raycast(f3(*origin), f3(*point), clearing, carving, 5.0, vsi, 0.1, b.ctypes.data, cap)
-        assert na == nb, (origin, point, vs, clearing, carving, na, nb)
-        assert np.array_equal(a[:min(na, cap)], b[:min(nb, cap)]), (origin, point, vs, clearing, carving)
+        trunc, max_ray = float(rng.choice([0.04, 0.1, 0.2])), float(rng.choice([2.5, 5.0]))
+        na = ref.ref_voxblox_raycast(f3(*origin), f3(*point), clearing, carving, max_ray, vsi, trunc, a.ctypes.data, cap)
+        nb = ora.oracle_voxblox_raycast(f3(*origin), f3(*point), clearing, carving, max_ray, vsi, trunc, b.ctypes.data, cap)
+        assert na == nb, (origin, point, vs, clearing, carving, trunc, max_ray, na, nb)
+        assert np.array_equal(a[:min(na, cap)], b[:min(nb, cap)]), (origin, point, vs, clearing, carving, trunc, max_ray)
         total += na
     assert total > 500000
 
