@@ -145,6 +145,23 @@ __device__ inline int dir_find_or_insert(const Directory& d, int x, int y, int z
   return slot;
 }
 
+// dir_find_or_insert for a caller whose blocks are nearly all in the map already, at their home entries: the entry's key
+// and slot are requested TOGETHER — both addresses follow from the hash alone — and a hit with a published slot costs one
+// global round trip instead of two.  The slot is used only under a matching key; a key that matches with the slot
+// still below zero, a miss and another block's entry all take dir_find_or_insert as if nothing had been read (a stale
+// line can only look emptier than the truth, see there).
+__device__ __forceinline__ int dir_find_or_insert_hit(const Directory& d, int x, int y, int z, int32_t* num_blocks,
+                                                      uint32_t* err) {
+  unsigned long long key;
+  if (pack_block(x, y, z, &key)) {
+    const uint32_t h = dir_hash(x, y, z, d.mask);
+    const unsigned long long cur = d.keys[h];
+    const int cached = d.slots[h];
+    if (cur == key && cached >= 0) return cached;
+  }
+  return dir_find_or_insert(d, x, y, z, num_blocks, err);
+}
+
 __device__ inline int dir_find(const Directory& d, int x, int y, int z) {
   unsigned long long key;
   if (!pack_block(x, y, z, &key)) return -1;

@@ -552,6 +552,41 @@ __device__ __forceinline__ bool grid_point(const GridSrc& g, const GridTile& t, 
   *z = d;
   return true;
 }
+// grid_point in three steps, for the set-up of a lean tile (walk_fast_tile): read through the pointer field by field
+// where each is used, the description cost a scalar round trip per field and the pixel two vector round trips in a row.
+//   grid_fetch       the fields the set-up reads, ALL requested before the first is used (the empty asm statement: the
+//                    values stand in scalar registers there, so the compiler can neither sink a field's load to its
+//                    use nor fetch the pointer again for it).  What the flush needs once more (key_bits, gw) it reads
+//                    through the pointer again — nothing of this copy is meant to live through the voxel loop, and
+//                    the members the set-up does not read (key_bits, the colour images') stay ZERO in it.
+//   grid_pixel_load  the pixel's depth and its (gx, gy), both in flight at once: the two addresses follow from the tile
+//                    and the thread alone.  Only for a pixel of the grid (false: neither is requested); a pixel whose
+//                    depth then fails the range test has read an entry of the 614 KB table it does not use.
+//                    Global loads: a pointer read from memory is generic to the compiler, and a flat load counts on
+//                    the LDS counter as well.
+//   grid_depth_ok    the range test, in double (:967)
+typedef float GridFloat2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ GridSrc grid_fetch(const GridSrc* __restrict__ gp) {
+  GridSrc g{};
+  g.depth = gp->depth; g.cam = gp->cam; g.image_stride = gp->image_stride; g.pitch = gp->pitch; g.step = gp->step;
+  g.gw = gp->gw; g.gh = gp->gh; g.ntx = gp->ntx; g.nty = gp->nty; g.min_depth = gp->min_depth; g.max_depth = gp->max_depth;
+  g.inv_ntx = gp->inv_ntx; g.inv_nty = gp->inv_nty;
+  asm volatile("" ::"s"(g.depth), "s"(g.cam), "s"(g.image_stride), "s"(g.pitch), "s"(g.step), "s"(g.gw), "s"(g.gh), "s"(g.ntx),
+               "s"(g.nty), "s"(g.min_depth), "s"(g.max_depth), "s"(g.inv_ntx), "s"(g.inv_nty));
+  return g;
+}
+__device__ __forceinline__ bool grid_pixel_load(const GridSrc& g, const GridTile& t, uint32_t rid, float* d, GridFloat2* c) {
+  const uint32_t m = t.row0 + rid / (uint32_t)kGridTileW, n = t.col0 + rid % (uint32_t)kGridTileW;
+  if (m >= g.gh || n >= g.gw) return false;
+  const auto* depth = (const __attribute__((address_space(1))) float*)(uintptr_t)g.depth;
+  const auto* cam = (const __attribute__((address_space(1))) GridFloat2*)(uintptr_t)g.cam;
+  *d = depth[(size_t)t.cloud * g.image_stride + (size_t)(m * g.step) * g.pitch + n * g.step];
+  *c = cam[m * g.gw + n];
+  return true;
+}
+__device__ __forceinline__ bool grid_depth_ok(const GridSrc& g, float d) {
+  return ((double)d > g.min_depth) && ((double)d < g.max_depth);
+}
 __device__ __forceinline__ uint32_t grid_order_key(const GridSrc& g, const GridTile& t, uint32_t rid) {
   return (t.cloud << g.key_bits) | ((t.row0 + rid / (uint32_t)kGridTileW) * g.gw + t.col0 + rid % (uint32_t)kGridTileW);
 }
@@ -1268,7 +1303,9 @@ __device__ __forceinline__ void walk_fast_tile(
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   // (tile = the local tile: output regions; listed_other = a listed tile that is not an overflow: passed on)
   const uint32_t gtile = tmap.tile_of(tile);             // its place in the point stream
-  const GridTile gt = grid ? grid_tile(*grid, gtile) : GridTile{0u, 0u, 0u};
+  // (kGrid: the set-up's copy of the grid description, one burst of scalar loads — grid_fetch)
+  const GridSrc gs = kGrid ? grid_fetch(grid_arg) : GridSrc{};
+  const GridTile gt = kGrid ? grid_tile(gs, gtile) : GridTile{0u, 0u, 0u};
   const TileSpan span = grid ? TileSpan{(int)gt.cloud, 0u, (uint32_t)kWalkRays}   // (a block of grid pixels of one image)
                       : tmap.tables ? tile_span_tables(offsets, nclouds, gtile, kWalkRays)   // (512 points of one cloud:
                                     : tile_span(offsets, nclouds, gtile, kWalkRays);          //  tsdf_directory.hpp)
@@ -1281,6 +1318,20 @@ __device__ __forceinline__ void walk_fast_tile(
   bool walks = false;
   int ox = 0, oy = 0, oz = 0;
   if (!defer) {
+    const Pose& pose = poses[cloud];   // (uniform address: scalar loads where it is used)
+    // kGrid: everything the ray is made of is requested here — the pixel's depth and (gx, gy) (grid_pixel_load) and the
+    // camera-to-world half of the pose, R and t, which is all make_ray reads — and waited for once, behind the reset of
+    // the tile's tables
+    float gd = 0.0f, pR[9], pt[3];
+    GridFloat2 gc = {0.0f, 0.0f};
+    bool gin = false;
+    if (kGrid) {
+      gin = grid_pixel_load(gs, gt, rid, &gd, &gc);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) pR[k] = pose.R[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) pt[k] = pose.t[k];
+    }
     subtile_reset(S, tid);
 #pragma unroll
     for (int k = 0; k < kWalkChunks * kSlabs / kWalkRays; ++k) S.rcnt[tid + k * kWalkRays] = 0u;
@@ -1291,9 +1342,19 @@ __device__ __forceinline__ void walk_fast_tile(
       S.vis_total = 0;
       S.any_cold = 0;
     }
-    const Pose& pose = poses[cloud];   // (uniform address: scalar loads where it is used)
     Ray ray;
-    walks = (uint32_t)tid < nrays && tile_ray_src(P, xyz, grid, gt, pose, first, rid, &ray, &ctr->err);
+    if (kGrid) {
+      asm volatile("" ::"s"(pR[0]), "s"(pR[1]), "s"(pR[2]), "s"(pR[3]), "s"(pR[4]), "s"(pR[5]), "s"(pR[6]), "s"(pR[7]), "s"(pR[8]),
+                   "s"(pt[0]), "s"(pt[1]), "s"(pt[2]));   // (as in grid_fetch: R and t in scalar registers here)
+      Pose cw{};
+#pragma unroll
+      for (int k = 0; k < 9; ++k) cw.R[k] = pR[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) cw.t[k] = pt[k];
+      walks = gin && grid_depth_ok(gs, gd) && ray_of_point(P, cw, gc.x * gd, gc.y * gd, gd, &ray, &ctr->err);
+    } else {
+      walks = (uint32_t)tid < nrays && tile_ray_src(P, xyz, grid, gt, pose, first, rid, &ray, &ctr->err);
+    }
     const float wu = walks ? P.weight / (2.0f * ray.truncation) : 0.0f;
     {   // origin of the voxel keys: below the start voxel of the first walking ray, on a chunk boundary
       const unsigned long long wm = __ballot(walks);
@@ -1391,7 +1452,7 @@ __device__ __forceinline__ void walk_fast_tile(
       if (slot < 0) {
         int cx, cy, cz;
         chunk_of_code(chunk_code(ekey[k]), ox, oy, oz, &cx, &cy, &cz);
-        slot = dir_find_or_insert(dir, cx, cy, cz, num_chunks, &ctr->err);
+        slot = dir_find_or_insert_hit(dir, cx, cy, cz, num_chunks, &ctr->err);
         if (slot >= 0) S.cslot[ci[k]] = slot;
       }
       if (slot < 0) continue;
