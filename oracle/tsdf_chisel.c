@@ -629,7 +629,7 @@ int oracle_chisel_carve(oracle_chisel* o, const float* depth, int width, int hei
           const float d = depth[(size_t)(int)v * (size_t)width + (size_t)(int)u];
           if (isnan(d)) continue;
           const float q = (o->tq * d * d + o->tl * d + o->tc) * o->ts;
-          const float trunc = q > diag ? q : diag;      /* std::max(truncator(depth), diag) */
+          const float trunc = q < diag ? diag : q;      /* std::max(truncator(depth), diag): a NaN q (depth +inf) stays NaN */
           const float surface = d - pc[2];
           if (surface > trunc + carving_dist) {
             if ((double)ch->sdf[i] < 1e-5) {

@@ -61,7 +61,10 @@ __global__ __launch_bounds__(256) void carve_chunks(Params P, CarveCamera C, con
     if (!(pc[2] < 0) && (u >= 0 && v >= 0 && u < C.width && v < C.height)) {
       const float d = depth[(size_t)(int)v * (size_t)C.iwidth + (size_t)(int)u];
       if (!isnan(d)) {
-        const float trunc = truncation_of(P, d);
+        // std::max(truncator(depth), diag) is (q < diag) ? diag : q: a depth of +inf makes q = inf - inf = NaN, which stays
+        // NaN and carves nothing (truncation_of's q > diag ? q : diag would floor it to diag and reset the voxel)
+        const float q = (P.tq * d * d + P.tl * d + P.tc) * P.ts;
+        const float trunc = q < P.diag ? P.diag : q;
         if (d - pc[2] > trunc + C.carving_dist && (double)sdf[a] < 1e-5) {
           sdf[a] = 99999.0f;   // DistVoxel::Reset
           weight[a] = 0.0f;

@@ -19,6 +19,17 @@ F = np.float32
 TRUNC = (0.0019, -0.00152, 0.001504, 6.0)      # ChiselServer.cpp:56-59
 
 
+# per-scan counters of the depth classes and voxel states a scan met (tests/chisel_scan_edge_scenario.py asserts on them):
+#   int_*   voxels INTEGRATED through a pixel of that class        on_*  voxels that project onto a pixel of that class
+#   cand_*  carving candidates (surfaceDist > truncation + carvingDist) by the state the voxel was in; *_reset of them reset
+CLASS_COUNTERS = ("int_pos_zero", "int_neg_zero", "int_negative", "int_tiny", "int_far", "int_pos_inf", "int_neg_inf",
+                  "on_pos_inf", "on_neg_inf", "on_nan", "on_negative", "int_cw4", "int_cw5", "int_cw255", "int_w_negative",
+                  "int_w_huge", "cand_sdf_f32_1e5", "cand_sdf_f32_1e5_reset", "cand_sdf_above_1e5", "cand_sdf_above_1e5_reset",
+                  "cand_sdf_below_1e5_reset", "cand_w_neg_zero", "cand_w_subnormal_reset", "cand_w_negative",
+                  "cand_w_tiny_reset")
+SDF_EDGE = np.float32(1e-5)                    # below the double 1e-5 the reference compares with
+
+
 def s3(a, b, c):
     return a + (b + c)
 
@@ -106,6 +117,30 @@ class ScanIntegrator:
             hit |= s3(v[:, 0] * n[p, 0], v[:, 1] * n[p, 1], v[:, 2] * n[p, 2]) + d[p] > 0
         return g[hit].astype(np.int32)
 
+    @staticmethod
+    def _count_classes(st, on, d, m1, m2, mr, sdf, w, cw):
+        neg0 = (d == 0) & np.signbit(d)
+        with np.errstate(all="ignore"):
+            cls = dict(pos_zero=(d == 0) & ~neg0, neg_zero=neg0, negative=d < 0, tiny=(d > 0) & (d < F(1e-3)), far=d == F(25.0),
+                       pos_inf=d == F(np.inf), neg_inf=d == F(-np.inf))
+            for k, m in cls.items():
+                st["int_" + k] += int((m1 & m).sum())
+            for k in ("pos_inf", "neg_inf", "negative"):
+                st["on_" + k] += int((on & cls[k]).sum())
+            st["on_nan"] += int((on & np.isnan(d)).sum())
+            for k, m in (("cw4", cw == 4), ("cw5", cw == 5), ("cw255", cw == 255), ("w_negative", w < 0), ("w_huge", w > F(1e29))):
+                st["int_" + k] += int((m1 & m).sum())
+            up = np.nextafter(SDF_EDGE, F(1))
+            tiny = np.finfo(F).tiny
+            for k, m in (("sdf_f32_1e5", sdf == SDF_EDGE), ("sdf_above_1e5", sdf == up)):
+                st["cand_" + k] += int((m2 & (w > 0) & m).sum())
+                st["cand_" + k + "_reset"] += int((mr & m).sum())
+            st["cand_sdf_below_1e5_reset"] += int((mr & (sdf == np.nextafter(SDF_EDGE, F(0)))).sum())
+            st["cand_w_neg_zero"] += int((m2 & (w == 0) & np.signbit(w)).sum())
+            st["cand_w_negative"] += int((m2 & (w < 0)).sum())
+            st["cand_w_subnormal_reset"] += int((mr & (w > 0) & (w < tiny)).sum())
+            st["cand_w_tiny_reset"] += int((mr & (w >= tiny) & (w < F(1e-14))).sum())
+
     # ---- one scan
     def integrate_scan(self, depth, bgr, Twc, slab=256):
         """-> dict(listed, created, kept, collected, integrated, reset, visits, updated [ids])"""
@@ -115,7 +150,8 @@ class ScanIntegrator:
         assert depth.shape == (c["height"], c["width"]) and bgr.shape[:2] == depth.shape and bgr.shape[2] in (3, 4)
         Twc = np.asarray(Twc, F).reshape(3, 4)
         ids = self.chunk_list(Twc)
-        st = dict(listed=len(ids), created=0, kept=0, collected=0, integrated=0, reset=0, visits=0, updated=[], zero_depth=0)
+        st = dict(listed=len(ids), created=0, kept=0, collected=0, integrated=0, reset=0, visits=0, updated=[], zero_depth=0,
+                  **{k: 0 for k in CLASS_COUNTERS})
         for a in range(0, len(ids), slab):
             self._slab(ids[a:a + slab], depth.reshape(-1), bgr.reshape(-1, bgr.shape[2]), Twc, st)
         st["collected"] = st["created"] - st["kept"]
@@ -152,6 +188,7 @@ class ScanIntegrator:
             for i, pl in enumerate(have):
                 if pl is not None:
                     sdf[i], w[i], kf[i], col[i] = pl
+            sdf0, w0 = sdf.copy(), w.copy()
             # colour (ColorVoxel::IntegrateSimple through ColorImage::AtBGR), only while the colour weight is below 5
             cw = col >> 24
             mc = m1 & (cw < 5)
@@ -172,6 +209,7 @@ class ScanIntegrator:
         st["integrated"] += int(m1.sum())
         st["reset"] += int(mr.sum())
         st["zero_depth"] += int((m1 & (d == 0)).sum())
+        self._count_classes(st, on, d, m1, m2, mr, sdf0, w0, cw)
         upd = (m1 | mr).any(1)
         for i, cid in enumerate(ids):
             key = tuple(int(x) for x in cid)

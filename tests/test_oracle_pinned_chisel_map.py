@@ -18,6 +18,7 @@ from tests.test_tsdf_loadmap import surface_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libchisel_full_ref.so")
+REF_SET_CHUNK = os.path.join(ROOT, "oracle", "_ref", "libchisel_set_chunk_ref.so")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(REF),
                                 reason="oracle/_ref/libchisel_full_ref.so (built where /root/reference exists) not present")
@@ -92,6 +93,13 @@ class RefChisel:
                np.empty(4096, np.uint32))
         ok = self.lib.ref_chisel_full_get_chunk(self.h, int(cx), int(cy), int(cz), *[_ptr(a) for a in out])
         return out if ok else None
+
+    def set_chunk(self, cx, cy, cz, sdf, weight, kfid, rgbw):
+        """Creates or overwrites one chunk through DistVoxel's and ColorVoxel's setters."""
+        a = [np.ascontiguousarray(p, t).reshape(4096) for p, t in zip((sdf, weight, kfid, rgbw), (np.float32, np.float32, np.uint32, np.uint32))]
+        lib = ctypes.CDLL(REF_SET_CHUNK)                         # (a library of its own beside REF, linked against it)
+        lib.ref_chisel_set_chunk.argtypes = [_vp, _i, _i, _i] + [_vp] * 4
+        lib.ref_chisel_set_chunk(self.h, int(cx), int(cy), int(cz), *[_ptr(x) for x in a])
 
     def deform(self, kfids, Rt):
         kfids = np.ascontiguousarray(kfids, np.uint32)
@@ -293,4 +301,72 @@ def test_deform_moves_the_stored_meshes_as_the_reference_library_does(oracle):
         total += len(v)
         moved += int((got_v != v).any(axis=1).sum())
     assert 0 < moved < total
+    ref.close()
+
+
+# ------------------------------------------------------------------ cameras with roll and pitch (tests/camera_attitudes.py)
+# Every pose above is a yaw about world z: no row of R^T (c - t), no frustum corner sum and no plane distance ever adds
+# three non-zero products there.  The cases below are shared with the GPU test of tests/test_tsdf_chisel_attitudes.py.
+def attitude_keyframes(cam, res=0.05, step=2):
+    """One key frame per pose of camera_attitudes.NAMES: the cloud PointCloudMapping would hand over (stride-`step` grid,
+    p = (gx d, gy d, d) for 0.1 < d < 5), its pose, and the full depth image."""
+    from tests import camera_attitudes as A
+    P = A.poses(res)
+    out = []
+    for k, name in enumerate(A.NAMES):
+        depth, bgr = A.render(P[name], cam, 500 + k)
+        d = depth[::step, ::step]
+        gx = ((np.arange(0, cam["width"], step) - cam["cx"]) / cam["fx"]).astype(np.float32)
+        gy = ((np.arange(0, cam["height"], step) - cam["cy"]) / cam["fy"]).astype(np.float32)
+        keep = (d > np.float32(0.1)) & (d < np.float32(5.0))
+        xyz = np.stack([gx[None, :] * d, gy[:, None] * d, d], -1)[keep]
+        out.append(dict(name=name, xyz=np.ascontiguousarray(xyz, np.float32), rgb=np.ascontiguousarray(bgr[::step, ::step, ::-1][keep]),
+                        kfid=np.full(len(xyz), k, np.uint32), Twc=P[name], depth=depth))
+    return out
+
+
+def carving_cases():
+    """-> (cam, chunks to upload first, [(key frame, depth image to carve with)]): the `depths` patches (+-inf, negative,
+    -0.0, 0, 1e-6, NaN, 25.0) and the seeded `voxel_states` chunks of tests/chisel_scan_edge_scenario.py, then every
+    attitude with its own depth image pushed back by 0.6 m (so that what the earlier key frames integrated is carved)."""
+    from tests import chisel_scan_edge_scenario as E
+    inp = E.inputs()
+    cam = inp["cam"]
+    kfs = attitude_keyframes(cam)
+    by_name = {k["name"]: k for k in kfs}
+    steps = [(by_name["general"], f["depth"]) for f in inp["depths"][:3]]
+    steps += [(by_name["general"], f["depth"]) for f in inp["voxel_states"][1:]]
+    steps += [(k, k["depth"] + np.float32(0.6)) for k in kfs]
+    return cam, inp["chunks"], steps
+
+
+def test_integrate_point_cloud_under_roll_and_pitch_equals_the_reference_library(oracle):
+    cam = small_cam(4)
+    ref, ora = RefChisel(0.05, cam), oracle.chisel(0.05)
+    for kf in attitude_keyframes(cam):
+        assert len(kf["xyz"]) > 1000, kf["name"]
+        ref.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+        ora.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+        maps_identical(ref, ora)
+    assert maps_identical(ref, ora) > 50
+    ref.close()
+
+
+@pytest.mark.skipif(not os.path.exists(REF_SET_CHUNK),
+                    reason="oracle/_ref/libchisel_set_chunk_ref.so (built where /root/reference exists) not present")
+def test_carving_under_roll_and_pitch_with_edge_depths_and_seeded_voxels_equals_the_reference_library(oracle):
+    cam, chunks, steps = carving_cases()
+    ref, ora = RefChisel(0.05, cam, carving=True), oracle.chisel(0.05)
+    for cid, planes in chunks:
+        ref.set_chunk(*cid, *planes)
+        ora.set_chunk(*cid, *planes)
+    maps_identical(ref, ora)
+    carved = []
+    for kf, depth in steps:
+        ref.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"], depth=depth)
+        n, _ = ora.carve(depth, cam["fx"], cam["fy"], cam["cx"], cam["cy"], kf["Twc"])
+        carved.append(n)
+        ora.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+        maps_identical(ref, ora)
+    assert carved[0] > 0 and sum(c > 0 for c in carved[5:]) >= 4, carved      # seeded voxels; most attitudes carve
     ref.close()
