@@ -185,6 +185,14 @@ struct HostStage {
 };
 HostStage& thread_stage();
 
+// No call leaves with its copies or kernels still in flight on the thread's staging block (error returns): armed when the first of
+// them is issued, disarmed after the call's own wait.
+struct StreamGuard {
+  hipStream_t s = nullptr;
+  bool armed = false;
+  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
+};
+
 static inline unsigned ceil_div(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // Integer tuning knob from the environment (host thread counts), clamped to [lo, hi].

@@ -128,11 +128,6 @@ __global__ __launch_bounds__(256) void motion_project_kernel(MotionParams P, con
   }
 }
 
-struct StreamGuard {   // no call leaves with its kernels still writing into the thread's staging block (error returns)
-  hipStream_t s;
-  bool armed = false;
-  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
-};
 
 int run(const plvs_motion_poses* M, const plvs_frame_view* F, const float* cur_angle, const plvs_line_frame_view* LF,
         const plvs_motion_points* P, const plvs_motion_lines* L, const plvs_motion_policy* pol, const uint8_t* occupied_points,
@@ -233,7 +228,7 @@ int run(const plvs_motion_poses* M, const plvs_frame_view* F, const float* cur_a
     memcpy(st.pinned + o_lq, L->desc, (size_t)nl * 32);
     memcpy(st.pinned + o_lt, LF->descriptors, (size_t)NL * 32);
   }
-  StreamGuard guard{stream};
+  plvs::StreamGuard guard{stream};
   PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
   guard.armed = true;
   const int line_blocks = (int)plvs::ceil_div((size_t)nl, 256);

@@ -160,11 +160,6 @@ __global__ __launch_bounds__(256) void frustum_kernel(TrackParams P, const float
 
 thread_local int g_test_flip = -1;
 
-struct StreamGuard {   // no call leaves with its kernels still writing into the thread's staging block (error returns)
-  hipStream_t s;
-  bool armed = false;
-  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
-};
 
 struct SearchArgs {
   const plvs_frame_view* F;
@@ -289,7 +284,7 @@ int run(const plvs_track_camera* cam, const plvs_track_points* P, const plvs_tra
     memcpy(st.pinned + o_lq, L->desc, (size_t)ml * 32);
     memcpy(st.pinned + o_lt, LF->descriptors, (size_t)nl * 32);
   }
-  StreamGuard guard{stream};
+  plvs::StreamGuard guard{stream};
   PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
   guard.armed = true;
   const int line_blocks = (int)plvs::ceil_div((size_t)ml, 256);

@@ -8,14 +8,6 @@
 namespace plvs {
 namespace fusejob {
 
-namespace {
-struct StreamGuard {   // no call leaves with its kernels still writing into the thread's staging block
-  hipStream_t s;
-  bool armed = false;
-  ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
-};
-}  // namespace
-
 int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_only, int* launches, int* waits, size_t* copied) {
   Part* parts[2] = {a, b};
   if (launches) *launches = 0;
@@ -39,12 +31,15 @@ int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_o
     size_t in_at = 0, scratch_at = in_total, out_at = in_total + scratch_total;
     for (Part* p : parts) {
       if (!p || !p->device) continue;
-      p->fill(st.pinned, in_at, scratch_at, out_at);
+      p->in_at = in_at;
+      p->scratch_at = scratch_at;
+      p->out_at = out_at;
+      p->fill(st.pinned);
       in_at += p->in_bytes;
       scratch_at += p->scratch_bytes;
       out_at += p->out_bytes;
     }
-    StreamGuard guard{stream};
+    plvs::StreamGuard guard{stream};
     PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_total, hipMemcpyHostToDevice, stream));
     guard.armed = true;
     if (copied) *copied = in_total;
@@ -74,14 +69,11 @@ int run_parts(Part* a, Part* b, hipStream_t stream, bool own_stream, bool copy_o
   return PLVS_OK;
 }
 
-int run_part_on_host(Part* p) {
-  p->prepare();
-  p->device = false;
-  p->host_all();
-  const int rc = p->refused();
-  if (rc != PLVS_OK) return rc;
-  p->post();
-  return PLVS_OK;
+int run_single(Part* p, int32_t* stats, int n_stats, void* stream, bool on_host, bool copy_only) {
+  for (int s = 0; stats && s < n_stats; ++s) stats[s] = 0;
+  if (!p) return PLVS_OK;
+  p->on_host = on_host;
+  return run_parts(p, nullptr, static_cast<hipStream_t>(stream), stream == nullptr, copy_only, nullptr, nullptr);
 }
 
 }  // namespace fusejob

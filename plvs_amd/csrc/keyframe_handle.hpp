@@ -6,7 +6,7 @@
 // array 16-byte aligned.  The host copy serves the pairs the device hands back (predict_level's and theta's ambiguous marks), the
 // launch-free shapes and the _kf_host entries; the grids in it are built on the host at creation (the line grid needs the host's
 // atan2f, the point grid has to exist on the host anyway).  Immutable after creation: any number of threads may read it at once.
-// Internal to the library; orb_fuse.hip fills the point side, line_fuse.hip the line side, keyframe_resident.hip owns the life cycle.
+// Internal: orb_fuse.hip fills and reads the point side (ResidentPoints), line_fuse.hip the line side (ResidentLines), keyframe_resident.hip owns the life cycle.
 #pragma once
 #include <vector>
 

@@ -89,10 +89,7 @@ int plvs_hip_orb_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyf
                                 void* stream) {
   std::unique_ptr<fj::Part> part;
   const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, false, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (!part) return PLVS_OK;
-  return fj::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, stream, false);
 }
 
 int plvs_hip_line_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
@@ -100,28 +97,21 @@ int plvs_hip_line_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_key
                                  void* stream) {
   std::unique_ptr<fj::Part> part;
   const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, false, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (!part) return PLVS_OK;
-  return fj::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, stream, false);
 }
 
 int plvs_hip_orb_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
                                      const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
   std::unique_ptr<fj::Part> part;
   const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, true, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  return part ? fj::run_part_on_host(part.get()) : PLVS_OK;
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, nullptr, true);
 }
 
 int plvs_hip_line_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
                                       const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
   std::unique_ptr<fj::Part> part;
   const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, true, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  return part ? fj::run_part_on_host(part.get()) : PLVS_OK;
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, nullptr, true);
 }
 
 int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,

@@ -24,6 +24,7 @@
 namespace {
 
 namespace lf = plvs::linefuse;
+namespace fj = plvs::fusejob;
 using lf::Front;
 using lf::KfConst;
 using lf::Member;
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void line_fuse_window_resident_kernel(const Kf
   walk_pair(D.k, D.a, L, i, f, th, lane, out + pair);
 }
 
-// pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there: with_pose())
+// pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there)
 KfConst kf_const(const plvs_line_fuse_keyframe& kf, bool pose = true) {
   KfConst c;
   for (int i = 0; i < 9; ++i) c.R[i] = pose ? kf.Rcw[i] : 0.0f;
@@ -195,106 +196,172 @@ void make_grid(const plvs_line_fuse_keyframe& kf, const KfConst& c, lf::Grid* g)
 
 // the refusals of every entry that are not a key frame's: before anything is launched or written
 int check_call(const void* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
-  PLVS_REQUIRE(n_kfs >= 0 && L && L->m >= 0, "null lines / negative size");
-  PLVS_REQUIRE(best_idx && best_dist, "null output");
-  PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
-  PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
-  PLVS_REQUIRE((long long)n_kfs * L->m <= (1ll << 30), "more than 2^30 pairs");
-  PLVS_REQUIRE(L->m == 0 || (L->start && L->end && L->normal && L->max_dist && L->desc), "null map line array");
-  return PLVS_OK;
-}
-
-int check_args(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, float th, const int32_t* best_idx, const int32_t* best_dist) {
-  const int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
-  if (rc != PLVS_OK) return rc;
-  for (int k = 0; k < n_kfs; ++k) {
-    const int rk = plvs::kfhandle::check_line_keyframe(kfs[k], true);
-    if (rk != PLVS_OK) return rk;
-  }
-  return PLVS_OK;
-}
-
-lf::Result host_pair(const plvs_line_fuse_keyframe& kf, const KfConst& c, const lf::Grid& grid, const plvs_fuse_lines* L, int i, float th) {
-  const lf::KfGrid G{grid.start.data(), grid.members.data(), kf.view.descriptors, kf.view.line_scale_factors, kf.view.line_inv_level_sigma2};
-  return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
-                       th, 0, 0);
+  return fj::check_common(kfs, n_kfs, L ? L->m : -1, L && L->start && L->end && L->normal && L->max_dist && L->desc, th, best_idx, best_dist,
+                          "null lines / negative size", "null map line array");
 }
 
 const char* const kFullThetaMessage =
     "GetLineFeaturesInArea: search over the full theta interval (deltaTheta above pi / 2: the reference terminates here)";
 
-// nothing is written when a pair asks for the full theta interval
-int refused_full_theta(const std::vector<lf::Result>& results) {
-  for (const lf::Result& r : results)
-    if (r.reached == lf::kFullTheta) {
-      plvs::set_error("invalid argument: %s", kFullThetaMessage);
-      return PLVS_ERR_INVALID_ARG;
-    }
-  return PLVS_OK;
-}
+// One call's line search as a part of the staging block (fuse_jobs.hpp): everything that depends on the query and the outputs
+// alone.  Where a key frame comes from is its source's, one of the two subclasses below:
+// [the source's key-frame table | lines | skip | what else the source stages] copied in one piece, [records, posted into the pinned side]
+struct LinePart : fj::Part {
+  const int n_kfs;
+  const plvs_fuse_lines* const L;
+  const uint8_t* const skip;
+  const float th;
+  int32_t *const best_idx, *const best_dist;
+  uint8_t* const reached;
+  int32_t* const stats;
+  const int n_stats;   // 4: the source writes stats[3], the bytes it put into the call's copy in
 
-// the outputs from the results; -> pairs that reached the window
-int post_results(const std::vector<lf::Result>& results, int32_t* best_idx, int32_t* best_dist, uint8_t* reached) {
-  int windows = 0;
-  for (size_t p = 0; p < results.size(); ++p) {
-    best_idx[p] = results[p].best_idx;
-    best_dist[p] = results[p].best_dist;
-    if (reached) reached[p] = (uint8_t)results[p].reached;
-    if (results[p].reached >= lf::kEmptyWindow) ++windows;
-  }
-  return windows;
-}
-
-// One call's line search as a part of the staging block (fuse_jobs.hpp)
-struct LinePart : plvs::fusejob::Part {
-  const plvs_line_fuse_keyframe* kfs;
-  int n_kfs;
-  const plvs_fuse_lines* L;
-  const uint8_t* skip;
-  float th;
-  int32_t *best_idx, *best_dist;
-  uint8_t* reached;
-  int32_t* stats;
-
-  std::vector<lf::Grid> grids;
-  std::vector<KfDev> tab;
-  std::vector<lf::Result> results;
+  std::vector<lf::Result> results;   // held back: a full-theta pair refuses the call before anything is written
   size_t o_tab = 0, o_start = 0, o_end = 0, o_nrm = 0, o_maxd = 0, o_desc = 0, o_skip = 0;   // from the part's inputs
-  size_t in_at = 0, out_at = 0;                                                              // the part's places in the block
   int st_host = 0;
 
-  LinePart(const plvs_line_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_, float th_, int32_t* best_idx_,
-           int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
-      : kfs(kfs_), n_kfs(n_kfs_), L(L_), skip(skip_), th(th_), best_idx(best_idx_), best_dist(best_dist_), reached(reached_), stats(stats_) {}
+  LinePart(int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_, float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_,
+           int32_t* stats_, int n_stats_)
+      : n_kfs(n_kfs_), L(L_), skip(skip_), th(th_), best_idx(best_idx_), best_dist(best_dist_), reached(reached_), stats(stats_),
+        n_stats(n_stats_) {}
+
+  // ---- the key-frame source
+  virtual bool has_lines(int k) const = 0;
+  virtual void prepare_host() = 0;                // what host_pair needs whether or not anything is launched
+  virtual size_t table_entry() const = 0;         // bytes of one key frame in the table at o_tab
+  virtual void size_kfs(fj::Take&) {}             // only when something is launched: what the source stages behind the query
+  virtual void fill_kfs(char* p) = 0;             // the table and what size_kfs took; p: the part's inputs in the pinned block
+  virtual void launch_kfs(char* dev, const char* table, const FuseLines& FL, int2* rec, hipStream_t stream) = 0;
+  virtual lf::Result host_pair(int k, int i) = 0;   // one pair on the host: pair_host() over the source's grid and constants
+
+  lf::Result pair_host(const lf::KfGrid& G, const KfConst& c, int i) const {
+    return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
+                         th, 0, 0);
+  }
 
   size_t n_pairs() const { return (size_t)n_kfs * L->m; }
 
   void prepare() override {
+    const size_t m = (size_t)L->m;
+    prepare_host();
+    // anything for the device?  a pair that is not skipped, and a key frame that has key lines
+    bool any_lines = false;
+    for (int k = 0; k < n_kfs && !any_lines; ++k) any_lines = has_lines(k);
+    device = any_lines && fj::any_unskipped(skip, n_pairs()) && !on_host;
+    if (!device) return;
+    fj::Take take;
+    o_tab = take(table_entry() * (size_t)n_kfs);
+    o_start = take(sizeof(float) * 3 * m); o_end = take(sizeof(float) * 3 * m); o_nrm = take(sizeof(float) * 3 * m);
+    o_maxd = take(sizeof(float) * m); o_desc = take(m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    size_kfs(take);
+    in_bytes = take.at;
+    out_bytes = fj::up16(sizeof(int2) * n_pairs());
+  }
+
+  void fill(char* pinned) override {
+    const size_t m = (size_t)L->m;
+    char* p = pinned + in_at;
+    memcpy(p + o_start, L->start, sizeof(float) * 3 * m);
+    memcpy(p + o_end, L->end, sizeof(float) * 3 * m);
+    memcpy(p + o_nrm, L->normal, sizeof(float) * 3 * m);
+    memcpy(p + o_maxd, L->max_dist, sizeof(float) * m);
+    memcpy(p + o_desc, L->desc, m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+    fill_kfs(p);
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FuseLines FL{reinterpret_cast<const float*>(d + o_start), reinterpret_cast<const float*>(d + o_end),
+                       reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
+                       reinterpret_cast<const uint4*>(d + o_desc), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                       L->m, (int)n_pairs()};
+    launch_kfs(dev, d + o_tab, FL, reinterpret_cast<int2*>(pinned + out_at), stream);
+    PLVS_KERNEL_CHECK();
+    ++launches;
+    return PLVS_OK;
+  }
+
+  void host_all() override {
     const int m = L->m;
+    results.resize(n_pairs());
+    for (int k = 0; k < n_kfs; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        results[pair] = (skip && skip[pair]) ? lf::Result{-1, -1, lf::kSkipped} : host_pair(k, i);
+      }
+  }
+
+  void collect(const char* pinned) override {
+    const int m = L->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    results.resize(n_pairs());
+    lf::Result* res_out = results.data();
+    int host = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const fj::Record r = fj::unpack(rec[pair]);
+        lf::Result res{r.idx, r.dist, r.reached};
+        if (r.ambiguous) {   // the level or theta is the host's to decide: the pair once more, by the host entry's code
+          res = host_pair(k, i);
+          ++host;
+        }
+        res_out[pair] = res;
+      }
+    st_host += host;
+  }
+
+  int refused() override {   // nothing is written when a pair asks for the full theta interval
+    for (const lf::Result& r : results)
+      if (r.reached == lf::kFullTheta) {
+        plvs::set_error("invalid argument: %s", kFullThetaMessage);
+        return PLVS_ERR_INVALID_ARG;
+      }
+    return PLVS_OK;
+  }
+
+  void post() override {
+    int windows = 0;   // pairs that reached the window
+    for (size_t p = 0; p < results.size(); ++p) {
+      best_idx[p] = results[p].best_idx;
+      best_dist[p] = results[p].best_dist;
+      if (reached) reached[p] = (uint8_t)results[p].reached;
+      if (results[p].reached >= lf::kEmptyWindow) ++windows;
+    }
+    if (!stats) return;
+    stats[0] = st_host; stats[1] = windows; stats[2] = launches;
+    if (n_stats == 4) stats[3] = fj::copy_in_stat(*this);
+  }
+};
+
+// Key frames staged per call: the grids and constants built always (host_all reads them), a KfDev table, and behind the query every
+// key frame's members, cell starts, descriptors and levels
+struct StagedLines : LinePart {
+  const plvs_line_fuse_keyframe* const kfs;
+  std::vector<lf::Grid> grids;
+  std::vector<KfDev> tab;
+
+  StagedLines(const plvs_line_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_, float th_, int32_t* best_idx_,
+              int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
+      : LinePart(n_kfs_, L_, skip_, th_, best_idx_, best_dist_, reached_, stats_, 3), kfs(kfs_) {}
+
+  bool has_lines(int k) const override { return kfs[k].view.n > 0; }
+  size_t table_entry() const override { return sizeof(KfDev); }
+
+  void prepare_host() override {
     grids.resize((size_t)n_kfs);
     tab.resize((size_t)n_kfs);
-    bool any_lines = false;
     for (int k = 0; k < n_kfs; ++k) {
       tab[k].k = kf_const(kfs[k]);
       make_grid(kfs[k], tab[k].k, &grids[k]);
       tab[k].n_members = (int)grids[k].members.size();
       tab[k].pad = 0;
-      any_lines = any_lines || kfs[k].view.n > 0;
     }
-    // anything for the device?  a pair that is not skipped, and a key frame that has key lines
-    bool work = false;
-    if (any_lines && m > 0) {
-      if (!skip) work = true;
-      for (size_t p = 0; !work && p < n_pairs(); ++p) work = !skip[p];
-    }
-    device = work;
-    if (!device) return;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
-    o_start = take(sizeof(float) * 3 * (size_t)m); o_end = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
-    o_maxd = take(sizeof(float) * (size_t)m); o_desc = take((size_t)m * 32);
-    o_skip = take(skip ? n_pairs() : 0);
+  }
+
+  void size_kfs(fj::Take& take) override {
     for (int k = 0; k < n_kfs; ++k) {
       KfDev& D = tab[k];
       D.o_mem = take(sizeof(Member) * (size_t)D.n_members);
@@ -303,24 +370,12 @@ struct LinePart : plvs::fusejob::Part {
       D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_line_levels);
       D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_line_levels);
     }
-    in_bytes = at;
-    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
   }
 
-  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
-    in_at = in_at_;
-    out_at = out_at_;
-    const int m = L->m;
-    char* p = pinned + in_at;
+  void fill_kfs(char* p) override {
     std::vector<KfDev> abs_tab = tab;   // the kernel reads a key frame's arrays at offsets from the BLOCK's start
     for (KfDev& D : abs_tab) { D.o_mem += in_at; D.o_start += in_at; D.o_desc += in_at; D.o_sf += in_at; D.o_sig += in_at; }
     memcpy(p + o_tab, abs_tab.data(), sizeof(KfDev) * (size_t)n_kfs);
-    memcpy(p + o_start, L->start, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_end, L->end, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_nrm, L->normal, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_maxd, L->max_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_desc, L->desc, (size_t)m * 32);
-    if (skip) memcpy(p + o_skip, skip, n_pairs());
     for (int k = 0; k < n_kfs; ++k) {
       const KfDev& D = tab[k];
       const plvs_line_fuse_keyframe& kf = kfs[k];
@@ -334,193 +389,60 @@ struct LinePart : plvs::fusejob::Part {
     }
   }
 
-  int launch(char* dev, char* pinned, hipStream_t stream) override {
-    const char* d = dev + in_at;
-    const FuseLines FL{reinterpret_cast<const float*>(d + o_start), reinterpret_cast<const float*>(d + o_end),
-                       reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
-                       reinterpret_cast<const uint4*>(d + o_desc), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
-                       L->m, (int)n_pairs()};
+  void launch_kfs(char* dev, const char* table, const FuseLines& FL, int2* rec, hipStream_t stream) override {
     hipLaunchKernelGGL(line_fuse_window_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream, dev,
-                       reinterpret_cast<const KfDev*>(d + o_tab), FL, th, reinterpret_cast<int2*>(pinned + out_at));
-    PLVS_KERNEL_CHECK();
-    ++launches;
-    return PLVS_OK;
+                       reinterpret_cast<const KfDev*>(table), FL, th, rec);
   }
 
-  void host_all() override {
-    const int m = L->m;
-    results.resize(n_pairs());
-    for (int k = 0; k < n_kfs; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        results[pair] = (skip && skip[pair]) ? lf::Result{-1, -1, lf::kSkipped} : host_pair(kfs[k], tab[k].k, grids[k], L, i, th);
-      }
-  }
-
-  void collect(const char* pinned) override {
-    const int m = L->m, K = n_kfs;
-    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
-    results.resize(n_pairs());
-    lf::Result* res_out = results.data();
-    int host = 0;
-    for (int k = 0; k < K; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        const int2 r = rec[pair];
-        lf::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
-        if ((r.y >> 24) & 1) {   // the level or theta is the host's to decide: the pair once more, by the host entry's code
-          res = host_pair(kfs[k], tab[k].k, grids[k], L, i, th);
-          ++host;
-        }
-        res_out[pair] = res;
-      }
-    st_host += host;
-  }
-
-  int refused() override { return refused_full_theta(results); }
-
-  void post() override {
-    const int windows = post_results(results, best_idx, best_dist, reached);
-    if (stats) { stats[0] = st_host; stats[1] = windows; stats[2] = launches; }
+  lf::Result host_pair(int k, int i) override {
+    const plvs_line_frame_view& v = kfs[k].view;
+    return pair_host({grids[k].start.data(), grids[k].members.data(), v.descriptors, v.line_scale_factors, v.line_inv_level_sigma2}, tab[k].k, i);
   }
 };
 
 // ---------------------------------------------------------------------------------------------------- resident key frames
-KfConst with_pose(const KfConst& resident, const plvs_keyframe_pose& pose) {
-  KfConst c = resident;
-  for (int i = 0; i < 9; ++i) c.R[i] = pose.Rcw[i];
-  for (int i = 0; i < 3; ++i) { c.t[i] = pose.tcw[i]; c.Ow[i] = pose.Ow[i]; }
-  return c;
-}
-
 KfArrays arrays_at(const char* block, const plvs_keyframe::Lines& s) {
   return KfArrays{reinterpret_cast<const Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
                   reinterpret_cast<const uint4*>(block + s.o_desc), reinterpret_cast<const float*>(block + s.o_sf),
                   reinterpret_cast<const float*>(block + s.o_sig), s.n_members};
 }
 
-lf::Result host_pair(const plvs_keyframe& h, const KfConst& c, const plvs_fuse_lines* L, int i, float th) {
-  const KfArrays a = arrays_at(h.host.data(), h.ln);
-  const lf::KfGrid G{a.start, a.members, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig};
-  return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
-                       th, 0, 0);
-}
-
-// One call's line search over resident key frames as a part of the staging block (fuse_jobs.hpp):
-// [key-frame table: pose, constants, pointers into the handles' allocations | lines | skip] copied in one piece,
-// [records, posted into the pinned side].  Nothing of a key frame is built, staged or copied.
-struct LinePartKf : plvs::fusejob::Part {
-  const plvs_keyframe* const* kfs;
-  const plvs_keyframe_pose* poses;
-  int n_kfs;
-  const plvs_fuse_lines* L;
-  const uint8_t* skip;
-  float th;
-  int32_t *best_idx, *best_dist;
-  uint8_t* reached;
-  int32_t* stats;
-
+// Key frames resident in HBM (keyframe_handle.hpp): a KfRes table — pose, constants, pointers into the handles' allocations — and
+// nothing else.  Nothing of a key frame is built, staged or copied.
+struct ResidentLines : LinePart {
+  const plvs_keyframe* const* const kfs;
+  const plvs_keyframe_pose* const poses;
   std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
-  std::vector<lf::Result> results;
-  size_t o_tab = 0, o_start = 0, o_end = 0, o_nrm = 0, o_maxd = 0, o_desc = 0, o_skip = 0;
-  size_t in_at = 0, out_at = 0;
-  int st_host = 0;
 
-  LinePartKf(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_,
-             float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
-      : kfs(kfs_), poses(poses_), n_kfs(n_kfs_), L(L_), skip(skip_), th(th_), best_idx(best_idx_), best_dist(best_dist_), reached(reached_),
-        stats(stats_) {}
+  ResidentLines(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_,
+                float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
+      : LinePart(n_kfs_, L_, skip_, th_, best_idx_, best_dist_, reached_, stats_, 4), kfs(kfs_), poses(poses_) {}
 
-  size_t n_pairs() const { return (size_t)n_kfs * L->m; }
+  bool has_lines(int k) const override { return kfs[k]->ln.n > 0; }
+  size_t table_entry() const override { return sizeof(KfRes); }
 
-  void prepare() override {
-    const int m = L->m;
+  void prepare_host() override {
     consts.resize((size_t)n_kfs);
-    bool any_lines = false;
     for (int k = 0; k < n_kfs; ++k) {
-      consts[k] = with_pose(kfs[k]->ln.c, poses[k]);
-      any_lines = any_lines || kfs[k]->ln.n > 0;
+      KfConst& c = consts[k] = kfs[k]->ln.c;
+      for (int i = 0; i < 9; ++i) c.R[i] = poses[k].Rcw[i];
+      for (int i = 0; i < 3; ++i) { c.t[i] = poses[k].tcw[i]; c.Ow[i] = poses[k].Ow[i]; }
     }
-    bool work = false;   // a pair that is not skipped, and a key frame that has key lines
-    if (any_lines && m > 0) {
-      if (!skip) work = true;
-      for (size_t p = 0; !work && p < n_pairs(); ++p) work = !skip[p];
-    }
-    device = work;
-    if (!device) return;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    o_tab = take(sizeof(KfRes) * (size_t)n_kfs);
-    o_start = take(sizeof(float) * 3 * (size_t)m); o_end = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
-    o_maxd = take(sizeof(float) * (size_t)m); o_desc = take((size_t)m * 32);
-    o_skip = take(skip ? n_pairs() : 0);
-    in_bytes = at;
-    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
   }
 
-  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
-    in_at = in_at_;
-    out_at = out_at_;
-    const int m = L->m;
-    char* p = pinned + in_at;
+  void fill_kfs(char* p) override {
     KfRes* tab = reinterpret_cast<KfRes*>(p + o_tab);
     for (int k = 0; k < n_kfs; ++k) tab[k] = KfRes{consts[k], arrays_at(kfs[k]->dev, kfs[k]->ln)};
-    memcpy(p + o_start, L->start, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_end, L->end, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_nrm, L->normal, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_maxd, L->max_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_desc, L->desc, (size_t)m * 32);
-    if (skip) memcpy(p + o_skip, skip, n_pairs());
   }
 
-  int launch(char* dev, char* pinned, hipStream_t stream) override {
-    const char* d = dev + in_at;
-    const FuseLines FL{reinterpret_cast<const float*>(d + o_start), reinterpret_cast<const float*>(d + o_end),
-                       reinterpret_cast<const float*>(d + o_nrm), reinterpret_cast<const float*>(d + o_maxd),
-                       reinterpret_cast<const uint4*>(d + o_desc), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
-                       L->m, (int)n_pairs()};
+  void launch_kfs(char*, const char* table, const FuseLines& FL, int2* rec, hipStream_t stream) override {
     hipLaunchKernelGGL(line_fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const KfRes*>(d + o_tab), FL, th, reinterpret_cast<int2*>(pinned + out_at));
-    PLVS_KERNEL_CHECK();
-    ++launches;
-    return PLVS_OK;
+                       reinterpret_cast<const KfRes*>(table), FL, th, rec);
   }
 
-  void host_all() override {
-    const int m = L->m;
-    results.resize(n_pairs());
-    for (int k = 0; k < n_kfs; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        results[pair] = (skip && skip[pair]) ? lf::Result{-1, -1, lf::kSkipped} : host_pair(*kfs[k], consts[k], L, i, th);
-      }
-  }
-
-  void collect(const char* pinned) override {
-    const int m = L->m, K = n_kfs;
-    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
-    results.resize(n_pairs());
-    lf::Result* res_out = results.data();
-    int host = 0;
-    for (int k = 0; k < K; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        const int2 r = rec[pair];
-        lf::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
-        if ((r.y >> 24) & 1) {   // the level or theta is the host's to decide: the pair once more, on the handle's host copy
-          res = host_pair(*kfs[k], consts[k], L, i, th);
-          ++host;
-        }
-        res_out[pair] = res;
-      }
-    st_host += host;
-  }
-
-  int refused() override { return refused_full_theta(results); }
-
-  void post() override {
-    const int windows = post_results(results, best_idx, best_dist, reached);
-    if (stats) { stats[0] = st_host; stats[1] = windows; stats[2] = launches; stats[3] = plvs::fusejob::copy_in_stat(*this); }
+  lf::Result host_pair(int k, int i) override {   // on the handle's host copy
+    const KfArrays a = arrays_at(kfs[k]->host.data(), kfs[k]->ln);
+    return pair_host({a.start, a.members, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig}, consts[k], i);
   }
 };
 
@@ -566,19 +488,19 @@ int plvs::fusejob::make_line_part_kf(const plvs_keyframe* const* kfs, const plvs
                                      bool host_entry, std::unique_ptr<Part>* out) {
   out->reset();
   int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
+  if (rc == PLVS_OK) rc = check_handles(kfs, poses, n_kfs, 2, host_entry);
   if (rc != PLVS_OK) return rc;
-  rc = check_handles(kfs, poses, n_kfs, 2, host_entry);
-  if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && L->m > 0) out->reset(new LinePartKf(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
+  if (n_kfs > 0 && L->m > 0) out->reset(new ResidentLines(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
   return PLVS_OK;
 }
 
 int plvs::fusejob::make_line_part(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
                                   int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {
   out->reset();
-  const int rc = check_args(kfs, n_kfs, L, th, best_idx, best_dist);
+  int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
+  for (int k = 0; rc == PLVS_OK && k < n_kfs; ++k) rc = plvs::kfhandle::check_line_keyframe(kfs[k], true);
   if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && L->m > 0) out->reset(new LinePart(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
+  if (n_kfs > 0 && L->m > 0) out->reset(new StagedLines(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
   return PLVS_OK;
 }
 
@@ -586,21 +508,16 @@ extern "C" {
 
 int plvs_hip_line_fuse_search(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
                               int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream) {
-  std::unique_ptr<plvs::fusejob::Part> part;
+  std::unique_ptr<fj::Part> part;
   const int rc = plvs::fusejob::make_line_part(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = 0;
-  if (!part) return PLVS_OK;
-  return plvs::fusejob::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, false, nullptr, nullptr);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 3, stream, false);
 }
 
 int plvs_hip_line_fuse_search_host(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_lines* L, const uint8_t* skip, float th,
                                    int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
-  std::unique_ptr<plvs::fusejob::Part> part;
+  std::unique_ptr<fj::Part> part;
   const int rc = plvs::fusejob::make_line_part(kfs, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = 0;
-  return part ? plvs::fusejob::run_part_on_host(part.get()) : PLVS_OK;
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 3, nullptr, true);
 }
 
 }  // extern "C"

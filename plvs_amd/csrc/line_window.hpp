@@ -63,9 +63,9 @@ int matrix_wait(MatrixJob& J) {
   if (J.started) PLVS_HIP_TRY(hipStreamSynchronize(plvs::thread_stage().stream));
   return PLVS_OK;
 }
-struct MatrixGuard {   // no call leaves with its kernel still writing into the thread's staging block (error returns)
+struct MatrixGuard {   // a plvs::StreamGuard on the thread's own stream, armed for as long as the job says it has started
   MatrixJob& j;
-  ~MatrixGuard() { if (j.started) (void)hipStreamSynchronize(plvs::thread_stage().stream); }
+  ~MatrixGuard() { plvs::StreamGuard g{plvs::thread_stage().stream, j.started}; }
 };
 
 struct Rep { float theta, d, nx, ny; };

@@ -27,6 +27,7 @@ using plvs::fusepair::Front;
 using plvs::fusepair::KfConst;
 using plvs::orbwin::FrameGrid;
 namespace fp = plvs::fusepair;
+namespace fj = plvs::fusejob;
 
 constexpr int kMaxLevels = 64;
 constexpr int kPosBits = 23;   // a lane's key: distance (9 bits) above the enumeration position
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void fuse_window_resident_kernel(const KfRes* 
   walk_pair(D.k, D.a, P, i, f, th, lane, out + pair);
 }
 
-// with_pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there: with_pose())
+// pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there)
 KfConst kf_const(const plvs_fuse_keyframe& kf, bool pose = true) {
   KfConst c;
   for (int i = 0; i < 4; ++i) c.q[i] = pose ? kf.q_cw[i] : 0.0f;
@@ -196,30 +197,8 @@ KfConst kf_const(const plvs_fuse_keyframe& kf, bool pose = true) {
 
 // the refusals of every entry that are not a key frame's: before anything is launched or written
 int check_call(const void* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
-  PLVS_REQUIRE(n_kfs >= 0 && P && P->m >= 0, "null points / negative size");
-  PLVS_REQUIRE(best_idx && best_dist, "null output");
-  PLVS_REQUIRE(n_kfs == 0 || kfs, "null key frames");
-  PLVS_REQUIRE(th >= 0.0f && th <= 1.0e6f, "th outside [0, 1e6]");
-  PLVS_REQUIRE((long long)n_kfs * P->m <= (1ll << 30), "more than 2^30 pairs");
-  PLVS_REQUIRE(P->m == 0 || (P->pos && P->normal && P->min_dist && P->max_dist && P->desc), "null map point array");
-  return PLVS_OK;
-}
-
-int check_args(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, float th, const int32_t* best_idx, const int32_t* best_dist) {
-  const int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
-  if (rc != PLVS_OK) return rc;
-  for (int k = 0; k < n_kfs; ++k) {
-    const int rk = plvs::kfhandle::check_point_keyframe(kfs[k], true);
-    if (rk != PLVS_OK) return rk;
-  }
-  return PLVS_OK;
-}
-
-// one pair on the host (the host entry; the device entry's ambiguous pairs and launch-free calls)
-fp::Result host_pair(const plvs_fuse_keyframe& kf, const KfConst& c, const FrameGrid& grid, const plvs_fuse_points* P, int i, float th) {
-  const fp::KfGrid<FrameGrid::Member> G{grid.start.data(), grid.members.data(), kf.view.u_right, kf.view.desc, kf.view.scale_factors,
-                                        kf.inv_level_sigma2};
-  return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
+  return fj::check_common(kfs, n_kfs, P ? P->m : -1, P && P->pos && P->normal && P->min_dist && P->max_dist && P->desc, th, best_idx, best_dist,
+                          "null points / negative size", "null map point array");
 }
 
 struct Outputs {
@@ -232,67 +211,147 @@ struct Outputs {
   }
 };
 
-void host_all(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th, const Outputs& out, int* windows) {
-  const int m = P->m;
-  for (int k = 0; k < n_kfs; ++k) {
-    const FrameGrid grid(&kfs[k].view);
-    const KfConst c = kf_const(kfs[k]);
-    for (int i = 0; i < m; ++i) {
-      const size_t pair = (size_t)k * m + i;
-      const fp::Result r = (skip && skip[pair]) ? fp::Result{-1, -1, fp::kSkipped} : host_pair(kfs[k], c, grid, P, i, th);
-      out.put(pair, r);
-      if (r.reached >= fp::kEmptyWindow) ++*windows;
-    }
-  }
-}
+// One call's point search as a part of the staging block (fuse_jobs.hpp): everything that depends on the query and the outputs
+// alone.  Where a key frame comes from is its source's, one of the two subclasses below:
+// [the source's key-frame table | points | skip | what else the source stages] copied in one piece,
+// [the source's scratch, HBM only], [records, posted into the pinned side]
+struct PointPart : fj::Part {
+  const int n_kfs;
+  const plvs_fuse_points* const P;
+  const uint8_t* const skip;
+  const float th;
+  const Outputs out;
+  int32_t* const stats;
+  const int n_stats;   // 4: the source writes stats[3], the bytes it put into the call's copy in
 
-// test / measurement hook.  1: the projection in a launch of its own in front of the windows; 2: the copy in alone
-thread_local int g_chained = 0;
-
-// One call's point search as a part of the staging block (fuse_jobs.hpp):
-// [key-frame table | points | every key frame's members, cell starts, u_right, descriptors, levels] copied in one piece,
-// [fronts (chained layout), HBM only], [records, posted into the pinned side]
-struct PointPart : plvs::fusejob::Part {
-  const plvs_fuse_keyframe* kfs;
-  int n_kfs;
-  const plvs_fuse_points* P;
-  const uint8_t* skip;
-  float th;
-  Outputs out;
-  int32_t* stats;
-  int chained;
-
-  std::vector<FrameGrid> grids;
-  std::vector<KfDev> tab;
   size_t o_tab = 0, o_pos = 0, o_nrm = 0, o_mind = 0, o_maxd = 0, o_pd = 0, o_skip = 0;   // from the part's inputs
-  size_t in_at = 0, scratch_at = 0, out_at = 0;                                           // the part's places in the block
   int st_host = 0, st_windows = 0;
 
-  PointPart(const plvs_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_, float th_, const Outputs& out_,
-            int32_t* stats_)
-      : kfs(kfs_), n_kfs(n_kfs_), P(P_), skip(skip_), th(th_), out(out_), stats(stats_), chained(g_chained) {}
+  PointPart(int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_, float th_, const Outputs& out_, int32_t* stats_, int n_stats_)
+      : n_kfs(n_kfs_), P(P_), skip(skip_), th(th_), out(out_), stats(stats_), n_stats(n_stats_) {}
+
+  // ---- the key-frame source
+  virtual bool has_points(int k) const = 0;
+  virtual void prepare_host() {}                  // what host_pair needs whether or not anything is launched
+  virtual size_t table_entry() const = 0;         // bytes of one key frame in the table at o_tab
+  virtual void size_kfs(fj::Take&) {}             // only when something is launched: what the source stages behind the query, its scratch
+  virtual void fill_kfs(char* p) = 0;             // the table and what size_kfs took; p: the part's inputs in the pinned block
+  virtual int launch_kfs(char* dev, const char* table, const FusePoints& FP, int2* rec, hipStream_t stream) = 0;   // launch() checks and counts its last
+  virtual void host_at(int) {}                    // host_all arrives at key frame k
+  virtual fp::Result host_pair(int k, int i) = 0;   // one pair on the host: pair_host() over the source's grid and constants
+
+  fp::Result pair_host(const fp::KfGrid<FrameGrid::Member>& G, const KfConst& c, int i) const {
+    return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
+  }
 
   size_t n_pairs() const { return (size_t)n_kfs * P->m; }
 
   void prepare() override {
-    const int m = P->m;
+    const size_t m = (size_t)P->m;
+    prepare_host();
     // anything for the device?  a pair that is not skipped, in a key frame that has key points
     bool work = false;
-    for (int k = 0; k < n_kfs && !work; ++k) {
-      if (kfs[k].view.n == 0) continue;
-      if (!skip) { work = m > 0; continue; }
-      for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
-    }
-    device = work;
+    for (int k = 0; k < n_kfs && !work; ++k) work = has_points(k) && fj::any_unskipped(skip ? skip + k * m : nullptr, m);
+    device = work && !on_host;
     if (!device) return;
+    fj::Take take;
+    o_tab = take(table_entry() * (size_t)n_kfs);
+    o_pos = take(sizeof(float) * 3 * m); o_nrm = take(sizeof(float) * 3 * m);
+    o_mind = take(sizeof(float) * m); o_maxd = take(sizeof(float) * m); o_pd = take(m * 32);
+    o_skip = take(skip ? n_pairs() : 0);
+    size_kfs(take);
+    in_bytes = take.at;
+    out_bytes = fj::up16(sizeof(int2) * n_pairs());
+  }
+
+  void fill(char* pinned) override {
+    const size_t m = (size_t)P->m;
+    char* p = pinned + in_at;
+    memcpy(p + o_pos, P->pos, sizeof(float) * 3 * m);
+    memcpy(p + o_nrm, P->normal, sizeof(float) * 3 * m);
+    memcpy(p + o_mind, P->min_dist, sizeof(float) * m);
+    memcpy(p + o_maxd, P->max_dist, sizeof(float) * m);
+    memcpy(p + o_pd, P->desc, m * 32);
+    if (skip) memcpy(p + o_skip, skip, n_pairs());
+    fill_kfs(p);
+  }
+
+  int launch(char* dev, char* pinned, hipStream_t stream) override {
+    const char* d = dev + in_at;
+    const FusePoints FP{reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm),
+                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const float*>(d + o_maxd),
+                        reinterpret_cast<const uint4*>(d + o_pd), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
+                        P->m, (int)n_pairs()};
+    const int rc = launch_kfs(dev, d + o_tab, FP, reinterpret_cast<int2*>(pinned + out_at), stream);
+    if (rc != PLVS_OK) return rc;
+    PLVS_KERNEL_CHECK();
+    ++launches;
+    return PLVS_OK;
+  }
+
+  // nothing launched: every pair is still reported (a key frame without key points: the tests, then an empty window)
+  void host_all() override {
+    const int m = P->m;
+    for (int k = 0; k < n_kfs; ++k) {
+      host_at(k);
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const fp::Result r = (skip && skip[pair]) ? fp::Result{-1, -1, fp::kSkipped} : host_pair(k, i);
+        out.put(pair, r);
+        if (r.reached >= fp::kEmptyWindow) ++st_windows;
+      }
+    }
+  }
+
+  void collect(const char* pinned) override {
+    const int m = P->m, K = n_kfs;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
+    const Outputs o = out;            // (locals: the stores through the output pointers may alias this object's members)
+    int host = 0, windows = 0;
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < m; ++i) {
+        const size_t pair = (size_t)k * m + i;
+        const fj::Record r = fj::unpack(rec[pair]);
+        fp::Result res{r.idx, r.dist, r.reached};
+        if (r.ambiguous) {   // the level is the host's to decide: the pair once more, by the host entry's code
+          res = host_pair(k, i);
+          ++host;
+        }
+        o.put(pair, res);
+        if (res.reached >= fp::kEmptyWindow) ++windows;
+      }
+    st_host += host;
+    st_windows += windows;
+  }
+
+  void post() override {
+    if (!stats) return;
+    stats[0] = st_host; stats[1] = st_windows; stats[2] = launches;
+    if (n_stats == 4) stats[3] = fj::copy_in_stat(*this);
+  }
+};
+
+// test / measurement hook.  1: the projection in a launch of its own in front of the windows; 2: the copy in alone
+thread_local int g_chained = 0;
+
+// Key frames staged per call: a KfDev table, and behind the query every key frame's members, cell starts, u_right, descriptors and
+// levels; the fronts of the chained layout are its scratch
+struct StagedPoints : PointPart {
+  const plvs_fuse_keyframe* const kfs;
+  const int chained;
+  std::vector<FrameGrid> grids;   // launched: every key frame's, built only then.  host_all: the one of the key frame it is at
+  std::vector<KfDev> tab;         // the same, for the constants
+
+  StagedPoints(const plvs_fuse_keyframe* kfs_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_, float th_, const Outputs& out_,
+               int32_t* stats_)
+      : PointPart(n_kfs_, P_, skip_, th_, out_, stats_, 3), kfs(kfs_), chained(g_chained) {}
+
+  bool has_points(int k) const override { return kfs[k].view.n > 0; }
+  size_t table_entry() const override { return sizeof(KfDev); }
+
+  void size_kfs(fj::Take& take) override {
     grids.reserve((size_t)n_kfs);
     for (int k = 0; k < n_kfs; ++k) grids.emplace_back(&kfs[k].view);
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    o_tab = take(sizeof(KfDev) * (size_t)n_kfs);
-    o_pos = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
-    o_mind = take(sizeof(float) * (size_t)m); o_maxd = take(sizeof(float) * (size_t)m); o_pd = take((size_t)m * 32);
-    o_skip = take(skip ? n_pairs() : 0);
     tab.resize((size_t)n_kfs);
     for (int k = 0; k < n_kfs; ++k) {
       KfDev& D = tab[k];
@@ -306,26 +365,13 @@ struct PointPart : plvs::fusejob::Part {
       D.o_sf = take(sizeof(float) * (size_t)kfs[k].n_levels);
       D.o_sig = take(sizeof(float) * (size_t)kfs[k].n_levels);
     }
-    in_bytes = at;
-    scratch_bytes = chained == 1 ? ((sizeof(Front) * n_pairs() + 15) & ~(size_t)15) : 0;
-    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
+    scratch_bytes = chained == 1 ? fj::up16(sizeof(Front) * n_pairs()) : 0;
   }
 
-  void fill(char* pinned, size_t in_at_, size_t scratch_at_, size_t out_at_) override {
-    in_at = in_at_;
-    scratch_at = scratch_at_;
-    out_at = out_at_;
-    const int m = P->m;
-    char* p = pinned + in_at;
+  void fill_kfs(char* p) override {
     std::vector<KfDev> abs_tab = tab;   // the kernel reads a key frame's arrays at offsets from the BLOCK's start
     for (KfDev& D : abs_tab) { D.o_mem += in_at; D.o_start += in_at; D.o_ur += in_at; D.o_desc += in_at; D.o_sf += in_at; D.o_sig += in_at; }
     memcpy(p + o_tab, abs_tab.data(), sizeof(KfDev) * (size_t)n_kfs);
-    memcpy(p + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_mind, P->min_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_pd, P->desc, (size_t)m * 32);
-    if (skip) memcpy(p + o_skip, skip, n_pairs());
     for (int k = 0; k < n_kfs; ++k) {
       const KfDev& D = tab[k];
       const plvs_fuse_keyframe& kf = kfs[k];
@@ -340,14 +386,8 @@ struct PointPart : plvs::fusejob::Part {
     }
   }
 
-  int launch(char* dev, char* pinned, hipStream_t stream) override {
-    const char* d = dev + in_at;
-    const FusePoints FP{reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm),
-                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const float*>(d + o_maxd),
-                        reinterpret_cast<const uint4*>(d + o_pd), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
-                        P->m, (int)n_pairs()};
-    const KfDev* dtab = reinterpret_cast<const KfDev*>(d + o_tab);
-    int2* rec = reinterpret_cast<int2*>(pinned + out_at);
+  int launch_kfs(char* dev, const char* table, const FusePoints& FP, int2* rec, hipStream_t stream) override {
+    const KfDev* dtab = reinterpret_cast<const KfDev*>(table);
     if (chained == 1) {
       Front* fronts = reinterpret_cast<Front*>(dev + scratch_at);
       hipLaunchKernelGGL(fuse_front_kernel, dim3(plvs::ceil_div(n_pairs(), 256)), dim3(256), 0, stream, dtab, FP, fronts);
@@ -357,168 +397,66 @@ struct PointPart : plvs::fusejob::Part {
     } else {
       hipLaunchKernelGGL(fuse_window_kernel<false>, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream, dev, dtab, FP, th, nullptr, rec);
     }
-    PLVS_KERNEL_CHECK();
-    ++launches;
     return PLVS_OK;
   }
 
-  // nothing launched: every pair is still reported (a key frame without key points: the tests, then an empty window)
-  void host_all() override { ::host_all(kfs, n_kfs, P, skip, th, out, &st_windows); }
-
-  void collect(const char* pinned) override {
-    const int m = P->m, K = n_kfs;
-    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
-    const Outputs o = out;            // (locals: the stores through the output pointers may alias this object's members)
-    int host = 0, windows = 0;
-    for (int k = 0; k < K; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        const int2 r = rec[pair];
-        fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
-        if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, by the host entry's code
-          res = host_pair(kfs[k], tab[k].k, grids[k], P, i, th);
-          ++host;
-        }
-        o.put(pair, res);
-        if (res.reached >= fp::kEmptyWindow) ++windows;
-      }
-    st_host += host;
-    st_windows += windows;
+  void host_at(int k) override {
+    grids.clear();
+    grids.emplace_back(&kfs[k].view);
+    tab.assign(1, KfDev{kf_const(kfs[k])});
   }
-
-  void post() override {
-    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = launches; }
+  fp::Result host_pair(int k, int i) override {
+    const size_t at = device ? (size_t)k : 0;
+    const plvs_fuse_keyframe& kf = kfs[k];
+    return pair_host({grids[at].start.data(), grids[at].members.data(), kf.view.u_right, kf.view.desc, kf.view.scale_factors, kf.inv_level_sigma2},
+                     tab[at].k, i);
   }
 };
 
 // ---------------------------------------------------------------------------------------------------- resident key frames
-KfConst with_pose(const KfConst& resident, const plvs_keyframe_pose& pose) {
-  KfConst c = resident;
-  for (int i = 0; i < 4; ++i) c.q[i] = pose.q_cw[i];
-  for (int i = 0; i < 3; ++i) { c.t[i] = pose.tcw[i]; c.Ow[i] = pose.Ow[i]; }
-  return c;
-}
-
 KfArrays arrays_at(const char* block, const plvs_keyframe::Points& s) {
   return KfArrays{reinterpret_cast<const FrameGrid::Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
                   reinterpret_cast<const float*>(block + s.o_ur), reinterpret_cast<const uint4*>(block + s.o_desc),
                   reinterpret_cast<const float*>(block + s.o_sf), reinterpret_cast<const float*>(block + s.o_sig), s.n};
 }
 
-fp::Result host_pair(const plvs_keyframe& h, const KfConst& c, const plvs_fuse_points* P, int i, float th) {
-  const KfArrays a = arrays_at(h.host.data(), h.pt);
-  const fp::KfGrid<FrameGrid::Member> G{a.start, a.members, a.u_right, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig};
-  return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
-}
-
-// One call's point search over resident key frames as a part of the staging block (fuse_jobs.hpp):
-// [key-frame table: pose, constants, pointers into the handles' allocations | points | skip] copied in one piece,
-// [records, posted into the pinned side].  Nothing of a key frame is built, staged or copied.
-struct PointPartKf : plvs::fusejob::Part {
-  const plvs_keyframe* const* kfs;
-  const plvs_keyframe_pose* poses;
-  int n_kfs;
-  const plvs_fuse_points* P;
-  const uint8_t* skip;
-  float th;
-  Outputs out;
-  int32_t* stats;
-
+// Key frames resident in HBM (keyframe_handle.hpp): a KfRes table — pose, constants, pointers into the handles' allocations — and
+// nothing else.  Nothing of a key frame is built, staged or copied.
+struct ResidentPoints : PointPart {
+  const plvs_keyframe* const* const kfs;
+  const plvs_keyframe_pose* const poses;
   std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
-  size_t o_tab = 0, o_pos = 0, o_nrm = 0, o_mind = 0, o_maxd = 0, o_pd = 0, o_skip = 0;
-  size_t in_at = 0, out_at = 0;
-  int st_host = 0, st_windows = 0;
 
-  PointPartKf(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_,
-              float th_, const Outputs& out_, int32_t* stats_)
-      : kfs(kfs_), poses(poses_), n_kfs(n_kfs_), P(P_), skip(skip_), th(th_), out(out_), stats(stats_) {}
+  ResidentPoints(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_,
+                 float th_, const Outputs& out_, int32_t* stats_)
+      : PointPart(n_kfs_, P_, skip_, th_, out_, stats_, 4), kfs(kfs_), poses(poses_) {}
 
-  size_t n_pairs() const { return (size_t)n_kfs * P->m; }
+  bool has_points(int k) const override { return kfs[k]->pt.n > 0; }
+  size_t table_entry() const override { return sizeof(KfRes); }
 
-  void prepare() override {
-    const int m = P->m;
+  void prepare_host() override {
     consts.resize((size_t)n_kfs);
-    for (int k = 0; k < n_kfs; ++k) consts[k] = with_pose(kfs[k]->pt.c, poses[k]);
-    bool work = false;   // a pair that is not skipped, in a key frame that has key points
-    for (int k = 0; k < n_kfs && !work; ++k) {
-      if (kfs[k]->pt.n == 0) continue;
-      if (!skip) { work = m > 0; continue; }
-      for (int i = 0; i < m && !work; ++i) work = !skip[(size_t)k * m + i];
+    for (int k = 0; k < n_kfs; ++k) {
+      KfConst& c = consts[k] = kfs[k]->pt.c;
+      for (int i = 0; i < 4; ++i) c.q[i] = poses[k].q_cw[i];
+      for (int i = 0; i < 3; ++i) { c.t[i] = poses[k].tcw[i]; c.Ow[i] = poses[k].Ow[i]; }
     }
-    device = work;
-    if (!device) return;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-    o_tab = take(sizeof(KfRes) * (size_t)n_kfs);
-    o_pos = take(sizeof(float) * 3 * (size_t)m); o_nrm = take(sizeof(float) * 3 * (size_t)m);
-    o_mind = take(sizeof(float) * (size_t)m); o_maxd = take(sizeof(float) * (size_t)m); o_pd = take((size_t)m * 32);
-    o_skip = take(skip ? n_pairs() : 0);
-    in_bytes = at;
-    out_bytes = (sizeof(int2) * n_pairs() + 15) & ~(size_t)15;
   }
 
-  void fill(char* pinned, size_t in_at_, size_t, size_t out_at_) override {
-    in_at = in_at_;
-    out_at = out_at_;
-    const int m = P->m;
-    char* p = pinned + in_at;
+  void fill_kfs(char* p) override {
     KfRes* tab = reinterpret_cast<KfRes*>(p + o_tab);
     for (int k = 0; k < n_kfs; ++k) tab[k] = KfRes{consts[k], arrays_at(kfs[k]->dev, kfs[k]->pt)};
-    memcpy(p + o_pos, P->pos, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_nrm, P->normal, sizeof(float) * 3 * (size_t)m);
-    memcpy(p + o_mind, P->min_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_maxd, P->max_dist, sizeof(float) * (size_t)m);
-    memcpy(p + o_pd, P->desc, (size_t)m * 32);
-    if (skip) memcpy(p + o_skip, skip, n_pairs());
   }
 
-  int launch(char* dev, char* pinned, hipStream_t stream) override {
-    const char* d = dev + in_at;
-    const FusePoints FP{reinterpret_cast<const float*>(d + o_pos), reinterpret_cast<const float*>(d + o_nrm),
-                        reinterpret_cast<const float*>(d + o_mind), reinterpret_cast<const float*>(d + o_maxd),
-                        reinterpret_cast<const uint4*>(d + o_pd), skip ? reinterpret_cast<const uint8_t*>(d + o_skip) : nullptr,
-                        P->m, (int)n_pairs()};
+  int launch_kfs(char*, const char* table, const FusePoints& FP, int2* rec, hipStream_t stream) override {
     hipLaunchKernelGGL(fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const KfRes*>(d + o_tab), FP, th, reinterpret_cast<int2*>(pinned + out_at));
-    PLVS_KERNEL_CHECK();
-    ++launches;
+                       reinterpret_cast<const KfRes*>(table), FP, th, rec);
     return PLVS_OK;
   }
 
-  void host_all() override {
-    const int m = P->m;
-    for (int k = 0; k < n_kfs; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        const fp::Result r = (skip && skip[pair]) ? fp::Result{-1, -1, fp::kSkipped} : host_pair(*kfs[k], consts[k], P, i, th);
-        out.put(pair, r);
-        if (r.reached >= fp::kEmptyWindow) ++st_windows;
-      }
-  }
-
-  void collect(const char* pinned) override {
-    const int m = P->m, K = n_kfs;
-    const int2* rec = reinterpret_cast<const int2*>(pinned + out_at);
-    const Outputs o = out;
-    int host = 0, windows = 0;
-    for (int k = 0; k < K; ++k)
-      for (int i = 0; i < m; ++i) {
-        const size_t pair = (size_t)k * m + i;
-        const int2 r = rec[pair];
-        fp::Result res{r.x, (int)(int16_t)(r.y & 0xffff), (r.y >> 16) & 0xff};
-        if ((r.y >> 24) & 1) {   // the level is the host's to decide: the pair once more, on the handle's host copy
-          res = host_pair(*kfs[k], consts[k], P, i, th);
-          ++host;
-        }
-        o.put(pair, res);
-        if (res.reached >= fp::kEmptyWindow) ++windows;
-      }
-    st_host += host;
-    st_windows += windows;
-  }
-
-  void post() override {
-    if (stats) { stats[0] = st_host; stats[1] = st_windows; stats[2] = launches; stats[3] = plvs::fusejob::copy_in_stat(*this); }
+  fp::Result host_pair(int k, int i) override {   // on the handle's host copy
+    const KfArrays a = arrays_at(kfs[k]->host.data(), kfs[k]->pt);
+    return pair_host({a.start, a.members, a.u_right, reinterpret_cast<const uint8_t*>(a.desc), a.sf, a.sig}, consts[k], i);
   }
 };
 
@@ -559,19 +497,19 @@ int plvs::fusejob::make_point_part_kf(const plvs_keyframe* const* kfs, const plv
                                       bool host_entry, std::unique_ptr<Part>* out) {
   out->reset();
   int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
+  if (rc == PLVS_OK) rc = check_handles(kfs, poses, n_kfs, 1, host_entry);
   if (rc != PLVS_OK) return rc;
-  rc = check_handles(kfs, poses, n_kfs, 1, host_entry);
-  if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && P->m > 0) out->reset(new PointPartKf(kfs, poses, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
+  if (n_kfs > 0 && P->m > 0) out->reset(new ResidentPoints(kfs, poses, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
   return PLVS_OK;
 }
 
 int plvs::fusejob::make_point_part(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
                                    int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out) {
   out->reset();
-  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
+  int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
+  for (int k = 0; rc == PLVS_OK && k < n_kfs; ++k) rc = plvs::kfhandle::check_point_keyframe(kfs[k], true);
   if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && P->m > 0) out->reset(new PointPart(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
+  if (n_kfs > 0 && P->m > 0) out->reset(new StagedPoints(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
   return PLVS_OK;
 }
 
@@ -579,22 +517,16 @@ extern "C" {
 
 int plvs_hip_orb_fuse_search(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
                              int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, void* stream) {
-  std::unique_ptr<plvs::fusejob::Part> part;
-  const int rc = plvs::fusejob::make_point_part(kfs, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, &part);
-  if (rc != PLVS_OK) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = 0;
-  if (!part) return PLVS_OK;
-  return plvs::fusejob::run_parts(part.get(), nullptr, static_cast<hipStream_t>(stream), stream == nullptr, g_chained == 2, nullptr, nullptr);
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part(kfs, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, &part);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 3, stream, false, g_chained == 2);
 }
 
 int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip, float th,
                                   int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats) {
-  const int rc = check_args(kfs, n_kfs, P, th, best_idx, best_dist);
-  if (rc != PLVS_OK) return rc;
-  int windows = 0;
-  if (n_kfs > 0 && P->m > 0) host_all(kfs, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, &windows);
-  if (stats) { stats[0] = 0; stats[1] = windows; stats[2] = 0; }
-  return PLVS_OK;
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part(kfs, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, &part);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 3, nullptr, true);
 }
 
 void plvs_hip_orb_fuse_test_chained(int mode) { g_chained = (mode == 1 || mode == 2) ? mode : 0; }

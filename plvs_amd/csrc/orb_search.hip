@@ -63,10 +63,6 @@ int pairs_finish(PairsJob& J, const int32_t* pair_q, const int32_t* pair_t, int 
   memcpy(dist, st.pinned + J.o_d, sizeof(int32_t) * (size_t)npairs);
   return PLVS_OK;
 }
-struct PairsGuard {   // (an error return between begin and finish must not leave the copy in flight on the staging block)
-  bool armed = false;
-  ~PairsGuard() { if (armed) (void)hipStreamSynchronize(plvs::thread_stage().stream); }
-};
 
 extern "C" {
 
@@ -211,7 +207,7 @@ int plvs_hip_orb_search_by_bow(const plvs_featvec_view* KV, const uint8_t* kf_de
   std::vector<int32_t> pair_q, pair_t;
   // the descriptors are on their way to the device while the pairs are enumerated (a walk over the nodes alone bounds them)
   PairsJob job;
-  PairsGuard guard;
+  plvs::StreamGuard guard;   // (an error return between begin and finish must not leave the copy in flight on the staging block)
   {
     long long bound = 0;
     int a0 = 0, b0 = 0;
@@ -226,6 +222,7 @@ int plvs_hip_orb_search_by_bow(const plvs_featvec_view* KV, const uint8_t* kf_de
     if (bound == 0) return PLVS_OK;
     const int rcb = pairs_begin(job, kf_desc, kf_n, f_desc, f_n, (int)bound);
     if (rcb != PLVS_OK) return rcb;
+    guard.s = plvs::thread_stage().stream;
     guard.armed = true;
     pair_q.reserve((size_t)bound);
     pair_t.reserve((size_t)bound);

@@ -188,26 +188,29 @@ def _fuse_outputs(K, M, outputs, want_reached):
             np.full((K, M), 255, np.uint8) if want_reached else None, np.full(3, -1, np.int32))
 
 
+def _single_fuse_search(kf_c_type, name, key_frames, items, th, skip, host, stream, want_reached, outputs):
+    """One single-kind Fuse search, points or lines alike: entry `name` (host=True: name + "_host", no HIP call) over `key_frames` as
+    an array of kf_c_type.  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [3])."""
+    kfs = (kf_c_type * max(len(key_frames), 1))(*[kf.as_c() for kf in key_frames])
+    ic = items.as_c()
+    K, M = len(key_frames), ic.m
+    sk = None if skip is None else _u8(skip).reshape(K, M)
+    best_idx, best_dist, reached, stats = _fuse_outputs(K, M, outputs, want_reached)
+    args = [kfs if K else None, K, ctypes.byref(ic), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
+            _lib.np_ptr(reached), _lib.np_ptr(stats)]
+    f = getattr(_lib.lib, name + ("_host" if host else ""))
+    f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp] + ([] if host else [_vp])
+    if not host:
+        args.append(stream)
+    _lib.check(f(*args))
+    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+
+
 def _line_fuse_search(self, key_frames, lines, th=3.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
     """The search stage of LineMatcher::Fuse(pKF, vpMapLines, th) (src/LineMatcher.cc:2043-2276) for every key frame of
     `key_frames` at once.  skip [K,M]: !pML || isBad() || IsInKeyFrame(pKF).  host=True: plvs_hip_line_fuse_search_host (no
     HIP call).  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [3])."""
-    kfs = (_LineFuseKeyFrameC * max(len(key_frames), 1))(*[kf.as_c() for kf in key_frames])
-    lc = lines.as_c()
-    K, M = len(key_frames), lc.m
-    sk = None if skip is None else _u8(skip).reshape(K, M)
-    best_idx, best_dist, reached, stats = _fuse_outputs(K, M, outputs, want_reached)
-    args = [kfs if K else None, K, ctypes.byref(lc), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
-            _lib.np_ptr(reached), _lib.np_ptr(stats)]
-    if host:
-        f = _lib.lib.plvs_hip_line_fuse_search_host
-        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]
-    else:
-        f = _lib.lib.plvs_hip_line_fuse_search
-        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]
-        args.append(stream)
-    _lib.check(f(*args))
-    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+    return _single_fuse_search(_LineFuseKeyFrameC, "plvs_hip_line_fuse_search", key_frames, lines, th, skip, host, stream, want_reached, outputs)
 
 
 LineMatcher.FuseSearch = _line_fuse_search

@@ -249,25 +249,8 @@ def _fuse_search(self, key_frames, points, th=3.0, skip=None, host=False, stream
     """The search stage of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:1244-1408) for every key frame of
     `key_frames` at once.  skip [K,M]: !pMP || isBad() || IsInKeyFrame(pKF).  host=True: plvs_hip_orb_fuse_search_host (no
     HIP call).  -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [3])."""
-    kfs = (_FuseKeyFrameC * max(len(key_frames), 1))(*[kf.as_c() for kf in key_frames])
-    pc = points.as_c()
-    K, M = len(key_frames), pc.m
-    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
-    best_idx = np.full((K, M), -7, np.int32) if outputs else None
-    best_dist = np.full((K, M), -7, np.int32) if outputs else None
-    reached = np.full((K, M), 255, np.uint8) if want_reached else None
-    stats = np.full(3, -1, np.int32)
-    args = [kfs if K else None, K, ctypes.byref(pc), _lib.np_ptr(sk), th, _lib.np_ptr(best_idx), _lib.np_ptr(best_dist),
-            _lib.np_ptr(reached), _lib.np_ptr(stats)]
-    if host:
-        f = _lib.lib.plvs_hip_orb_fuse_search_host
-        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]
-    else:
-        f = _lib.lib.plvs_hip_orb_fuse_search
-        f.argtypes = [_vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]
-        args.append(stream)
-    _lib.check(f(*args))
-    return dict(best_idx=best_idx, best_dist=best_dist, reached=reached, stats=stats)
+    from .linematcher import _single_fuse_search   # (here: linematcher imports this module's C types the same way)
+    return _single_fuse_search(_FuseKeyFrameC, "plvs_hip_orb_fuse_search", key_frames, points, th, skip, host, stream, want_reached, outputs)
 
 
 ORBmatcher.FuseSearch = _fuse_search
