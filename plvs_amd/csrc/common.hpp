@@ -193,6 +193,13 @@ struct StreamGuard {
   ~StreamGuard() { if (armed) (void)hipStreamSynchronize(s); }
 };
 
+// The allocator of a share of a staging block: every array at a multiple of 16.
+static inline size_t up16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+struct Take {
+  size_t at = 0;
+  size_t operator()(size_t bytes) { const size_t o = at; at += up16(bytes); return o; }
+};
+
 static inline unsigned ceil_div(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // Integer tuning knob from the environment (host thread counts), clamped to [lo, hi].

@@ -17,6 +17,7 @@
 // orb_window_candidates — launched behind it on the same stream — reads it.
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "common.hpp"
@@ -27,7 +28,6 @@
 namespace {
 
 using plvs::orbwin::FrameGrid;
-using plvs::orbwin::WinFrame;
 using plvs::orbwin::WinQuery;
 using plvs::trackpose::V3;
 
@@ -128,42 +128,23 @@ __global__ __launch_bounds__(256) void motion_project_kernel(MotionParams P, con
   }
 }
 
+// ---- one call: what run() and its stages below hand on
+struct Call {
+  const plvs_frame_view* F; const float* cur_angle; const plvs_line_frame_view* LF;   // the entry's arguments
+  const plvs_motion_points* P; const plvs_motion_lines* L; const plvs_motion_policy* pol;
+  const uint8_t *occupied_points, *occupied_lines;
+  int32_t *assigned_points, *assigned_lines;
+  plvs_motion_result* res;
+  int n, nl;
+  MotionParams K;
+  int launches = 0, point_retries = 0, line_retries = 0, spills = 0;   // the stats
+  int larger_lines = 0;                                                // bLargerLineSearch after the points (:3636)
+  std::vector<uint8_t> pv, lv;                                         // the projection's fields, off the staging block
+  std::vector<float> pu, pvv, pz, proj6;
+  std::vector<int32_t> q_at, q_n, pair_t, dist;                        // the points' candidates, off the staging block
+};
 
-int run(const plvs_motion_poses* M, const plvs_frame_view* F, const float* cur_angle, const plvs_line_frame_view* LF,
-        const plvs_motion_points* P, const plvs_motion_lines* L, const plvs_motion_policy* pol, const uint8_t* occupied_points,
-        const uint8_t* occupied_lines, int32_t* assigned_points, int32_t* assigned_lines, plvs_motion_result* res, int32_t* stats,
-        int levels, hipStream_t stream, bool own_stream) {
-  const int n = P ? P->n : 0, nl = L ? L->n : 0;
-  int st_launches = 0, st_point_retries = 0, st_line_retries = 0, st_spills = 0;
-  auto post_stats = [&]() {
-    if (stats) { stats[0] = st_launches; stats[1] = st_point_retries; stats[2] = st_line_retries; stats[3] = st_spills; }
-  };
-  // ---- the two poses decide the level bands once, on the host (:1788-1795; the line matcher's :851-860 is the same expression)
-  plvs::trackpose::direction(M->q_lw, M->tlw, M->Ow, M->mb, M->mono, &res->forward, &res->backward);
-  res->th_used = pol->th;
-  int larger_lines = 0;
-  // no points to search (no last-frame point, or a frame without key points): the reference's first search returns 0, and so does
-  // its repetition at 2 * th (:3631-3640)
-  auto nothing_to_search = [&]() {
-    if (0 < pol->min_point_matches) {
-      larger_lines = 1;
-      ++st_point_retries;
-      res->th_used = 2 * pol->th;
-    }
-  };
-  if (n == 0 && nl == 0) {   // nothing to launch; the policy as below
-    nothing_to_search();
-    res->larger_line_search_used = larger_lines;
-    post_stats();
-    return PLVS_OK;
-  }
-  post_stats();
-  const bool search_points = n > 0 && F->n > 0;
-  const bool search_lines = nl > 0 && LF && LF->n > 0;
-  const int N = search_points ? F->n : 0, NL = search_lines ? LF->n : 0;
-  const bool matrix = search_lines && (long long)nl * NL <= plvs::linewin::kMatrixMaxPairs;
-  const int direction = res->forward ? 1 : (res->backward ? 2 : 0);
-
+MotionParams kernel_params(const plvs_motion_poses* M, const Call& c, bool make_queries) {
   MotionParams K;
   for (int i = 0; i < 4; ++i) K.q[i] = M->q_cw[i];
   for (int i = 0; i < 3; ++i) K.t[i] = M->tcw[i];
@@ -173,231 +154,215 @@ int run(const plvs_motion_poses* M, const plvs_frame_view* F, const float* cur_a
   K.lfx = KL[0]; K.lfy = KL[1]; K.lcx = KL[2]; K.lcy = KL[3];
   K.mbf = M->mbf;
   K.min_x = M->bounds4[0]; K.max_x = M->bounds4[1]; K.min_y = M->bounds4[2]; K.max_y = M->bounds4[3];
-  K.th = pol->th;
-  K.forward = res->forward; K.backward = res->backward;
-  K.n = n; K.nl = nl; K.point_blocks = (int)plvs::ceil_div((size_t)n, 256);
-  K.make_queries = search_points ? 1 : 0;
+  K.th = c.pol->th;
+  K.forward = c.res->forward; K.backward = c.res->backward;
+  K.n = c.n; K.nl = c.nl; K.point_blocks = (int)plvs::ceil_div((size_t)c.n, 256);
+  K.make_queries = make_queries ? 1 : 0;
+  return K;
+}
 
-  // ---- one staged block: [inputs, copied in one piece | window queries, HBM only | results, posted into the pinned side]
-  std::vector<FrameGrid> grid_holder;
-  if (search_points) grid_holder.emplace_back(F);
-  const FrameGrid* grid = search_points ? &grid_holder[0] : nullptr;
-  const size_t nm = search_points ? grid->members.size() : 0, nstart = search_points ? grid->start.size() : 0;
-  const size_t out_cap = (size_t)n * 32 + 4096;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_pts = take(sizeof(float) * 3 * (size_t)n), o_pvalid = take((size_t)n), o_poct = take(sizeof(int32_t) * (size_t)n);
-  const size_t o_lns = take(sizeof(float) * kLineIn * (size_t)nl), o_lvalid = take((size_t)nl);
-  const size_t o_sf = take(search_points ? sizeof(float) * (size_t)levels : 0);
-  const size_t o_mem = take(sizeof(FrameGrid::Member) * nm), o_start = take(sizeof(int) * nstart);
-  const size_t o_ur = take(sizeof(float) * (size_t)N), o_fd = take((size_t)N * 32), o_qd = take(search_points ? (size_t)n * 32 : 0);
-  const size_t o_cur = take(16);
-  const size_t o_lq = take(matrix ? (size_t)nl * 32 : 0), o_lt = take(matrix ? (size_t)NL * 32 : 0);
-  const size_t in_end = at;
-  const size_t o_wq = take(search_points ? sizeof(WinQuery) * (size_t)n : 0);
-  const size_t o_pout = take(sizeof(float) * kPointOut * (size_t)n), o_lout = take(sizeof(float) * kLineOut * (size_t)nl);
-  const size_t o_first = take(search_points ? sizeof(int32_t) * (size_t)n : 0), o_count = take(search_points ? sizeof(int32_t) * (size_t)n : 0);
-  const size_t o_rec = take(search_points ? sizeof(int2) * out_cap : 0);
-  const size_t o_mat = take(matrix ? sizeof(uint16_t) * (size_t)nl * (size_t)NL : 0);
-  plvs::HostStage& st = plvs::thread_stage();
-  PLVS_HIP_TRY(st.reserve(at + 16));
-  if (own_stream) stream = st.stream;
-
-  if (n) {
-    memcpy(st.pinned + o_pts, P->pos, sizeof(float) * 3 * (size_t)n);
-    memcpy(st.pinned + o_pvalid, P->valid, (size_t)n);
-    memcpy(st.pinned + o_poct, P->octave, sizeof(int32_t) * (size_t)n);
+// the element inputs: the points' arrays as they are, kLineIn floats per line, and the valid flags
+void pack_elements(const Call& c, char* pts, char* pvalid, char* poct, float* lin, char* lvalid) {
+  const plvs_motion_points* P = c.P; const plvs_motion_lines* L = c.L;
+  if (c.n) {
+    memcpy(pts, P->pos, sizeof(float) * 3 * (size_t)c.n);
+    memcpy(pvalid, P->valid, (size_t)c.n);
+    memcpy(poct, P->octave, sizeof(int32_t) * (size_t)c.n);
   }
-  float* lin = reinterpret_cast<float*>(st.pinned + o_lns);
-  for (int k = 0; k < nl; ++k) {
+  for (int k = 0; k < c.nl; ++k) {
     float* d = lin + (size_t)kLineIn * k;
     for (int j = 0; j < 3; ++j) { d[j] = L->start[3 * (size_t)k + j]; d[3 + j] = L->end[3 * (size_t)k + j]; }
     d[6] = L->max_dist[k];
   }
-  if (nl) memcpy(st.pinned + o_lvalid, L->valid, (size_t)nl);
-  if (search_points) {
-    memcpy(st.pinned + o_sf, F->scale_factors, sizeof(float) * (size_t)levels);
-    memcpy(st.pinned + o_mem, grid->members.data(), sizeof(FrameGrid::Member) * nm);
-    memcpy(st.pinned + o_start, grid->start.data(), sizeof(int) * nstart);
-    memcpy(st.pinned + o_ur, F->u_right, sizeof(float) * (size_t)N);
-    memcpy(st.pinned + o_fd, F->desc, (size_t)N * 32);
-    memcpy(st.pinned + o_qd, P->desc, (size_t)n * 32);
-  }
-  memset(st.pinned + o_cur, 0, 16);
-  if (matrix) {
-    memcpy(st.pinned + o_lq, L->desc, (size_t)nl * 32);
-    memcpy(st.pinned + o_lt, LF->descriptors, (size_t)NL * 32);
-  }
-  plvs::StreamGuard guard{stream};
-  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
-  guard.armed = true;
-  const int line_blocks = (int)plvs::ceil_div((size_t)nl, 256);
-  hipLaunchKernelGGL(motion_project_kernel, dim3(K.point_blocks + line_blocks), dim3(256), 0, stream, K,
-                     reinterpret_cast<const float*>(st.dev + o_pts), reinterpret_cast<const uint8_t*>(st.dev + o_pvalid),
-                     reinterpret_cast<const int32_t*>(st.dev + o_poct), reinterpret_cast<const float*>(st.dev + o_lns),
-                     reinterpret_cast<const uint8_t*>(st.dev + o_lvalid), reinterpret_cast<const float*>(st.dev + o_sf),
-                     reinterpret_cast<float*>(st.pinned + o_pout), reinterpret_cast<float*>(st.pinned + o_lout),
-                     reinterpret_cast<WinQuery*>(st.dev + o_wq));
-  PLVS_KERNEL_CHECK();
-  if (search_points) {   // the windows of every point, straight behind the kernel that wrote their queries
-    const WinFrame wf{reinterpret_cast<const FrameGrid::Member*>(st.dev + o_mem), reinterpret_cast<const int*>(st.dev + o_start),
-                      reinterpret_cast<const float*>(st.dev + o_ur), reinterpret_cast<const uint4*>(st.dev + o_fd),
-                      F->min_x, F->min_y, F->grid_w_inv, F->grid_h_inv};
-    hipLaunchKernelGGL(plvs::orbwin::orb_window_candidates, dim3(plvs::ceil_div((size_t)n, 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const WinQuery*>(st.dev + o_wq), n, wf, reinterpret_cast<const uint4*>(st.dev + o_qd),
-                       reinterpret_cast<uint32_t*>(st.dev + o_cur), reinterpret_cast<int32_t*>(st.pinned + o_first),
-                       reinterpret_cast<int32_t*>(st.pinned + o_count), reinterpret_cast<int2*>(st.pinned + o_rec), (uint32_t)out_cap);
-    PLVS_KERNEL_CHECK();
-    ++st_launches;
-  }
-  if (matrix) {   // depends on the descriptors alone
-    hipLaunchKernelGGL(plvs::linewin::hamming_matrix_kernel, dim3(plvs::ceil_div((size_t)nl * NL, 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint4*>(st.dev + o_lq), nl, reinterpret_cast<const uint4*>(st.dev + o_lt), NL,
-                       reinterpret_cast<uint16_t*>(st.pinned + o_mat));
-    PLVS_KERNEL_CHECK();
-  }
-  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
-  guard.armed = false;
+  if (c.nl) memcpy(lvalid, L->valid, (size_t)c.nl);
+}
 
-  // ---- the projection's fields leave the staging block
-  std::vector<uint8_t> pv((size_t)n), lv((size_t)nl);
-  std::vector<float> pu((size_t)n), pvv((size_t)n), pz((size_t)n), proj6((size_t)nl * 6);
-  const float* po = reinterpret_cast<const float*>(st.pinned + o_pout);
+// after the wait: the projection's fields leave the staging block, for the searches and for the caller
+void read_fields(Call& c, const float* po, const float* lo) {
+  const int n = c.n, nl = c.nl;
+  c.pv.resize((size_t)n); c.pu.resize((size_t)n); c.pvv.resize((size_t)n); c.pz.resize((size_t)n);
+  c.lv.resize((size_t)nl); c.proj6.resize((size_t)nl * 6);
   for (int i = 0; i < n; ++i) {
     const float* o = po + (size_t)kPointOut * i;
     int ok;
     memcpy(&ok, o + 3, 4);
-    pv[i] = (uint8_t)ok; pu[i] = o[0]; pvv[i] = o[1]; pz[i] = o[2];
+    c.pv[i] = (uint8_t)ok; c.pu[i] = o[0]; c.pvv[i] = o[1]; c.pz[i] = o[2];
   }
-  const float* lo = reinterpret_cast<const float*>(st.pinned + o_lout);
   for (int i = 0; i < nl; ++i) {
     const float* o = lo + (size_t)kLineOut * i;
     int ok;
     memcpy(&ok, o + 6, 4);
-    lv[i] = (uint8_t)ok;
-    for (int j = 0; j < 6; ++j) proj6[6 * (size_t)i + j] = o[j];
+    c.lv[i] = (uint8_t)ok;
+    for (int j = 0; j < 6; ++j) c.proj6[6 * (size_t)i + j] = o[j];
   }
   if (n) {
-    if (P->proj_valid) memcpy(P->proj_valid, pv.data(), (size_t)n);
-    if (P->u) memcpy(P->u, pu.data(), sizeof(float) * (size_t)n);
-    if (P->v) memcpy(P->v, pvv.data(), sizeof(float) * (size_t)n);
-    if (P->invz) memcpy(P->invz, pz.data(), sizeof(float) * (size_t)n);
+    if (c.P->proj_valid) memcpy(c.P->proj_valid, c.pv.data(), (size_t)n);
+    if (c.P->u) memcpy(c.P->u, c.pu.data(), sizeof(float) * (size_t)n);
+    if (c.P->v) memcpy(c.P->v, c.pvv.data(), sizeof(float) * (size_t)n);
+    if (c.P->invz) memcpy(c.P->invz, c.pz.data(), sizeof(float) * (size_t)n);
   }
   if (nl) {
-    if (L->proj_valid) memcpy(L->proj_valid, lv.data(), (size_t)nl);
-    if (L->proj6) memcpy(L->proj6, proj6.data(), sizeof(float) * 6 * (size_t)nl);
+    if (c.L->proj_valid) memcpy(c.L->proj_valid, c.lv.data(), (size_t)nl);
+    if (c.L->proj6) memcpy(c.L->proj6, c.proj6.data(), sizeof(float) * 6 * (size_t)nl);
   }
+}
 
-  // ---- the candidates of the points, and the line distances if a repeated launch is going to reuse the block
-  std::vector<int32_t> q_at((size_t)n, 0), q_n((size_t)n, 0), pair_t, dist, src((size_t)n);
+// no points to search (no last-frame point, or a frame without key points): the reference's first search returns 0, and so does
+// its repetition at 2 * th (:3631-3640)
+void nothing_to_search(Call& c) {
+  if (0 < c.pol->min_point_matches) { c.larger_lines = 1; ++c.point_retries; c.res->th_used = 2 * c.pol->th; }
+}
+
+// ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) over the candidates the call's launch left (or, where it spilled
+// with `found` candidates, over those of one more launch), and Tracking.cc:3631-3640
+int point_search(Call& c, const FrameGrid& grid, bool spilled, size_t found, plvs::linewin::MatrixStage& M) {
+  const plvs_motion_points* P = c.P; const plvs_frame_view* F = c.F;
+  const int n = c.n;
+  std::vector<int32_t> src((size_t)n);
   for (int i = 0; i < n; ++i) src[i] = i;
-  bool spilled = false;
-  size_t found = 0;
-  if (search_points) {
-    const int32_t* qf = reinterpret_cast<const int32_t*>(st.pinned + o_first);
-    const int32_t* qc = reinterpret_cast<const int32_t*>(st.pinned + o_count);
-    for (int i = 0; i < n; ++i) found += (size_t)qc[i];
-    spilled = found > out_cap;
-    if (!spilled) {
-      const int2* rec = reinterpret_cast<const int2*>(st.pinned + o_rec);
-      pair_t.resize(found);
-      dist.resize(found);
-      uint32_t w = 0;
-      for (int i = 0; i < n; ++i) {
-        q_at[i] = (int32_t)w;
-        q_n[i] = qc[i];
-        for (int c = 0; c < qc[i]; ++c) { pair_t[w + c] = rec[qf[i] + c].x; dist[w + c] = rec[qf[i] + c].y; }
-        w += (uint32_t)qc[i];
-      }
-    }
-  }
-  const uint16_t* mat = matrix ? reinterpret_cast<const uint16_t*>(st.pinned + o_mat) : nullptr;
-  std::vector<uint16_t> mat_keep;
-  auto keep_matrix = [&]() {   // before anything else uses the staging block
-    if (matrix && mat_keep.empty()) {
-      mat_keep.assign(mat, mat + (size_t)nl * (size_t)NL);
-      mat = mat_keep.data();
-    }
+  // the windows once more from the fields the host now holds (the projection kernel is not run again); the launch lays out the
+  // staging block anew: the matrix leaves it first
+  auto relaunch = [&](float th, size_t first_cap) -> int {
+    M.keep();
+    std::vector<WinQuery> wq;
+    for (int i = 0; i < n; ++i)
+      if (c.pv[i]) wq.push_back(plvs::orbwin::last_frame_query(c.pu[i], c.pvv[i], c.pz[i], P->octave[i], th, F->scale_factors[P->octave[i]],
+                                                               c.K.mbf, c.K.forward, c.K.backward, i));
+    std::vector<int32_t> qa, qn;
+    const int before = c.launches;
+    const int rc = plvs::orbwin::window_candidates(F, grid, wq, P->desc, n, qa, qn, c.pair_t, c.dist, first_cap, &c.launches);
+    if (rc != PLVS_OK) return rc;
+    if (c.launches - before > 1) c.spills += c.launches - before - 1;
+    std::fill(c.q_at.begin(), c.q_at.end(), 0);
+    std::fill(c.q_n.begin(), c.q_n.end(), 0);
+    for (size_t j = 0; j < wq.size(); ++j) { c.q_at[wq[j].src] = qa[j]; c.q_n[wq[j].src] = qn[j]; }
+    return PLVS_OK;
   };
-
-  // ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), and Tracking.cc:3631-3640
-  if (search_points) {
-    // the windows once more from the fields the host now holds (the projection kernel is not run again)
-    auto relaunch = [&](float th, size_t first_cap) -> int {
-      keep_matrix();
-      std::vector<WinQuery> wq;
-      for (int i = 0; i < n; ++i)
-        if (pv[i]) wq.push_back(plvs::orbwin::last_frame_query(pu[i], pvv[i], pz[i], P->octave[i], th, F->scale_factors[P->octave[i]], K.mbf,
-                                                               K.forward, K.backward, i));
-      std::vector<int32_t> qa, qn;
-      const int before = st_launches;
-      const int rc = plvs::orbwin::window_candidates(F, *grid, wq, P->desc, n, qa, qn, pair_t, dist, first_cap, &st_launches);
-      if (rc != PLVS_OK) return rc;
-      if (st_launches - before > 1) st_spills += st_launches - before - 1;
-      std::fill(q_at.begin(), q_at.end(), 0);
-      std::fill(q_n.begin(), q_n.end(), 0);
-      for (size_t j = 0; j < wq.size(); ++j) { q_at[wq[j].src] = qa[j]; q_n[wq[j].src] = qn[j]; }
-      return PLVS_OK;
-    };
-    auto greedy = [&]() {
-      for (int i = 0; i < N; ++i) assigned_points[i] = -1;
-      return plvs::orbwin::greedy_last_frame_points(F, cur_angle, src.data(), (size_t)n, q_at, q_n, pair_t, dist, P->angle, P->has_obs,
-                                                    pol->check_orientation, occupied_points, assigned_points);
-    };
-    if (spilled) {   // more candidates than the block had room for: once more with the room they need
-      ++st_spills;
-      const int rc = relaunch(pol->th, found + 64);
-      if (rc != PLVS_OK) { post_stats(); return rc; }
-    }
-    res->nmatches_points = greedy();
-    if (res->nmatches_points < pol->min_point_matches) {   // :3631
-      larger_lines = 1;
-      ++st_point_retries;
-      res->th_used = 2 * pol->th;
-      const int rc = relaunch(res->th_used, 0);
-      if (rc != PLVS_OK) { post_stats(); return rc; }
-      res->nmatches_points = greedy();
-    }
-  } else {
-    nothing_to_search();
+  auto greedy = [&]() {
+    for (int i = 0; i < F->n; ++i) c.assigned_points[i] = -1;
+    return plvs::orbwin::greedy_last_frame_points(F, c.cur_angle, src.data(), (size_t)n, c.q_at, c.q_n, c.pair_t, c.dist, P->angle, P->has_obs,
+                                                  c.pol->check_orientation, c.occupied_points, c.assigned_points);
+  };
+  if (spilled) {   // more candidates than the block had room for: once more with the room they need
+    ++c.spills;
+    const int rc = relaunch(c.pol->th, found + 64);
+    if (rc != PLVS_OK) return rc;
   }
+  c.res->nmatches_points = greedy();
+  if (c.res->nmatches_points < c.pol->min_point_matches) {   // :3631
+    c.larger_lines = 1;
+    ++c.point_retries;
+    c.res->th_used = 2 * c.pol->th;
+    const int rc = relaunch(c.res->th_used, 0);
+    if (rc != PLVS_OK) return rc;
+    c.res->nmatches_points = greedy();
+  }
+  return PLVS_OK;
+}
 
-  // ---- LineMatcher::SearchByProjection(CurrentFrame, LastFrame, bLargerSearch, bMono), and :3653-3662: windows and gates on the
-  // host from proj6; the distances have been in the pinned block since the wait
-  res->larger_line_search_used = larger_lines;
-  if (search_lines) {
-    const plvs::linewin::LineGrid lgrid(LF);
-    auto line_search = [&](int larger, int* nmatches) -> int {
-      plvs::linewin::Candidates C;
-      int rc = plvs::linewin::last_frame_line_candidates(LF, lgrid, nl, lv.data(), proj6.data(), L->octave, larger, direction, C);
-      if (rc != PLVS_OK) return rc;
-      if (matrix) {
-        C.dist.assign(C.q.size(), 0);
-        for (size_t c = 0; c < C.q.size(); ++c) C.dist[c] = (int)mat[(size_t)C.q[c] * (size_t)NL + (size_t)C.t[c]];
-      } else {
-        plvs::linewin::MatrixJob none;
-        rc = plvs::linewin::candidate_distances(LF, L->desc, nl, C, none);
-        if (rc != PLVS_OK) return rc;
-      }
-      for (int i = 0; i < NL; ++i) assigned_lines[i] = -1;
-      *nmatches = plvs::linewin::greedy_last_frame_lines(LF, nl, C, occupied_lines, L->has_obs, L->angle, pol->nn_ratio_lines,
-                                                         pol->check_orientation, assigned_lines);
-      return PLVS_OK;
-    };
-    int rc = line_search(larger_lines, &res->nmatches_lines);
-    if (rc != PLVS_OK) { post_stats(); return rc; }
-    if (res->nmatches_lines < pol->min_line_matches && !larger_lines) {   // :3654
-      ++st_line_retries;
-      res->larger_line_search_used = 1;
-      rc = line_search(1, &res->nmatches_lines);
-      if (rc != PLVS_OK) { post_stats(); return rc; }
-    }
-  } else if (nl > 0 && LF && 0 < pol->min_line_matches && !larger_lines) {
-    ++st_line_retries;   // (an empty line frame: both searches return 0)
-    res->larger_line_search_used = 1;
+// LineMatcher::SearchByProjection(CurrentFrame, LastFrame, bLargerSearch, bMono), and :3653-3662: windows and gates on the host from
+// proj6; the distances have been in the matrix since the wait
+int line_search(Call& c, bool search_lines, int direction, plvs::linewin::MatrixStage& M) {
+  const plvs_motion_lines* L = c.L; const plvs_line_frame_view* LF = c.LF;
+  c.res->larger_line_search_used = c.larger_lines;
+  if (!search_lines) {   // (an empty line frame: both searches return 0)
+    if (c.nl > 0 && LF && 0 < c.pol->min_line_matches && !c.larger_lines) { ++c.line_retries; c.res->larger_line_search_used = 1; }
+    return PLVS_OK;
+  }
+  const plvs::linewin::LineGrid lgrid(LF);
+  auto search = [&](int larger) -> int {
+    plvs::linewin::Candidates C;
+    int rc = plvs::linewin::last_frame_line_candidates(LF, lgrid, c.nl, c.lv.data(), c.proj6.data(), L->octave, larger, direction, C);
+    if (rc != PLVS_OK) return rc;
+    rc = plvs::linewin::candidate_distances(LF, L->desc, c.nl, C, M);
+    if (rc != PLVS_OK) return rc;
+    for (int i = 0; i < LF->n; ++i) c.assigned_lines[i] = -1;
+    c.res->nmatches_lines = plvs::linewin::greedy_last_frame_lines(LF, c.nl, C, c.occupied_lines, L->has_obs, L->angle, c.pol->nn_ratio_lines,
+                                                                  c.pol->check_orientation, c.assigned_lines);
+    return PLVS_OK;
+  };
+  int rc = search(c.larger_lines);
+  if (rc == PLVS_OK && c.res->nmatches_lines < c.pol->min_line_matches && !c.larger_lines) {   // :3654
+    ++c.line_retries;
+    c.res->larger_line_search_used = 1;
+    rc = search(1);
+  }
+  return rc;
+}
+
+int run(const plvs_motion_poses* M, const plvs_frame_view* F, const float* cur_angle, const plvs_line_frame_view* LF,
+        const plvs_motion_points* P, const plvs_motion_lines* L, const plvs_motion_policy* pol, const uint8_t* occupied_points,
+        const uint8_t* occupied_lines, int32_t* assigned_points, int32_t* assigned_lines, plvs_motion_result* res, int32_t* stats,
+        int levels, hipStream_t stream, bool own_stream) {
+  Call c{F, cur_angle, LF, P, L, pol, occupied_points, occupied_lines, assigned_points, assigned_lines, res, P ? P->n : 0, L ? L->n : 0};
+  const int n = c.n, nl = c.nl;
+  auto post_stats = [&]() {
+    if (stats) { stats[0] = c.launches; stats[1] = c.point_retries; stats[2] = c.line_retries; stats[3] = c.spills; }
+  };
+  // ---- the two poses decide the level bands once, on the host (:1788-1795; the line matcher's :851-860 is the same expression)
+  plvs::trackpose::direction(M->q_lw, M->tlw, M->Ow, M->mb, M->mono, &res->forward, &res->backward);
+  res->th_used = pol->th;
+  if (n == 0 && nl == 0) {   // nothing to launch; the policy as below
+    nothing_to_search(c);
+    res->larger_line_search_used = c.larger_lines;
+    post_stats();
+    return PLVS_OK;
   }
   post_stats();
-  return PLVS_OK;
+  const bool search_points = n > 0 && F->n > 0;
+  const bool search_lines = nl > 0 && LF && LF->n > 0;
+  const int direction = res->forward ? 1 : (res->backward ? 2 : 0);
+  c.K = kernel_params(M, c, search_points);
+
+  // ---- one staged block: [inputs, copied in one piece | window queries, HBM only | results, posted into the pinned side]
+  std::optional<FrameGrid> grid;
+  plvs::orbwin::WindowStage W;
+  if (search_points) W = plvs::orbwin::WindowStage{F, &grid.emplace(F), n, n, P->desc};
+  plvs::linewin::MatrixStage X;
+  if (search_lines) X = plvs::linewin::MatrixStage{L->desc, LF->descriptors, nl, LF->n};
+  plvs::Take take;
+  const size_t o_pts = take(sizeof(float) * 3 * (size_t)n), o_pvalid = take((size_t)n), o_poct = take(sizeof(int32_t) * (size_t)n);
+  const size_t o_lns = take(sizeof(float) * kLineIn * (size_t)nl), o_lvalid = take((size_t)nl);
+  const size_t o_sf = take(search_points ? sizeof(float) * (size_t)levels : 0);
+  W.take_inputs(take); X.take_inputs(take);
+  const size_t in_end = take.at;
+  W.take_scratch(take);
+  const size_t o_pout = take(sizeof(float) * kPointOut * (size_t)n), o_lout = take(sizeof(float) * kLineOut * (size_t)nl);
+  W.take_outputs(take); X.take_outputs(take);
+  plvs::HostStage& st = plvs::thread_stage();
+  PLVS_HIP_TRY(st.reserve(take.at + 16));
+  if (own_stream) stream = st.stream;
+
+  pack_elements(c, st.pinned + o_pts, st.pinned + o_pvalid, st.pinned + o_poct, reinterpret_cast<float*>(st.pinned + o_lns), st.pinned + o_lvalid);
+  if (search_points) memcpy(st.pinned + o_sf, F->scale_factors, sizeof(float) * (size_t)levels);
+  W.fill(st.pinned); X.fill(st.pinned);
+  plvs::StreamGuard guard{stream};
+  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
+  guard.armed = true;
+  const int line_blocks = (int)plvs::ceil_div((size_t)nl, 256);
+  hipLaunchKernelGGL(motion_project_kernel, dim3(c.K.point_blocks + line_blocks), dim3(256), 0, stream, c.K,
+                     reinterpret_cast<const float*>(st.dev + o_pts), reinterpret_cast<const uint8_t*>(st.dev + o_pvalid),
+                     reinterpret_cast<const int32_t*>(st.dev + o_poct), reinterpret_cast<const float*>(st.dev + o_lns),
+                     reinterpret_cast<const uint8_t*>(st.dev + o_lvalid), reinterpret_cast<const float*>(st.dev + o_sf),
+                     reinterpret_cast<float*>(st.pinned + o_pout), reinterpret_cast<float*>(st.pinned + o_lout), W.queries(st.dev));
+  PLVS_KERNEL_CHECK();
+  int rc = W.launch(st.dev, st.pinned, stream);   // the windows of every point, straight behind the kernel that wrote their queries
+  if (rc != PLVS_OK) return rc;
+  c.launches += search_points ? 1 : 0;
+  if ((rc = X.launch(st.dev, st.pinned, stream)) != PLVS_OK) return rc;
+  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
+  guard.armed = false;
+
+  // ---- the fields and the candidates of the points leave the staging block; the matrix stays until a launch wants the block (keep())
+  read_fields(c, reinterpret_cast<const float*>(st.pinned + o_pout), reinterpret_cast<const float*>(st.pinned + o_lout));
+  c.q_at.assign((size_t)n, 0); c.q_n.assign((size_t)n, 0);
+  size_t found = 0;
+  const bool spilled = search_points && !W.unpack(st.pinned, &found, c.q_at, c.q_n, c.pair_t, c.dist);
+  if (search_points) rc = point_search(c, *grid, spilled, found, X);
+  else nothing_to_search(c);
+  if (rc == PLVS_OK) rc = line_search(c, search_lines, direction, X);
+  post_stats();
+  return rc;
 }
 
 }  // namespace

@@ -311,7 +311,7 @@ int line_matches(const plvs_keyline* klu, const uint8_t* desc, int n, const plvs
   P.nn_ratio = nn_ratio;
   P.check_orientation = check_orientation;
   P.descriptor_dist = descriptor_dist;
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  using plvs::up16;
   const size_t o_dl = 0, o_dr = o_dl + up16(32 * (size_t)n), o_ll = o_dr + up16(32 * (size_t)n_right),
                o_lr = o_ll + up16(4 * kLineWords * (size_t)n), o_s2 = o_lr + up16(4 * kLineWords * (size_t)n_right),
                o_out = o_s2 + up16(4 * (size_t)n_levels), b_out = up16(4 * (4 * (size_t)n + 1)), o_hold = o_out + b_out,

@@ -16,6 +16,7 @@
 // writes its point's window query in HBM, where orb_window_candidates — launched behind it on the same stream — reads it.
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <vector>
 
 #include "common.hpp"
@@ -26,7 +27,6 @@
 namespace {
 
 using plvs::orbwin::FrameGrid;
-using plvs::orbwin::WinFrame;
 using plvs::orbwin::WinQuery;
 
 constexpr int kPointIn = 8;     // pos[3], normal[3], mfMinDistance, mfMaxDistance
@@ -160,7 +160,6 @@ __global__ __launch_bounds__(256) void frustum_kernel(TrackParams P, const float
 
 thread_local int g_test_flip = -1;
 
-
 struct SearchArgs {
   const plvs_frame_view* F;
   const plvs_line_frame_view* LF;
@@ -200,24 +199,18 @@ int check_lines(const plvs_track_lines* L, const plvs_track_camera* cam, bool se
   return PLVS_OK;
 }
 
-// Both loops in one launch and, with S, the two searches behind them: one wait on the common path.
-int run(const plvs_track_camera* cam, const plvs_track_points* P, const plvs_track_lines* L, const SearchArgs* S, int* n_in_view_points,
-        int* n_in_view_lines, int32_t* stats, hipStream_t stream, bool own_stream) {
-  const int m = P ? P->m : 0, ml = L ? L->m : 0;
-  int st_amb_points = 0, st_amb_lines = 0, st_changed = 0, st_launches = 0;
-  auto finish = [&](int nv, int nvl) {
-    if (n_in_view_points) *n_in_view_points = nv;
-    if (n_in_view_lines) *n_in_view_lines = nvl;
-    if (stats) { stats[0] = st_amb_points; stats[1] = st_amb_lines; stats[2] = st_changed; stats[3] = st_launches; }
-  };
-  if (m == 0 && ml == 0) { finish(0, 0); return PLVS_OK; }
-  const plvs_frame_view* F = S ? S->F : nullptr;
-  const plvs_line_frame_view* LF = S ? S->LF : nullptr;
-  const bool search_points = S && m > 0 && F->n > 0;
-  const bool search_lines = S && ml > 0 && LF && LF->n > 0;
-  const int n = search_points ? F->n : 0, nl = search_lines ? LF->n : 0;
-  const bool matrix = search_lines && (long long)ml * nl <= plvs::linewin::kMatrixMaxPairs;
+// ---- one call: what run() and its stages below hand on
+struct Call {
+  const plvs_track_points* P; const plvs_track_lines* L; const SearchArgs* S;   // the entry's arguments
+  int m, ml;
+  TrackParams K;
+  int amb_points = 0, amb_lines = 0, levels_changed = 0, launches = 0;   // the stats
+  int nv = 0, nvl = 0;                                                   // elements in view
+  std::vector<int32_t> changed;                                          // points whose level the host decided otherwise
+  std::vector<int32_t> q_at, q_n, pair_t, dist;                          // the points' candidates, off the staging block
+};
 
+TrackParams kernel_params(const plvs_track_camera* cam, const SearchArgs* S, int m, int ml, bool make_queries) {
   TrackParams K;
   K.fx = cam->K4[0]; K.fy = cam->K4[1]; K.cx = cam->K4[2]; K.cy = cam->K4[3]; K.mbf = cam->mbf;
   K.min_x = cam->bounds4[0]; K.max_x = cam->bounds4[1]; K.min_y = cam->bounds4[2]; K.max_y = cam->bounds4[3];
@@ -227,215 +220,183 @@ int run(const plvs_track_camera* cam, const plvs_track_points* P, const plvs_tra
   K.lsf = cam->log_scale_factor; K.line_lsf = cam->line_log_scale_factor;
   K.levels = cam->n_levels; K.line_levels = cam->n_line_levels;
   K.m = m; K.ml = ml; K.point_blocks = (int)plvs::ceil_div((size_t)m, 256);
-  K.make_queries = search_points ? 1 : 0;
+  K.make_queries = make_queries ? 1 : 0;
   K.th = S ? S->th : 1.0f; K.factor = (S && S->th != 1.0f) ? 1 : 0;
   K.far_points = S ? S->far_points : 0; K.th_far = S ? S->th_far : 0.0f;
   K.flip = g_test_flip;
+  return K;
+}
 
-  // ---- one staged block: [inputs, copied in one piece | window queries, HBM only | results, posted into the pinned side]
-  std::vector<FrameGrid> grid_holder;
-  if (search_points) grid_holder.emplace_back(F);
-  const FrameGrid* grid = search_points ? &grid_holder[0] : nullptr;
-  const size_t nm = search_points ? grid->members.size() : 0, nstart = search_points ? grid->start.size() : 0;
-  const size_t out_cap = (size_t)m * 32 + 4096;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_pts = take(sizeof(float) * kPointIn * (size_t)m), o_pskip = take((size_t)m);
-  const size_t o_lns = take(sizeof(float) * kLineIn * (size_t)ml), o_lskip = take((size_t)ml);
-  const size_t o_sf = take(search_points ? sizeof(float) * (size_t)K.levels : 0);
-  const size_t o_mem = take(sizeof(FrameGrid::Member) * nm), o_start = take(sizeof(int) * nstart);
-  const size_t o_ur = take(sizeof(float) * (size_t)n), o_fd = take((size_t)n * 32), o_qd = take(search_points ? (size_t)m * 32 : 0);
-  const size_t o_cur = take(16);
-  const size_t o_lq = take(matrix ? (size_t)ml * 32 : 0), o_lt = take(matrix ? (size_t)nl * 32 : 0);
-  const size_t in_end = at;
-  const size_t o_wq = take(search_points ? sizeof(WinQuery) * (size_t)m : 0);
-  const size_t o_pout = take(sizeof(float) * kPointOut * (size_t)m), o_lout = take(sizeof(float) * kLineOut * (size_t)ml);
-  const size_t o_first = take(search_points ? sizeof(int32_t) * (size_t)m : 0), o_count = take(search_points ? sizeof(int32_t) * (size_t)m : 0);
-  const size_t o_rec = take(search_points ? sizeof(int2) * out_cap : 0);
-  const size_t o_mat = take(matrix ? sizeof(uint16_t) * (size_t)ml * (size_t)nl : 0);
-  plvs::HostStage& st = plvs::thread_stage();
-  PLVS_HIP_TRY(st.reserve(at + 16));
-  if (own_stream) stream = st.stream;
-
-  float* pin = reinterpret_cast<float*>(st.pinned + o_pts);
-  for (int k = 0; k < m; ++k) {
+// the element inputs: kPointIn / kLineIn floats per element, and the skip flags
+void pack_elements(const Call& c, float* pin, uint8_t* pskip, float* lin, uint8_t* lskip) {
+  const plvs_track_points* P = c.P; const plvs_track_lines* L = c.L;
+  for (int k = 0; k < c.m; ++k) {
     float* d = pin + (size_t)kPointIn * k;
     for (int j = 0; j < 3; ++j) { d[j] = P->pos[3 * (size_t)k + j]; d[3 + j] = P->normal[3 * (size_t)k + j]; }
     d[6] = P->min_dist[k]; d[7] = P->max_dist[k];
   }
-  if (m) memcpy(st.pinned + o_pskip, P->skip, (size_t)m);
-  float* lin = reinterpret_cast<float*>(st.pinned + o_lns);
-  for (int k = 0; k < ml; ++k) {
+  if (c.m) memcpy(pskip, P->skip, (size_t)c.m);
+  for (int k = 0; k < c.ml; ++k) {
     float* d = lin + (size_t)kLineIn * k;
     for (int j = 0; j < 3; ++j) { d[j] = L->start[3 * (size_t)k + j]; d[3 + j] = L->end[3 * (size_t)k + j]; d[6 + j] = L->normal[3 * (size_t)k + j]; }
     d[9] = L->max_dist[k];
   }
-  if (ml) memcpy(st.pinned + o_lskip, L->skip, (size_t)ml);
-  if (search_points) {
-    memcpy(st.pinned + o_sf, F->scale_factors, sizeof(float) * (size_t)K.levels);
-    memcpy(st.pinned + o_mem, grid->members.data(), sizeof(FrameGrid::Member) * nm);
-    memcpy(st.pinned + o_start, grid->start.data(), sizeof(int) * nstart);
-    memcpy(st.pinned + o_ur, F->u_right, sizeof(float) * (size_t)n);
-    memcpy(st.pinned + o_fd, F->desc, (size_t)n * 32);
-    memcpy(st.pinned + o_qd, P->desc, (size_t)m * 32);
-  }
-  memset(st.pinned + o_cur, 0, 16);
-  if (matrix) {
-    memcpy(st.pinned + o_lq, L->desc, (size_t)ml * 32);
-    memcpy(st.pinned + o_lt, LF->descriptors, (size_t)nl * 32);
-  }
-  plvs::StreamGuard guard{stream};
-  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
-  guard.armed = true;
-  const int line_blocks = (int)plvs::ceil_div((size_t)ml, 256);
-  hipLaunchKernelGGL(frustum_kernel, dim3(K.point_blocks + line_blocks), dim3(256), 0, stream, K,
-                     reinterpret_cast<const float*>(st.dev + o_pts), reinterpret_cast<const uint8_t*>(st.dev + o_pskip),
-                     reinterpret_cast<const float*>(st.dev + o_lns), reinterpret_cast<const uint8_t*>(st.dev + o_lskip),
-                     reinterpret_cast<const float*>(st.dev + o_sf), reinterpret_cast<float*>(st.pinned + o_pout),
-                     reinterpret_cast<float*>(st.pinned + o_lout), reinterpret_cast<WinQuery*>(st.dev + o_wq));
-  PLVS_KERNEL_CHECK();
-  if (search_points) {   // the windows of every point, straight behind the kernel that wrote their queries
-    const WinFrame wf{reinterpret_cast<const FrameGrid::Member*>(st.dev + o_mem), reinterpret_cast<const int*>(st.dev + o_start),
-                      reinterpret_cast<const float*>(st.dev + o_ur), reinterpret_cast<const uint4*>(st.dev + o_fd),
-                      F->min_x, F->min_y, F->grid_w_inv, F->grid_h_inv};
-    hipLaunchKernelGGL(plvs::orbwin::orb_window_candidates, dim3(plvs::ceil_div((size_t)m, 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const WinQuery*>(st.dev + o_wq), m, wf, reinterpret_cast<const uint4*>(st.dev + o_qd),
-                       reinterpret_cast<uint32_t*>(st.dev + o_cur), reinterpret_cast<int32_t*>(st.pinned + o_first),
-                       reinterpret_cast<int32_t*>(st.pinned + o_count), reinterpret_cast<int2*>(st.pinned + o_rec), (uint32_t)out_cap);
-    PLVS_KERNEL_CHECK();
-    ++st_launches;
-  }
-  if (matrix) {   // depends on the descriptors alone
-    hipLaunchKernelGGL(plvs::linewin::hamming_matrix_kernel, dim3(plvs::ceil_div((size_t)ml * nl, 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const uint4*>(st.dev + o_lq), ml, reinterpret_cast<const uint4*>(st.dev + o_lt), nl,
-                       reinterpret_cast<uint16_t*>(st.pinned + o_mat));
-    PLVS_KERNEL_CHECK();
-  }
-  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
-  guard.armed = false;
+  if (c.ml) memcpy(lskip, L->skip, (size_t)c.ml);
+}
 
-  // ---- the fields, with the level of every marked element decided by the reference's expression on this process's libm
-  int nv = 0, nvl = 0;
-  std::vector<int> changed;
-  const float* po = reinterpret_cast<const float*>(st.pinned + o_pout);
-  for (int k = 0; k < m; ++k) {
+// after the wait: the fields, with the level of every marked element decided by the reference's expression on this process's libm
+void read_fields(Call& c, const float* po, const float* lo) {
+  const plvs_track_points* P = c.P; const plvs_track_lines* L = c.L;
+  for (int k = 0; k < c.m; ++k) {
     const float* o = po + (size_t)kPointOut * k;
     int level, flags;
     memcpy(&level, o + 5, 4);
     memcpy(&flags, o + 6, 4);
     if (flags & kAmbiguous) {
-      ++st_amb_points;
-      const int host = plvs::predict_level_host(o[7], K.lsf, K.levels, 0);
-      if (host != level) { level = host; changed.push_back(k); }
+      ++c.amb_points;
+      const int host = plvs::predict_level_host(o[7], c.K.lsf, c.K.levels, 0);
+      if (host != level) { level = host; c.changed.push_back(k); }
     }
     P->in_view[k] = (flags & kInView) ? 1 : 0;
-    nv += (flags & kInView) ? 1 : 0;
+    c.nv += (flags & kInView) ? 1 : 0;
     P->proj_x[k] = o[0]; P->proj_y[k] = o[1]; P->proj_xr[k] = o[2]; P->track_depth[k] = o[3]; P->view_cos[k] = o[4];
     P->level[k] = level;
   }
-  const float* lo = reinterpret_cast<const float*>(st.pinned + o_lout);
-  for (int k = 0; k < ml; ++k) {
+  for (int k = 0; k < c.ml; ++k) {
     const float* o = lo + (size_t)kLineOut * k;
     int level, flags;
     memcpy(&level, o + 9, 4);
     memcpy(&flags, o + 10, 4);
     if (flags & kAmbiguous) {
-      ++st_amb_lines;
-      const int host = plvs::predict_level_host(o[11], K.line_lsf, K.line_levels, 0);
-      if (host != level) { level = host; ++st_changed; }
+      ++c.amb_lines;
+      const int host = plvs::predict_level_host(o[11], c.K.line_lsf, c.K.line_levels, 0);
+      if (host != level) { level = host; ++c.levels_changed; }
     }
     L->in_view[k] = (flags & kInView) ? 1 : 0;
-    nvl += (flags & kInView) ? 1 : 0;
+    c.nvl += (flags & kInView) ? 1 : 0;
     for (int j = 0; j < 6; ++j) L->proj[6 * (size_t)k + j] = o[j];
     L->proj_xr[2 * (size_t)k] = o[6]; L->proj_xr[2 * (size_t)k + 1] = o[7];
     L->view_cos[k] = o[8];
     L->level[k] = level;
   }
-  st_changed += (int)changed.size();
-  finish(nv, nvl);
-  if (!S) return PLVS_OK;
+  c.levels_changed += (int)c.changed.size();
+}
 
-  // ---- the candidates of the points leave the staging block before anything else uses it
-  std::vector<int32_t> q_at((size_t)m, 0), q_n((size_t)m, 0), pair_t, dist;
-  size_t found = 0;
-  bool spilled = false;
-  if (search_points && nv > 0) {
-    const int32_t* qf = reinterpret_cast<const int32_t*>(st.pinned + o_first);
-    const int32_t* qc = reinterpret_cast<const int32_t*>(st.pinned + o_count);
-    for (int k = 0; k < m; ++k) found += (size_t)qc[k];
-    spilled = found > out_cap;
-    if (!spilled) {
-      const int2* rec = reinterpret_cast<const int2*>(st.pinned + o_rec);
-      pair_t.resize(found);
-      dist.resize(found);
-      uint32_t w = 0;
-      for (int k = 0; k < m; ++k) {
-        q_at[k] = (int32_t)w;
-        q_n[k] = qc[k];
-        for (int c = 0; c < qc[k]; ++c) { pair_t[w + c] = rec[qf[k] + c].x; dist[w + c] = rec[qf[k] + c].y; }
-        w += (uint32_t)qc[k];
-      }
-    }
-  }
+// LineMatcher::SearchByProjection(F, vpMapLines, bLargerSearch): windows and gates on the host from the fields; the distances have
+// been in the matrix since the wait
+int line_search(const Call& c, plvs::linewin::MatrixStage& M) {
+  const SearchArgs* S = c.S;
+  const plvs::linewin::LineGrid lgrid(S->LF);
+  plvs::linewin::Candidates C;
+  int rc = plvs::linewin::map_line_candidates(S->LF, lgrid, c.ml, c.L->in_view, c.L->proj, c.L->level, S->larger_search, C);
+  if (rc != PLVS_OK) return rc;
+  rc = plvs::linewin::candidate_distances(S->LF, c.L->desc, c.ml, C, M);
+  if (rc != PLVS_OK) return rc;
+  *S->nmatches_lines = plvs::linewin::greedy_map_lines(S->LF, c.ml, C, S->occupied_lines, c.L->has_obs, S->nn_ratio, S->assigned_lines);
+  return PLVS_OK;
+}
 
-  // ---- LineMatcher::SearchByProjection(F, vpMapLines, bLargerSearch): windows and gates on the host from the fields above;
-  // the distances have been in the pinned block since the wait.  (Run before the points' greedy pass: the two write
-  // different outputs, and a repeated window launch of the points would reuse the staging block.)
-  if (search_lines && nvl > 0) {   // the nToMatch > 0 gate of src/Tracking.cc:4569
-    const plvs::linewin::LineGrid lgrid(LF);
-    plvs::linewin::Candidates C;
-    int rc = plvs::linewin::map_line_candidates(LF, lgrid, ml, L->in_view, L->proj, L->level, S->larger_search, C);
+// ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) over the candidates the call's launch left — or,
+// where it spilled (`found` candidates) or the host decided a level otherwise, over those of one more launch
+int point_search(Call& c, const FrameGrid& grid, bool spilled, size_t found, plvs::linewin::MatrixStage& M) {
+  const plvs_track_points* P = c.P; const plvs_frame_view* F = c.S->F; const TrackParams& K = c.K;
+  // the windows of the points `ks` once more, from the fields the host now holds (the frustum kernel is not run again), their lists
+  // appended; the launch lays out the staging block anew: the matrix leaves it first
+  auto rewindow = [&](const std::vector<int32_t>& ks, size_t first_cap) -> int {
+    std::vector<WinQuery> wq;
+    for (int k : ks)
+      if (P->in_view[k] && !(K.far_points && P->track_depth[k] > K.th_far))
+        wq.push_back(plvs::orbwin::map_point_query(P->proj_x[k], P->proj_y[k], P->proj_xr[k], P->view_cos[k], P->level[k], K.th, K.factor,
+                                                   F->scale_factors[P->level[k]], k));
+    if (wq.empty()) return PLVS_OK;
+    M.keep();
+    std::vector<int32_t> qa, qn, pt2, d2;
+    const int rc = plvs::orbwin::window_candidates(F, grid, wq, P->desc, c.m, qa, qn, pt2, d2, first_cap, &c.launches);
     if (rc != PLVS_OK) return rc;
-    if (matrix) {
-      const uint16_t* mat = reinterpret_cast<const uint16_t*>(st.pinned + o_mat);
-      C.dist.assign(C.q.size(), 0);
-      for (size_t c = 0; c < C.q.size(); ++c) C.dist[c] = (int)mat[(size_t)C.q[c] * (size_t)nl + (size_t)C.t[c]];
-    } else {
-      plvs::linewin::MatrixJob none;
-      rc = plvs::linewin::candidate_distances(LF, L->desc, ml, C, none);
-      if (rc != PLVS_OK) return rc;
-    }
-    *S->nmatches_lines = plvs::linewin::greedy_map_lines(LF, ml, C, S->occupied_lines, L->has_obs, S->nn_ratio, S->assigned_lines);
-  }
+    const int32_t base = (int32_t)c.pair_t.size();
+    c.pair_t.insert(c.pair_t.end(), pt2.begin(), pt2.end());
+    c.dist.insert(c.dist.end(), d2.begin(), d2.end());
+    for (size_t j = 0; j < wq.size(); ++j) { c.q_at[wq[j].src] = base + qa[j]; c.q_n[wq[j].src] = qn[j]; }
+    return PLVS_OK;
+  };
+  std::vector<int32_t> src((size_t)c.m);
+  for (int k = 0; k < c.m; ++k) src[k] = k;
+  int rc = PLVS_OK;
+  if (spilled) rc = rewindow(src, found + 64);                  // more candidates than the block had room for: every window
+  else if (!c.changed.empty()) rc = rewindow(c.changed, 0);     // the windows of the points with another level alone
+  if (rc != PLVS_OK) return rc;
+  *c.S->nmatches_points = plvs::orbwin::greedy_points(F, src.data(), (size_t)c.m, c.q_at, c.q_n, c.pair_t, c.dist, c.S->nn_ratio,
+                                                     c.S->occupied_points, P->has_obs, c.S->assigned_points);
+  return PLVS_OK;
+}
 
-  // ---- ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints)
-  if (search_points && nv > 0) {   // the nToMatch > 0 gate of :4475
-    auto host_query = [&](int k) {
-      return plvs::orbwin::map_point_query(P->proj_x[k], P->proj_y[k], P->proj_xr[k], P->view_cos[k], P->level[k], K.th, K.factor,
-                                           F->scale_factors[P->level[k]], k);
-    };
-    auto searched = [&](int k) { return P->in_view[k] && !(K.far_points && P->track_depth[k] > K.th_far); };
-    if (spilled) {
-      // more candidates than the block had room for: the windows once more with the room they need, from the fields the
-      // host now holds (the frustum kernel is not run again)
-      std::vector<WinQuery> wq;
-      for (int k = 0; k < m; ++k)
-        if (searched(k)) wq.push_back(host_query(k));
-      std::vector<int32_t> qa, qn;
-      const int rc = plvs::orbwin::window_candidates(F, *grid, wq, P->desc, m, qa, qn, pair_t, dist, found + 64, &st_launches);
-      if (rc != PLVS_OK) return rc;
-      for (size_t j = 0; j < wq.size(); ++j) { q_at[wq[j].src] = qa[j]; q_n[wq[j].src] = qn[j]; }
-    } else if (!changed.empty()) {
-      // a level the host decided otherwise: the windows of those points alone, their lists appended
-      std::vector<WinQuery> wq;
-      for (int k : changed)
-        if (searched(k)) wq.push_back(host_query(k));
-      if (!wq.empty()) {
-        std::vector<int32_t> qa, qn, pt2, d2;
-        const int rc = plvs::orbwin::window_candidates(F, *grid, wq, P->desc, m, qa, qn, pt2, d2, 0, &st_launches);
-        if (rc != PLVS_OK) return rc;
-        const int32_t base = (int32_t)pair_t.size();
-        pair_t.insert(pair_t.end(), pt2.begin(), pt2.end());
-        dist.insert(dist.end(), d2.begin(), d2.end());
-        for (size_t j = 0; j < wq.size(); ++j) { q_at[wq[j].src] = base + qa[j]; q_n[wq[j].src] = qn[j]; }
-      }
-    }
-    std::vector<int32_t> src((size_t)m);
-    for (int k = 0; k < m; ++k) src[k] = k;
-    *S->nmatches_points = plvs::orbwin::greedy_points(F, src.data(), (size_t)m, q_at, q_n, pair_t, dist, S->nn_ratio, S->occupied_points,
-                                                     P->has_obs, S->assigned_points);
-  }
-  if (stats) stats[3] = st_launches;
+// Both loops in one launch and, with S, the two searches behind them: one wait on the common path.
+int run(const plvs_track_camera* cam, const plvs_track_points* P, const plvs_track_lines* L, const SearchArgs* S, int* n_in_view_points,
+        int* n_in_view_lines, int32_t* stats, hipStream_t stream, bool own_stream) {
+  Call c{P, L, S, P ? P->m : 0, L ? L->m : 0};
+  const int m = c.m, ml = c.ml;
+  auto finish = [&]() {
+    if (n_in_view_points) *n_in_view_points = c.nv;
+    if (n_in_view_lines) *n_in_view_lines = c.nvl;
+    if (stats) { stats[0] = c.amb_points; stats[1] = c.amb_lines; stats[2] = c.levels_changed; stats[3] = c.launches; }
+  };
+  if (m == 0 && ml == 0) { finish(); return PLVS_OK; }
+  const plvs_frame_view* F = S ? S->F : nullptr;
+  const plvs_line_frame_view* LF = S ? S->LF : nullptr;
+  const bool search_points = S && m > 0 && F->n > 0;
+  const bool search_lines = S && ml > 0 && LF && LF->n > 0;
+  c.K = kernel_params(cam, S, m, ml, search_points);
+
+  // ---- one staged block: [inputs, copied in one piece | window queries, HBM only | results, posted into the pinned side]
+  std::optional<FrameGrid> grid;
+  plvs::orbwin::WindowStage W;
+  if (search_points) W = plvs::orbwin::WindowStage{F, &grid.emplace(F), m, m, P->desc};
+  plvs::linewin::MatrixStage M;
+  if (search_lines) M = plvs::linewin::MatrixStage{L->desc, LF->descriptors, ml, LF->n};
+  plvs::Take take;
+  const size_t o_pts = take(sizeof(float) * kPointIn * (size_t)m), o_pskip = take((size_t)m);
+  const size_t o_lns = take(sizeof(float) * kLineIn * (size_t)ml), o_lskip = take((size_t)ml);
+  const size_t o_sf = take(search_points ? sizeof(float) * (size_t)c.K.levels : 0);
+  W.take_inputs(take); M.take_inputs(take);
+  const size_t in_end = take.at;
+  W.take_scratch(take);
+  const size_t o_pout = take(sizeof(float) * kPointOut * (size_t)m), o_lout = take(sizeof(float) * kLineOut * (size_t)ml);
+  W.take_outputs(take); M.take_outputs(take);
+  plvs::HostStage& st = plvs::thread_stage();
+  PLVS_HIP_TRY(st.reserve(take.at + 16));
+  if (own_stream) stream = st.stream;
+
+  pack_elements(c, reinterpret_cast<float*>(st.pinned + o_pts), reinterpret_cast<uint8_t*>(st.pinned + o_pskip),
+                reinterpret_cast<float*>(st.pinned + o_lns), reinterpret_cast<uint8_t*>(st.pinned + o_lskip));
+  if (search_points) memcpy(st.pinned + o_sf, F->scale_factors, sizeof(float) * (size_t)c.K.levels);
+  W.fill(st.pinned); M.fill(st.pinned);
+  plvs::StreamGuard guard{stream};
+  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, stream));
+  guard.armed = true;
+  const int line_blocks = (int)plvs::ceil_div((size_t)ml, 256);
+  hipLaunchKernelGGL(frustum_kernel, dim3(c.K.point_blocks + line_blocks), dim3(256), 0, stream, c.K,
+                     reinterpret_cast<const float*>(st.dev + o_pts), reinterpret_cast<const uint8_t*>(st.dev + o_pskip),
+                     reinterpret_cast<const float*>(st.dev + o_lns), reinterpret_cast<const uint8_t*>(st.dev + o_lskip),
+                     reinterpret_cast<const float*>(st.dev + o_sf), reinterpret_cast<float*>(st.pinned + o_pout),
+                     reinterpret_cast<float*>(st.pinned + o_lout), W.queries(st.dev));
+  PLVS_KERNEL_CHECK();
+  int rc = W.launch(st.dev, st.pinned, stream);   // the windows of every point, straight behind the kernel that wrote their queries
+  if (rc != PLVS_OK) return rc;
+  c.launches += search_points ? 1 : 0;
+  if ((rc = M.launch(st.dev, st.pinned, stream)) != PLVS_OK) return rc;
+  PLVS_HIP_TRY(hipStreamSynchronize(stream));   // the call's one wait
+  guard.armed = false;
+
+  read_fields(c, reinterpret_cast<const float*>(st.pinned + o_pout), reinterpret_cast<const float*>(st.pinned + o_lout));
+  finish();
+  if (!S) return PLVS_OK;
+  // ---- the candidates of the points leave the staging block with the fields; the matrix stays until a launch wants the block (keep())
+  c.q_at.assign((size_t)m, 0); c.q_n.assign((size_t)m, 0);
+  size_t found = 0;
+  const bool spilled = search_points && c.nv > 0 && !W.unpack(st.pinned, &found, c.q_at, c.q_n, c.pair_t, c.dist);
+  if (search_lines && c.nvl > 0 && (rc = line_search(c, M)) != PLVS_OK) return rc;                            // nToMatch > 0, src/Tracking.cc:4569
+  if (search_points && c.nv > 0 && (rc = point_search(c, *grid, spilled, found, M)) != PLVS_OK) return rc;    // :4475
+  if (stats) stats[3] = c.launches;
   return PLVS_OK;
 }
 

@@ -34,13 +34,8 @@ struct Part {
 inline int32_t copy_in_stat(const Part& p) { return p.device ? (int32_t)p.in_bytes : 0; }
 
 // ---- what the two kinds' parts share: textually the same on both sides, and blind to the element type
-inline size_t up16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-// the allocator of a part's share of the block: every array at a multiple of 16
-struct Take {
-  size_t at = 0;
-  size_t operator()(size_t bytes) { const size_t o = at; at += up16(bytes); return o; }
-};
+using plvs::Take;   // the allocator of a part's share of the block (common.hpp)
+using plvs::up16;
 
 // the record a pair posts (pack() of either kernel file): best_idx, and best_dist (16 bits, 0xffff = -1) | reached << 16 | ambiguous << 24
 struct Record {

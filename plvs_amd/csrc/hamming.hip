@@ -106,7 +106,7 @@ int plvs_hip_hamming_knn2(const uint8_t* query, int nq, const uint8_t* train, in
   }
   PLVS_REQUIRE(query && train && idx && dist, "null descriptor or output pointer");
   // one staged block: [query | train | mask] in, [idx | dist] out (16-byte aligned pieces)
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  using plvs::up16;
   const size_t o_q = 0, o_t = o_q + up16((size_t)nq * 32), o_m = o_t + up16((size_t)nt * 32),
                o_i = o_m + up16(qmask ? (size_t)nq : 0), o_d = o_i + up16((size_t)nq * 2 * sizeof(int32_t)),
                total = o_d + up16((size_t)nq * 2 * sizeof(int32_t));

@@ -1,7 +1,8 @@
 // The candidate windows of the guided line searches — the (theta, d) grid of Frame::GetLineFeaturesInArea, the point-to-line
-// gates, the all-pairs descriptor launch — and the two passes of SearchByProjection(F, MapLines): what
-// plvs_hip_lines_search_by_projection does once its inputs exist, shared with the one-call local-map search
-// (frame_track.hip).  Everything sits in an unnamed namespace: each translation unit that includes this gets its own copy.
+// gates, the all-pairs descriptor launch and its one staging (MatrixStage) — and the two passes of SearchByProjection(F, MapLines)
+// and of SearchByProjection(CurrentFrame, LastFrame): what the two entries of line_proj_search.hip do once their inputs exist,
+// shared with the one-call searches (frame_track.hip, frame_motion.hip), which launch the matrix behind their projection kernels.
+// Everything sits in an unnamed namespace: each translation unit that includes this gets its own copy.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -34,30 +35,61 @@ __global__ __launch_bounds__(256) void hamming_matrix_kernel(const uint4* __rest
                       __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w));
 }
 constexpr int kMatrixMaxPairs = 1 << 18;   // (512 x 512 lines; beyond that the candidate pairs go through plvs_hip_hamming_pairs)
-struct MatrixJob {
-  const uint16_t* dist = nullptr;   // nq x nt, valid after matrix_wait
-  int nt = 0;
-  bool started = false;
-};
-int matrix_begin(MatrixJob& J, const uint8_t* query, int nq, const uint8_t* train, int nt) {
-  J.started = false;
-  if (nq <= 0 || nt <= 0 || (long long)nq * nt > kMatrixMaxPairs) return PLVS_OK;
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t o_q = 0, o_t = o_q + up16((size_t)nq * 32), o_d = o_t + up16((size_t)nt * 32), total = o_d + up16(sizeof(uint16_t) * (size_t)nq * nt);
-  plvs::HostStage& st = plvs::thread_stage();
-  PLVS_HIP_TRY(st.reserve(total));
-  memcpy(st.pinned + o_q, query, (size_t)nq * 32);
-  memcpy(st.pinned + o_t, train, (size_t)nt * 32);
+// One hamming_matrix_kernel launch as a share of a staging block, in the manner of orbwin::WindowStage: its places through the
+// caller's allocator — the two descriptor sets among the inputs the caller copies in one piece, the u16 matrix in the pinned side —,
+// fill, launch, and after the caller's wait the matrix at `dist`.
+struct MatrixStage {
+  const uint8_t *query = nullptr, *train = nullptr;
+  int nq = 0, nt = 0;
+  size_t o_q = 0, o_t = 0, o_d = 0;
+  const uint16_t* dist = nullptr;   // nq x nt, valid after the wait: in the pinned block until keep()
+  bool started = false;             // launched by matrix_begin on the thread's own stream, which candidate_distances waits for
+  std::vector<uint16_t> kept;
+
+  // false: too many pairs (or none) — nothing is taken or launched, the candidates' pairs go through the pair list
+  bool on() const { return nq > 0 && nt > 0 && (long long)nq * nt <= kMatrixMaxPairs; }
   // (the descriptors are copied: every one is read by hundreds of threads, and a read of pinned host memory is not cached)
-  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, o_d, hipMemcpyHostToDevice, st.stream));
-  hipLaunchKernelGGL(hamming_matrix_kernel, dim3(plvs::ceil_div((size_t)nq * nt, 256)), dim3(256), 0, st.stream,
-                     reinterpret_cast<const uint4*>(st.dev + o_q), nq, reinterpret_cast<const uint4*>(st.dev + o_t), nt,
-                     reinterpret_cast<uint16_t*>(st.pinned + o_d));
-  PLVS_KERNEL_CHECK();
-  J.dist = reinterpret_cast<const uint16_t*>(st.pinned + o_d);
-  J.nt = nt;
-  J.started = true;
-  return PLVS_OK;
+  void take_inputs(plvs::Take& take) {
+    if (on()) { o_q = take((size_t)nq * 32); o_t = take((size_t)nt * 32); }
+  }
+  void take_outputs(plvs::Take& take) { if (on()) o_d = take(sizeof(uint16_t) * (size_t)nq * nt); }
+  void fill(char* pinned) const {
+    if (!on()) return;
+    memcpy(pinned + o_q, query, (size_t)nq * 32);
+    memcpy(pinned + o_t, train, (size_t)nt * 32);
+  }
+  int launch(char* dev, char* pinned, hipStream_t stream) {   // depends on the descriptors alone
+    if (!on()) return PLVS_OK;
+    hipLaunchKernelGGL(hamming_matrix_kernel, dim3(plvs::ceil_div((size_t)nq * nt, 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const uint4*>(dev + o_q), nq, reinterpret_cast<const uint4*>(dev + o_t), nt,
+                       reinterpret_cast<uint16_t*>(pinned + o_d));
+    PLVS_KERNEL_CHECK();
+    dist = reinterpret_cast<const uint16_t*>(pinned + o_d);
+    return PLVS_OK;
+  }
+  // After the wait, before anything else lays out the staging block (a repeated window launch): the matrix leaves it.
+  void keep() {
+    if (!on() || !kept.empty()) return;
+    kept.assign(dist, dist + (size_t)nq * (size_t)nt);
+    dist = kept.data();
+  }
+};
+
+using MatrixJob = MatrixStage;   // the stage as the first thing of a call of its own, on the thread's own stream and staging block
+int matrix_begin(MatrixJob& J, const uint8_t* query, int nq, const uint8_t* train, int nt) {
+  J = MatrixStage{query, train, nq, nt};
+  if (!J.on()) return PLVS_OK;
+  plvs::Take take;
+  J.take_inputs(take);
+  const size_t in_end = take.at;
+  J.take_outputs(take);
+  plvs::HostStage& st = plvs::thread_stage();
+  PLVS_HIP_TRY(st.reserve(take.at));
+  J.fill(st.pinned);
+  PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, st.stream));
+  const int rc = J.launch(st.dev, st.pinned, st.stream);
+  J.started = rc == PLVS_OK;
+  return rc;
 }
 int matrix_wait(MatrixJob& J) {
   if (J.started) PLVS_HIP_TRY(hipStreamSynchronize(plvs::thread_stage().stream));
@@ -193,12 +225,14 @@ struct Candidates {   // per projected line: its gated candidates, and one dista
   std::vector<int32_t> q, t, dist;
 };
 
-int candidate_distances(const plvs_line_frame_view* F, const uint8_t* qdesc, int nq, Candidates& C, MatrixJob& J) {
+// The distance of every candidate: out of the matrix where one was launched (a call of its own waits for it here; the one-call
+// searches have waited on their stream), else by the pair-list launch.
+int candidate_distances(const plvs_line_frame_view* F, const uint8_t* qdesc, int nq, Candidates& C, MatrixStage& M) {
   C.dist.assign(C.q.size(), 0);
-  if (J.started) {   // (the matrix has been on its way since the call began)
-    const int rc = matrix_wait(J);
+  if (M.on()) {   // (the matrix has been on its way since the call began)
+    const int rc = matrix_wait(M);
     if (rc != PLVS_OK) return rc;
-    for (size_t c = 0; c < C.q.size(); ++c) C.dist[c] = (int)J.dist[(size_t)C.q[c] * (size_t)J.nt + (size_t)C.t[c]];
+    for (size_t c = 0; c < C.q.size(); ++c) C.dist[c] = (int)M.dist[(size_t)C.q[c] * (size_t)M.nt + (size_t)C.t[c]];
     return PLVS_OK;
   }
   if (C.q.empty()) return PLVS_OK;
@@ -209,7 +243,6 @@ bool view_ok(const plvs_line_frame_view* F) {
   return F != nullptr && F->n >= 0 && (F->n == 0 || (F->keylines_un && F->descriptors)) && F->line_scale_factors &&
          F->line_inv_level_sigma2 && F->max_diag > 0.0f;
 }
-
 
 // Pass 1 of SearchByProjection(F, MapLines) (src/LineMatcher.cc:1310-1430): window and gates of every map line in view.
 int map_line_candidates(const plvs_line_frame_view* F, const LineGrid& grid, int n_map, const uint8_t* in_view, const float* proj,

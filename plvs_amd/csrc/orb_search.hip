@@ -25,7 +25,7 @@ struct PairsJob {
   int nq = 0, nt = 0, max_pairs = 0;
 };
 int pairs_begin(PairsJob& J, const uint8_t* query, int nq, const uint8_t* train, int nt, int max_pairs) {
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  using plvs::up16;
   const size_t o_q = 0, o_t = o_q + up16((size_t)nq * 32);
   J.o_pq = o_t + up16((size_t)nt * 32);
   J.o_pt = J.o_pq + up16(sizeof(int32_t) * (size_t)max_pairs);
@@ -74,7 +74,7 @@ int plvs_hip_hamming_pairs(const uint8_t* query, int nq, const uint8_t* train, i
   for (int p = 0; p < npairs; ++p)
     PLVS_REQUIRE(pair_q[p] >= 0 && pair_q[p] < nq && pair_t[p] >= 0 && pair_t[p] < nt, "pair index out of range");
   // one staged block: [query | train | pair_q | pair_t] in, [dist] out
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  using plvs::up16;
   const size_t o_q = 0, o_t = o_q + up16((size_t)nq * 32), o_pq = o_t + up16((size_t)nt * 32),
                o_pt = o_pq + up16(sizeof(int32_t) * (size_t)npairs), o_d = o_pt + up16(sizeof(int32_t) * (size_t)npairs),
                total = o_d + up16(sizeof(int32_t) * (size_t)npairs);

@@ -1,7 +1,9 @@
 // The candidate windows of the point searches — Frame::AssignFeaturesToGrid / GetFeaturesInArea as a CSR grid, the window
-// kernel that walks it, its staged launch (window_candidates) — and the greedy pass of SearchByProjection(F, MapPoints):
-// what plvs_hip_orb_search_by_projection does once its inputs exist, shared with the one-call local-map search
-// (frame_track.hip).  Everything sits in an unnamed namespace: each translation unit that includes this gets its own copy.
+// kernel that walks it, that kernel's one staging (WindowStage) and its launch as a call of its own (window_candidates) — and the
+// greedy passes of SearchByProjection(F, MapPoints) and SearchByProjection(CurrentFrame, LastFrame): what the two entries of
+// orb_search.hip do once their inputs exist, shared with the one-call searches (frame_track.hip, frame_motion.hip), whose projection
+// kernels write the queries the stage's launch reads.  Everything sits in an unnamed namespace: each translation unit that includes
+// this gets its own copy.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -165,8 +167,84 @@ __global__ __launch_bounds__(256) void orb_window_candidates(const WinQuery* __r
   }
 }
 
-// The windows of `wq` on frame F (orb_window_candidates): per query k the accepted candidates pair_t / dist
-// [q_at[k], q_at[k] + q_n[k]) in the reference's enumeration order.  qdesc: the queries' descriptor rows (n_qdesc x 32).
+// One orb_window_candidates launch over frame F with nq queries, as a share of a staging block (a fusejob::Part in small): it
+// takes its places through the caller's allocator — inputs the caller copies in one piece, scratch that lives in HBM only, outputs
+// the kernel posts into the pinned side —, fills its inputs, launches, and after the caller's wait unpacks.  The queries are either
+// host-built (host_wq: they travel inside the input share) or written at queries(dev) by an earlier kernel on the same stream.
+struct WindowStage {
+  const plvs_frame_view* F = nullptr;
+  const FrameGrid* grid = nullptr;
+  int nq = 0, n_qdesc = 0;             // nq == 0: a stage that takes nothing and is not launched
+  const uint8_t* qdesc = nullptr;      // the queries' descriptor rows (n_qdesc x 32)
+  const WinQuery* host_wq = nullptr;
+  size_t out_cap = 0;                  // before take_outputs: a caller that knows the count already; after: the records there is room for
+  size_t o_wq = 0, o_mem = 0, o_start = 0, o_ur = 0, o_fd = 0, o_qd = 0, o_cur = 0, o_first = 0, o_count = 0, o_rec = 0;
+
+  void take_inputs(plvs::Take& take) {
+    if (nq == 0) return;
+    if (host_wq) o_wq = take(sizeof(WinQuery) * (size_t)nq);
+    o_mem = take(sizeof(FrameGrid::Member) * grid->members.size()); o_start = take(sizeof(int) * grid->start.size());
+    o_ur = take(sizeof(float) * (size_t)F->n); o_fd = take((size_t)F->n * 32); o_qd = take((size_t)n_qdesc * 32);
+    o_cur = take(16);   // (stays in HBM: it is the target of the waves' atomics)
+  }
+  void take_scratch(plvs::Take& take) { if (nq && !host_wq) o_wq = take(sizeof(WinQuery) * (size_t)nq); }
+  // (first / count / records go straight into the pinned block — posted writes over the link, a few tens of KB —: one copy in, one
+  // launch, one wait; the copies back and the second wait they needed cost more than the search's arithmetic)
+  void take_outputs(plvs::Take& take) {
+    if (nq == 0) return;
+    out_cap = std::max((size_t)nq * 32 + 4096, out_cap);
+    o_first = take(sizeof(int32_t) * (size_t)nq); o_count = take(sizeof(int32_t) * (size_t)nq);
+    o_rec = take(sizeof(int2) * out_cap);
+  }
+  void fill(char* pinned) const {
+    if (nq == 0) return;
+    if (host_wq) memcpy(pinned + o_wq, host_wq, sizeof(WinQuery) * (size_t)nq);
+    memcpy(pinned + o_mem, grid->members.data(), sizeof(FrameGrid::Member) * grid->members.size());
+    memcpy(pinned + o_start, grid->start.data(), sizeof(int) * grid->start.size());
+    memcpy(pinned + o_ur, F->u_right, sizeof(float) * (size_t)F->n);
+    memcpy(pinned + o_fd, F->desc, (size_t)F->n * 32);
+    memcpy(pinned + o_qd, qdesc, (size_t)n_qdesc * 32);
+    memset(pinned + o_cur, 0, 16);
+  }
+  WinQuery* queries(char* dev) const { return reinterpret_cast<WinQuery*>(dev + o_wq); }
+  int launch(char* dev, char* pinned, hipStream_t stream) const {
+    if (nq == 0) return PLVS_OK;
+    const WinFrame wf{reinterpret_cast<const FrameGrid::Member*>(dev + o_mem), reinterpret_cast<const int*>(dev + o_start),
+                      reinterpret_cast<const float*>(dev + o_ur), reinterpret_cast<const uint4*>(dev + o_fd),
+                      F->min_x, F->min_y, F->grid_w_inv, F->grid_h_inv};
+    hipLaunchKernelGGL(orb_window_candidates, dim3(plvs::ceil_div((size_t)nq, 4)), dim3(256), 0, stream, queries(dev), nq, wf,
+                       reinterpret_cast<const uint4*>(dev + o_qd), reinterpret_cast<uint32_t*>(dev + o_cur),
+                       reinterpret_cast<int32_t*>(pinned + o_first), reinterpret_cast<int32_t*>(pinned + o_count),
+                       reinterpret_cast<int2*>(pinned + o_rec), (uint32_t)out_cap);
+    PLVS_KERNEL_CHECK();
+    return PLVS_OK;
+  }
+  // After the wait: *found candidates in all; false when they are more than the block had room for (a spill: nothing is written),
+  // else per query k its candidates pair_t / dist [q_at[k], q_at[k] + q_n[k]) in the reference's enumeration order.
+  bool unpack(const char* pinned, size_t* found, std::vector<int32_t>& q_at, std::vector<int32_t>& q_n, std::vector<int32_t>& pair_t,
+              std::vector<int32_t>& dist) const {
+    const int32_t* qf = reinterpret_cast<const int32_t*>(pinned + o_first);
+    const int32_t* qc = reinterpret_cast<const int32_t*>(pinned + o_count);
+    *found = 0;
+    for (int k = 0; k < nq; ++k) *found += (size_t)qc[k];
+    if (*found > out_cap) return false;
+    const int2* rec = reinterpret_cast<const int2*>(pinned + o_rec);
+    pair_t.resize(*found);
+    dist.resize(*found);
+    // (the ranges were reserved in the order the waves arrived: copied here query after query)
+    uint32_t at = 0;
+    for (int k = 0; k < nq; ++k) {
+      q_at[k] = (int32_t)at;
+      q_n[k] = qc[k];
+      for (int c = 0; c < qc[k]; ++c) { pair_t[at + c] = rec[qf[k] + c].x; dist[at + c] = rec[qf[k] + c].y; }
+      at += (uint32_t)qc[k];
+    }
+    return true;
+  }
+};
+
+// The windows of `wq` on frame F as a call of its own, on the thread's own stream and staging block: per query k the accepted
+// candidates pair_t / dist [q_at[k], q_at[k] + q_n[k]).  One repetition with the room that is needed when the first launch spills.
 int window_candidates(const plvs_frame_view* F, const FrameGrid& grid, const std::vector<WinQuery>& wq, const uint8_t* qdesc,
                       int n_qdesc, std::vector<int32_t>& q_at, std::vector<int32_t>& q_n, std::vector<int32_t>& pair_t,
                       std::vector<int32_t>& dist, size_t first_cap = 0, int* launches = nullptr) {
@@ -176,62 +254,24 @@ int window_candidates(const plvs_frame_view* F, const FrameGrid& grid, const std
   pair_t.clear();
   dist.clear();
   if (nq == 0) return PLVS_OK;
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t nm = grid.members.size();
   plvs::HostStage& st = plvs::thread_stage();
-  size_t out_cap = std::max((size_t)nq * 32 + 4096, first_cap);   // (first_cap: a caller that knows the count already)
   for (int attempt = 0;; ++attempt) {
     if (launches) ++*launches;
-    const size_t o_wq = 0, o_mem = o_wq + up16(sizeof(WinQuery) * (size_t)nq), o_start = o_mem + up16(sizeof(FrameGrid::Member) * nm),
-                 o_ur = o_start + up16(sizeof(int) * grid.start.size()), o_fd = o_ur + up16(sizeof(float) * (size_t)F->n),
-                 o_qd = o_fd + up16((size_t)F->n * 32), o_cur = o_qd + up16((size_t)n_qdesc * 32), o_first = o_cur + 16,
-                 o_count = o_first + up16(sizeof(int32_t) * (size_t)nq), o_out = o_count + up16(sizeof(int32_t) * (size_t)nq),
-                 total = o_out + up16(sizeof(int2) * out_cap);
-    PLVS_HIP_TRY(st.reserve(total));
-    memcpy(st.pinned + o_wq, wq.data(), sizeof(WinQuery) * (size_t)nq);
-    memcpy(st.pinned + o_mem, grid.members.data(), sizeof(FrameGrid::Member) * nm);
-    memcpy(st.pinned + o_start, grid.start.data(), sizeof(int) * grid.start.size());
-    memcpy(st.pinned + o_ur, F->u_right, sizeof(float) * (size_t)F->n);
-    memcpy(st.pinned + o_fd, F->desc, (size_t)F->n * 32);
-    memcpy(st.pinned + o_qd, qdesc, (size_t)n_qdesc * 32);
-    memset(st.pinned + o_cur, 0, 16);
-    PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, o_first, hipMemcpyHostToDevice, st.stream));
-    const WinFrame wf{reinterpret_cast<const FrameGrid::Member*>(st.dev + o_mem), reinterpret_cast<const int*>(st.dev + o_start),
-                      reinterpret_cast<const float*>(st.dev + o_ur), reinterpret_cast<const uint4*>(st.dev + o_fd),
-                      F->min_x, F->min_y, F->grid_w_inv, F->grid_h_inv};
-    hipLaunchKernelGGL(orb_window_candidates, dim3(plvs::ceil_div((size_t)nq, 4)), dim3(256), 0, st.stream,
-                       reinterpret_cast<const WinQuery*>(st.dev + o_wq), nq, wf, reinterpret_cast<const uint4*>(st.dev + o_qd),
-                       reinterpret_cast<uint32_t*>(st.dev + o_cur), reinterpret_cast<int32_t*>(st.pinned + o_first),
-                       reinterpret_cast<int32_t*>(st.pinned + o_count), reinterpret_cast<int2*>(st.pinned + o_out), (uint32_t)out_cap);
-    // (first / count / records go straight into the pinned block — posted writes over the link, a few tens of KB —:
-    // one copy in, one launch, one wait; the copies back and the second wait they needed cost more than the search's
-    // arithmetic.  The cursor stays in HBM: it is the target of the waves' atomics.)
-    PLVS_KERNEL_CHECK();
+    WindowStage W{F, &grid, nq, n_qdesc, qdesc, wq.data(), first_cap};
+    plvs::Take take;
+    W.take_inputs(take);
+    const size_t in_end = take.at;
+    W.take_outputs(take);
+    PLVS_HIP_TRY(st.reserve(take.at));
+    W.fill(st.pinned);
+    PLVS_HIP_TRY(hipMemcpyAsync(st.dev, st.pinned, in_end, hipMemcpyHostToDevice, st.stream));
+    const int rc = W.launch(st.dev, st.pinned, st.stream);
+    if (rc != PLVS_OK) return rc;
     PLVS_HIP_TRY(hipStreamSynchronize(st.stream));
-    const int32_t* qf = reinterpret_cast<const int32_t*>(st.pinned + o_first);
-    const int32_t* qc = reinterpret_cast<const int32_t*>(st.pinned + o_count);
     size_t found = 0;
-    for (int k = 0; k < nq; ++k) found += (size_t)qc[k];
-    if (found > out_cap) {   // more candidates than room: once more with what is needed
-      PLVS_REQUIRE(attempt == 0, "candidate count changed between two identical launches");
-      out_cap = found + 64;
-      continue;
-    }
-    const int2* rec = reinterpret_cast<const int2*>(st.pinned + o_out);
-    pair_t.resize(found);
-    dist.resize(found);
-    // (the ranges were reserved in the order the waves arrived: copied here query after query)
-    uint32_t at = 0;
-    for (int k = 0; k < nq; ++k) {
-      q_at[k] = (int32_t)at;
-      q_n[k] = qc[k];
-      for (int c = 0; c < qc[k]; ++c) {
-        pair_t[at + c] = rec[qf[k] + c].x;
-        dist[at + c] = rec[qf[k] + c].y;
-      }
-      at += (uint32_t)qc[k];
-    }
-    return PLVS_OK;
+    if (W.unpack(st.pinned, &found, q_at, q_n, pair_t, dist)) return PLVS_OK;
+    PLVS_REQUIRE(attempt == 0, "candidate count changed between two identical launches");
+    first_cap = found + 64;   // more candidates than room: once more with what is needed
   }
 }
 
@@ -248,7 +288,6 @@ void three_maxima(const int* count, int L, int& ind1, int& ind2, int& ind3) {
   if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
   else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
 }
-
 
 // The greedy assignment of SearchByProjection(F, MapPoints) in map-point order (src/ORBmatcher.cc:106-163) over the candidate
 // lists of window_candidates: query k belongs to map point src[k] (ascending).  -> the reference's return value.

@@ -303,6 +303,25 @@ def test_sizes_against_the_restatement(scenario, m, ml):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("ml", [512, 513])
+def test_line_distances_on_both_sides_of_the_matrix_switch(ml):
+    """512 map lines over 512 key lines are 2^18 descriptor pairs, the last size at which the candidates' distances are read out of
+    the all-pairs matrix launched behind the frustum kernel; 513 over 512 take the pair-list launch after the wait.  Either way the
+    line search is the stand-alone entry's over the fields the one call reports."""
+    n_kl = 512
+    assert (ml * n_kl > 2 ** 18) == (ml == 513)
+    inp = S.random_inputs(m=8, ml=ml, seed=7, n_kp=64, n_kl=n_kl)
+    want = R.is_in_frustum(inp["cam"], inp["points"], inp["lines"])
+    got = _one_call(inp)
+    _check_fields(got, want)
+    fields = {"l_" + k: got["lines"][k] for k in LINE_KEYS}
+    n, a = _existing_lines(inp, fields, False, True)
+    print("line matches:", got["nmatches_lines"], "of", int(want["l_in_view"].sum()), "map lines in view")
+    assert n == got["nmatches_lines"] and same(a, got["assigned_lines"])
+    assert got["nmatches_lines"] > 0
+
+
+@pytest.mark.gpu
 def test_lines_absent_and_closed_gates(scenario):
     inp, g = scenario
     facts = _facts()["facts"]

@@ -404,6 +404,23 @@ def test_sizes_against_the_restatement(oracle, n, nl):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("nl", [512, 513])
+def test_line_distances_on_both_sides_of_the_matrix_switch(nl):
+    """512 last-frame lines over 512 key lines are 2^18 descriptor pairs, the last size at which the candidates' distances are read out
+    of the all-pairs matrix launched behind the projection kernel; 513 over 512 take the pair-list launch after the wait.  Either way
+    the line search is the stand-alone entry's over the fields the one call reports."""
+    n_kl = 512
+    assert (nl * n_kl > 2 ** 18) == (nl == 513)
+    inp = S.random_inputs(8, nl, seed=11, n_kp=64, n_kl=n_kl)
+    got = _one_call(inp)
+    _check_fields(got, R.project_points(inp["poses"], inp["points"]), R.project_lines(inp["poses"], inp["lines"]))
+    n, a = _existing_lines(inp, dict(proj_valid=got["proj_valid_lines"], proj6=got["proj6"]), 0, S.direction_code(got["forward"], got["backward"]), 1, 1)
+    print("line matches:", got["nmatches_lines"], "of", int(got["proj_valid_lines"].sum()), "projected lines")
+    assert n == got["nmatches_lines"] and same(a, got["assigned_lines"])
+    assert got["nmatches_lines"] > 0
+
+
+@pytest.mark.gpu
 def test_lines_absent(scenario):
     inp, g = scenario
     facts = _facts()["facts"]
