@@ -1862,6 +1862,60 @@ int plvs_hip_line_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plv
                                       const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
                                       uint8_t* reached, int32_t* stats);
 
+/* ------------------------------------------------- LoopClosing::SearchAndFuse: the Sim3 Fuse searches over resident key frames
+ * The search stage of ORBmatcher::Fuse(pKF, Sophus::Sim3f& Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1437-1553) and of
+ * LineMatcher::Fuse(pKF, const Sophus::Sim3f& Scw, vpLines, th, vpReplaceLine) (src/LineMatcher.cc:2321-2561) up to the choice of
+ * bestIdx, for every key frame of the corrected group that the two overloads of LoopClosing::SearchAndFuse
+ * (src/LoopClosing.cc:3155-3233, :3236-3310) call them with (th = 4): K key frames x M loop map points or lines in one call.
+ * These are not the SE3 searches with another pose:
+ *   points  no chi-square gate (:1520: the level band [level - 1, level] alone); bestDist from INT_MAX, <= TH_LOW (50) (:1513, :1535);
+ *   lines   the two point-to-line gates multiply by mvLineInvLevelSigma2[nPredictedLevel] (:2463-2464), not [klLevel]; no right-image
+ *           check (#if 0, :2471); (bestDist <= TH_LOW) && (bestIdx >= 0) with TH_LOW 60 (:2530).
+ * The library never decomposes a Sim3: the decomposition is Eigen's (normalise, toRotationMatrix, matrix -> quaternion), and only
+ * the caller's own Eigen is bit-exact with the caller.  The caller writes, with its own Sophus: */
+typedef struct plvs_keyframe_sim3_pose {
+  float q_cw[4];       /* Tcw.unit_quaternion().coeffs(), Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) (:1446)  */
+  float Rcw[9];        /* Scw.rotationMatrix(), column-major: the line side projects by the matrix (:2324)                           */
+  float tcw[3];        /* Scw.translation() / Scw.scale() (:1446, :2326)                                                             */
+  float Ow_points[3];  /* Tcw.inverse().translation() (src/ORBmatcher.cc:1447)                                                       */
+  float Ow_lines[3];   /* -Rcw.transpose() * tcw (src/LineMatcher.cc:2327): NOT the same rounding as Ow_points                       */
+} plvs_keyframe_sim3_pose;
+/* Key frame k = (kfs[k], sim3_poses[k]); the second SearchAndFuse overload (Scw from GetPose(), scale 1) fills the same struct.
+ * skip[k * m + i]: pMP->isBad() || spAlreadyFound.count(pMP) at the time of the call (:1463, :2347) — the snapshot
+ * GetMapPointsUnordered() / GetMapLinesUnordered(), not the live IsInKeyFrame.  reached: the PLVS_FUSE_* / PLVS_LINE_FUSE_* codes
+ * (NO_CANDIDATE: nobody passed the gate of THIS overload).  The mutation is deferred in the reference (vpReplacePoint[i] during the
+ * loop, Replace after it under the map mutex) and stays the caller's; INTEGRATION.md 2l has the replay.  Outputs, the 4-entry stats
+ * ([3] = bytes this kind put into the call's copy in), th, stream, the launch-free shapes (n_kfs == 0, m == 0, no key frame with
+ * features, every pair skipped), the theta refusal, the handle checks and every other refusal: those of the _kf entries above.
+ * Every result equals the reference's bit for bit. */
+int plvs_hip_orb_loop_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                     const plvs_fuse_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                     uint8_t* reached, int32_t* stats, void* stream);
+int plvs_hip_line_loop_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                      const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                      uint8_t* reached, int32_t* stats, void* stream);
+/* Both in one call, shaped like plvs_hip_fuse_search_points_and_lines_kf: one key-frame list, one copy in, both kernels on one
+ * stream, one wait.  stats (3 entries, may be NULL): launches, device waits, bytes of the copy in. */
+int plvs_hip_loop_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                  const plvs_fuse_points* points, const uint8_t* skip_points, float th_points,
+                                                  int32_t* point_best_idx, int32_t* point_best_dist, uint8_t* point_reached,
+                                                  int32_t* point_stats, const plvs_fuse_lines* lines, const uint8_t* skip_lines,
+                                                  float th_lines, int32_t* line_best_idx, int32_t* line_best_dist,
+                                                  uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream);
+/* The same on the host copy, serially, with no HIP call (PLVS_KEYFRAME_HOST_ONLY handles and others alike): the replay's re-query,
+ * machines without a device.  stats[0] = stats[2] = stats[3] = 0. */
+int plvs_hip_orb_loop_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                          const plvs_fuse_points* P, const uint8_t* skip, float th, int32_t* best_idx,
+                                          int32_t* best_dist, uint8_t* reached, int32_t* stats);
+int plvs_hip_line_loop_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                           const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx,
+                                           int32_t* best_dist, uint8_t* reached, int32_t* stats);
+/* Testing and measurement only, outside the stable ABI: the layout of the point kernel for the calling thread's later
+ * plvs_hip_orb_loop_fuse_search_kf / plvs_hip_loop_fuse_search_points_and_lines_kf calls.  0 (the default): the sieve — a thread
+ * per pair through the projection and its tests, then a wave per surviving pair through the window; 1: a wave per pair from the
+ * start, the layout of plvs_hip_orb_fuse_search_kf.  Both give the same outputs. */
+void plvs_hip_loop_fuse_test_layout(int mode);
+
 #ifdef __cplusplus
 }
 #endif

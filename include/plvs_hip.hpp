@@ -456,7 +456,8 @@ class KeyFrameHandle {
 };
 
 namespace detail {
-inline std::vector<const plvs_keyframe*> raw_handles(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_pose>& poses) {
+template <typename Pose>
+inline std::vector<const plvs_keyframe*> raw_handles(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<Pose>& poses) {
   if (keyFrames.size() != poses.size()) throw std::invalid_argument("FuseSearch: one pose per key frame handle");
   std::vector<const plvs_keyframe*> raw(keyFrames.size() + 1, nullptr);
   for (size_t k = 0; k < keyFrames.size(); ++k) raw[k] = keyFrames[k] ? keyFrames[k]->get() : nullptr;
@@ -526,6 +527,78 @@ inline int FuseSearchPointsAndLines(const std::vector<const KeyFrameHandle*>& ke
                                                  points.bestIdx.data(), points.bestDist.data(), points.reached.data(), ps, &vpMapLines,
                                                  skipLines, thLines, lines.bestIdx.data(), lines.bestDist.data(), lines.reached.data(), ls,
                                                  stats, stream));
+  for (int s = 0; s < 3; ++s) { points.stats[s] = ps[s]; lines.stats[s] = ls[s]; }
+  points.bestIdx.resize(pp);
+  points.bestDist.resize(pp);
+  points.reached.resize(pp);
+  int n = lines.finish(lp);
+  for (size_t p = 0; p < pp; ++p) n += points.bestIdx[p] >= 0 ? 1 : 0;
+  return n;
+}
+
+// The Sim3 Fuse searches of LoopClosing::SearchAndFuse (ORBmatcher::Fuse / LineMatcher::Fuse with Scw, src/ORBmatcher.cc:1437-1553,
+// src/LineMatcher.cc:2321-2561) over resident key frames: key frame k = (keyFrames[k], poses[k]), the caller's own decomposition of
+// Scw (plvs_hip.h: plvs_keyframe_sim3_pose).  skip: isBad() || spAlreadyFound.count() at the time of the call.  Results, onHost,
+// stream and copyInBytes as FuseSearch over handles.
+inline int LoopFuseSearch(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_sim3_pose>& poses,
+                          const plvs_fuse_points& vpPoints, const uint8_t* skip, float th, ORBmatcher::FuseResult& result, bool onHost = false,
+                          void* stream = nullptr, int32_t* copyInBytes = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpPoints.m;
+  result.bestIdx.assign(pairs + 1, -1);
+  result.bestDist.assign(pairs + 1, -1);
+  result.reached.assign(pairs + 1, 0);
+  int32_t st[4] = {0, 0, 0, 0};
+  if (onHost)
+    check(plvs_hip_orb_loop_fuse_search_kf_host(raw.data(), poses.data(), K, &vpPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                                result.reached.data(), st));
+  else
+    check(plvs_hip_orb_loop_fuse_search_kf(raw.data(), poses.data(), K, &vpPoints, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                           result.reached.data(), st, stream));
+  for (int s = 0; s < 3; ++s) result.stats[s] = st[s];
+  if (copyInBytes) *copyInBytes = st[3];
+  result.bestIdx.resize(pairs);
+  result.bestDist.resize(pairs);
+  result.reached.resize(pairs);
+  int n = 0;
+  for (size_t p = 0; p < pairs; ++p) n += result.bestIdx[p] >= 0 ? 1 : 0;
+  return n;
+}
+inline int LoopFuseSearch(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_sim3_pose>& poses,
+                          const plvs_fuse_lines& vpLines, const uint8_t* skip, float th, LineMatcher::FuseResult& result, bool onHost = false,
+                          void* stream = nullptr, int32_t* copyInBytes = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpLines.m;
+  result.prepare(pairs);
+  int32_t st[4] = {0, 0, 0, 0};
+  if (onHost)
+    check(plvs_hip_line_loop_fuse_search_kf_host(raw.data(), poses.data(), K, &vpLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                                 result.reached.data(), st));
+  else
+    check(plvs_hip_line_loop_fuse_search_kf(raw.data(), poses.data(), K, &vpLines, skip, th, result.bestIdx.data(), result.bestDist.data(),
+                                            result.reached.data(), st, stream));
+  for (int s = 0; s < 3; ++s) result.stats[s] = st[s];
+  if (copyInBytes) *copyInBytes = st[3];
+  return result.finish(pairs);
+}
+// both in one call; stats (3 entries, may be null): launches, waits, bytes of the copy in
+inline int LoopFuseSearchPointsAndLines(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_sim3_pose>& poses,
+                                        const plvs_fuse_points& vpPoints, const uint8_t* skipPoints, float thPoints,
+                                        ORBmatcher::FuseResult& points, const plvs_fuse_lines& vpLines, const uint8_t* skipLines, float thLines,
+                                        LineMatcher::FuseResult& lines, int32_t stats[3] = nullptr, void* stream = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const size_t pp = keyFrames.size() * (size_t)vpPoints.m, lp = keyFrames.size() * (size_t)vpLines.m;
+  points.bestIdx.assign(pp + 1, -1);
+  points.bestDist.assign(pp + 1, -1);
+  points.reached.assign(pp + 1, 0);
+  lines.prepare(lp);
+  int32_t ps[4] = {0, 0, 0, 0}, ls[4] = {0, 0, 0, 0};
+  check(plvs_hip_loop_fuse_search_points_and_lines_kf(raw.data(), poses.data(), (int)keyFrames.size(), &vpPoints, skipPoints, thPoints,
+                                                      points.bestIdx.data(), points.bestDist.data(), points.reached.data(), ps, &vpLines,
+                                                      skipLines, thLines, lines.bestIdx.data(), lines.bestDist.data(), lines.reached.data(), ls,
+                                                      stats, stream));
   for (int s = 0; s < 3; ++s) { points.stats[s] = ps[s]; lines.stats[s] = ls[s]; }
   points.bestIdx.resize(pp);
   points.bestDist.resize(pp);

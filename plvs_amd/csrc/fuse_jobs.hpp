@@ -72,16 +72,17 @@ int make_line_part(const plvs_line_fuse_keyframe* kfs, int n_kfs, const plvs_fus
                    int32_t* best_dist, uint8_t* reached, int32_t* stats, std::unique_ptr<Part>* out);
 
 // The same over resident key frames (keyframe_handle.hpp): key frame k = (kfs[k], poses[k]).  host_entry: the _kf_host entries
-// (PLVS_KEYFRAME_HOST_ONLY handles are taken, no HIP call is made, not even for the device id).
+// (PLVS_KEYFRAME_HOST_ONLY handles are taken, no HIP call is made, not even for the device id).  sim3: not null — the Sim3 overloads
+// of loop closing (the kGateSim3 policy of the pair headers) with these poses, `poses` is not read.
 int make_point_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
                        const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, bool host_entry,
-                       std::unique_ptr<Part>* out);
+                       std::unique_ptr<Part>* out, const plvs_keyframe_sim3_pose* sim3 = nullptr);
 int make_line_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
                       const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, bool host_entry,
-                      std::unique_ptr<Part>* out);
+                      std::unique_ptr<Part>* out, const plvs_keyframe_sim3_pose* sim3 = nullptr);
 // the refusals of a handle list, in this order: a NULL handle or a handle without the side the call needs (side: 1 = points,
 // 2 = lines), for a device entry a host-only handle — all before any HIP call — and then a handle of another device
-int check_handles(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, int side, bool host_entry);
+int check_handles(const plvs_keyframe* const* kfs, const void* poses, int n_kfs, int side, bool host_entry);
 // A single-kind entry after its make_*: the n_stats (3, a resident part's 4) stats zeroed, nothing more for an empty part (null),
 // else run_parts over the one part — on the host (the _host entries: every pair by the host's code, no HIP call) or on `stream`
 // (null: the calling thread's own)

@@ -20,6 +20,11 @@
 //   :1365-1392  per candidate: the level band, then the chi-square gate — stereo if mvuRight[idx] >= 0 (not > 0) — with the
 //               product in f32 and the comparison in f64 against the double literal
 //   :1400  dist < bestDist from 256 in the window's enumeration order: the first minimum wins
+//
+// The Sim3 overload of loop closing and map merging, ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1437-1553), is the
+// gate policy kGateSim3 of the same text: :1467-1499 is :1294-1337 without ur (the pose is the caller's decomposition of Scw,
+// plvs_hip.h: plvs_keyframe_sim3_pose), and a candidate passes the level band alone (:1520) — no chi-square gate.  bestDist starts at
+// INT_MAX there (:1513) and is compared <= TH_LOW (:1535): 256 serves, no Hamming distance lies above it.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -46,6 +51,7 @@ enum Reached : int {
 };
 constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / ROWS: KeyFrame copies mnGridCols / mnGridRows from them
 constexpr int kThLow = 50;                      // ORBmatcher::TH_LOW
+enum Gate : int { kGateSE3 = 0, kGateSim3 = 1 };   // which overload's candidate gate (see the head)
 
 // what the pair loop reads of pKF besides its grid
 struct KfConst {
@@ -120,9 +126,11 @@ PLVS_FUSE_FN bool in_area(float kx, float ky, float x, float y, float r) {
   return fabsf(distx) < r && fabsf(disty) < r;
 }
 
-// :1365-1392 — true: the candidate's Hamming distance is taken
+// :1365-1392 (kGateSim3: :1520 alone) — true: the candidate's Hamming distance is taken
+template <Gate kGate = kGateSE3>
 PLVS_FUSE_FN bool candidate_gate(float u, float v, float ur, int level, float kx, float ky, int octave, float kr, const float* inv_level_sigma2) {
   if (octave < level - 1 || octave > level) return false;
+  if (kGate == kGateSim3) return true;
   const float ex = u - kx, ey = v - ky;
   if (kr >= 0) {
     const float er = ur - kr;
@@ -161,7 +169,7 @@ struct KfGrid {
 struct Result { int best_idx, best_dist, reached; };
 
 // :1340-1408 for a pair whose tests passed, serially, with the level given (the host's)
-template <typename Member>
+template <Gate kGate = kGateSE3, typename Member>
 inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Front& f, int level, float th, const uint8_t* point_desc) {
   Result res{-1, -1, kEmptyWindow};
   const float radius = th * G.scale_factors[level];
@@ -177,7 +185,7 @@ inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Fro
     for (; m < end; ++m) {
       if (!in_area(m->x, m->y, f.u, f.v, radius)) continue;
       any = true;
-      if (!candidate_gate(f.u, f.v, f.ur, level, m->x, m->y, m->octave, G.u_right[m->idx], G.inv_level_sigma2)) continue;
+      if (!candidate_gate<kGate>(f.u, f.v, f.ur, level, m->x, m->y, m->octave, G.u_right[m->idx], G.inv_level_sigma2)) continue;
       gated = true;
       uint32_t td[8];
       std::memcpy(td, G.desc + 32 * (size_t)m->idx, 32);
@@ -192,12 +200,12 @@ inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Fro
 }
 
 // the whole pair on the host: the level is the reference's own expression on the host's libm
-template <typename Member>
+template <Gate kGate = kGateSE3, typename Member>
 inline Result pair_host(const KfConst& K, const KfGrid<Member>& G, const float* pos, const float* normal, float min_dist, float max_dist,
                         const uint8_t* point_desc, float th, int double_overload) {
   const Front f = front(K, pos, normal, min_dist, max_dist);
   if (f.reached != kEmptyWindow) return Result{-1, -1, f.reached};
-  return search_window(K, G, f, predict_level_host(f.ratio, K.log_scale_factor, K.n_levels, double_overload), th, point_desc);
+  return search_window<kGate>(K, G, f, predict_level_host(f.ratio, K.log_scale_factor, K.n_levels, double_overload), th, point_desc);
 }
 
 }  // namespace fusepair

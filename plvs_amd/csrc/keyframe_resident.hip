@@ -3,13 +3,14 @@
 // calling thread's staging block, one copy, one wait — and from then on a search carries the poses, the map points or lines and
 // `skip`: the per-call grid build, staging and copy of every target key frame (76 % of the point call) are gone.  The
 // kernels are orb_fuse.hip's and line_fuse.hip's resident ones, the call is fuse_both.hip's run_parts: one reserve, one copy in, one
-// launch per kind, one wait.
+// launch per kind, one wait.  The Sim3 Fuse searches of LoopClosing::SearchAndFuse (the _loop_ entries) are the same parts with
+// the other gate and a plvs_keyframe_sim3_pose per key frame.
 #include "fuse_jobs.hpp"
 #include "keyframe_handle.hpp"
 
 namespace fj = plvs::fusejob;
 
-int plvs::fusejob::check_handles(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, int side, bool host_entry) {
+int plvs::fusejob::check_handles(const plvs_keyframe* const* kfs, const void* poses, int n_kfs, int side, bool host_entry) {
   PLVS_REQUIRE(n_kfs == 0 || poses, "null poses");
   for (int k = 0; k < n_kfs; ++k) {
     PLVS_REQUIRE(kfs[k], "null key-frame handle in the list");
@@ -114,21 +115,23 @@ int plvs_hip_line_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plv
   return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, nullptr, true);
 }
 
-int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
-                                             const plvs_fuse_points* P, const uint8_t* skip_points, float th_points, int32_t* point_best_idx,
-                                             int32_t* point_best_dist, uint8_t* point_reached, int32_t* point_stats, const plvs_fuse_lines* L,
-                                             const uint8_t* skip_lines, float th_lines, int32_t* line_best_idx, int32_t* line_best_dist,
-                                             uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream) {
+}  // extern "C"
+
+// the combined entry over handles, SE3 (poses) or Sim3 (sim3): one of the two is null
+static int both_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, const plvs_keyframe_sim3_pose* sim3, int n_kfs,
+                   const plvs_fuse_points* P, const uint8_t* skip_points, float th_points, int32_t* point_best_idx, int32_t* point_best_dist,
+                   uint8_t* point_reached, int32_t* point_stats, const plvs_fuse_lines* L, const uint8_t* skip_lines, float th_lines,
+                   int32_t* line_best_idx, int32_t* line_best_dist, uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream) {
   PLVS_REQUIRE(P || L, "neither points nor lines");
   std::unique_ptr<fj::Part> points, lines;
   if (P) {   // both kinds' refusals before anything is launched or written
     const int rc = fj::make_point_part_kf(kfs, poses, n_kfs, P, skip_points, th_points, point_best_idx, point_best_dist, point_reached,
-                                          point_stats, false, &points);
+                                          point_stats, false, &points, sim3);
     if (rc != PLVS_OK) return rc;
   }
   if (L) {
     const int rc = fj::make_line_part_kf(kfs, poses, n_kfs, L, skip_lines, th_lines, line_best_idx, line_best_dist, line_reached, line_stats,
-                                         false, &lines);
+                                         false, &lines, sim3);
     if (rc != PLVS_OK) return rc;
   }
   if (P && point_stats) point_stats[0] = point_stats[1] = point_stats[2] = point_stats[3] = 0;
@@ -139,6 +142,66 @@ int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, co
   const int rc = fj::run_parts(points.get(), lines.get(), static_cast<hipStream_t>(stream), stream == nullptr, false, &launches, &waits, &copied);
   if (stats) { stats[0] = launches; stats[1] = waits; stats[2] = (int32_t)copied; }
   return rc;
+}
+
+extern "C" {
+
+int plvs_hip_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs,
+                                             const plvs_fuse_points* P, const uint8_t* skip_points, float th_points, int32_t* point_best_idx,
+                                             int32_t* point_best_dist, uint8_t* point_reached, int32_t* point_stats, const plvs_fuse_lines* L,
+                                             const uint8_t* skip_lines, float th_lines, int32_t* line_best_idx, int32_t* line_best_dist,
+                                             uint8_t* line_reached, int32_t* line_stats, int32_t* stats, void* stream) {
+  return both_kf(kfs, poses, nullptr, n_kfs, P, skip_points, th_points, point_best_idx, point_best_dist, point_reached, point_stats, L, skip_lines,
+                 th_lines, line_best_idx, line_best_dist, line_reached, line_stats, stats, stream);
+}
+
+// ---- LoopClosing::SearchAndFuse: the Sim3 overloads.  A NULL pose list is refused here: both_kf and the parts tell the two searches
+// apart by it (without key frames no part is made, and there is nothing to tell).
+int plvs_hip_orb_loop_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                     const plvs_fuse_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                     uint8_t* reached, int32_t* stats, void* stream) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part_kf(kfs, nullptr, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, false, &part, sim3_poses);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, stream, false);
+}
+
+int plvs_hip_line_loop_fuse_search_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                      const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                      uint8_t* reached, int32_t* stats, void* stream) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_line_part_kf(kfs, nullptr, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, false, &part, sim3_poses);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, stream, false);
+}
+
+int plvs_hip_orb_loop_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                          const plvs_fuse_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                          uint8_t* reached, int32_t* stats) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_point_part_kf(kfs, nullptr, n_kfs, P, skip, th, best_idx, best_dist, reached, stats, true, &part, sim3_poses);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, nullptr, true);
+}
+
+int plvs_hip_line_loop_fuse_search_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                           const plvs_fuse_lines* L, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist,
+                                           uint8_t* reached, int32_t* stats) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_line_part_kf(kfs, nullptr, n_kfs, L, skip, th, best_idx, best_dist, reached, stats, true, &part, sim3_poses);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 4, nullptr, true);
+}
+
+int plvs_hip_loop_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                  const plvs_fuse_points* P, const uint8_t* skip_points, float th_points,
+                                                  int32_t* point_best_idx, int32_t* point_best_dist, uint8_t* point_reached,
+                                                  int32_t* point_stats, const plvs_fuse_lines* L, const uint8_t* skip_lines, float th_lines,
+                                                  int32_t* line_best_idx, int32_t* line_best_dist, uint8_t* line_reached, int32_t* line_stats,
+                                                  int32_t* stats, void* stream) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  return both_kf(kfs, nullptr, sim3_poses, n_kfs, P, skip_points, th_points, point_best_idx, point_best_dist, point_reached, point_stats, L,
+                 skip_lines, th_lines, line_best_idx, line_best_dist, line_reached, line_stats, stats, stream);
 }
 
 }  // extern "C"

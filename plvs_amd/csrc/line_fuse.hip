@@ -12,6 +12,9 @@
 // rule marks ambiguous are evaluated once more by the host entry's code after the wait, and their result is simply the host's.
 //
 // Map mutation (AddObservation, AddMapLine, Replace) stays the caller's: INTEGRATION.md has the replay.
+//
+// The Sim3 overload of LoopClosing::SearchAndFuse (src/LineMatcher.cc:2321-2561, line_fuse_pair.hpp's kGateSim3) runs over resident
+// key frames only, by the resident kernel with the other gate: there are few lines, and the front is the larger part of the work.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -70,6 +73,7 @@ static_assert(sizeof(KfRes) == 168, "the per-call table entry: stats[3] of the r
 // One wave, one pair past front(): theta's plan and its ambiguity, the walk of the one or two sub-windows in 64-member strides, the
 // gates, the (distance, enumeration position) key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and
 // the resident kernel both call it.
+template <lf::Gate kGate>
 __device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, const FuseLines& L, int i, const Front& f, float th, int lane,
                                           int2* __restrict__ rec) {
   if (f.reached != lf::kEmptyWindow) {
@@ -92,7 +96,7 @@ __device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, c
   const uint4* desc = A.desc;
   const float* sig = A.sig;
   const uint4 qa = L.desc[2 * (size_t)i], qb = L.desc[2 * (size_t)i + 1];
-  const lf::Rep rr = lf::right_rep(K, f);
+  const lf::Rep rr = kGate == lf::kGateSE3 ? lf::right_rep(K, f) : lf::Rep{0.0f, 0.0f, 0.0f};
   const float dmin = f.rep.d - dd, dmax = f.rep.d + dd;
   uint32_t best = 0xffffffffu;
   int best_idx = -1;
@@ -105,7 +109,7 @@ __device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, c
       const int a = start[ix * lf::kRows + c.r0], e = start[ix * lf::kRows + c.r1 + 1];
       for (int j = a + lane; j < e; j += 64) {
         const Member mb = members[j];
-        if (!lf::candidate_gate(f.rep, rr, f.level, mb, sig)) continue;
+        if (!lf::candidate_gate<kGate>(f.rep, rr, f.level, mb, sig)) continue;
         gated = true;
         const uint4 ta = desc[2 * (size_t)mb.idx], tb = desc[2 * (size_t)mb.idx + 1];
         const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
@@ -152,12 +156,13 @@ __global__ __launch_bounds__(256) void line_fuse_window_kernel(const char* __res
   const KfArrays A{reinterpret_cast<const Member*>(base + D.o_mem), reinterpret_cast<const int*>(base + D.o_start),
                    reinterpret_cast<const uint4*>(base + D.o_desc), reinterpret_cast<const float*>(base + D.o_sf),
                    reinterpret_cast<const float*>(base + D.o_sig), D.n_members};
-  walk_pair(D.k, A, L, i, f, th, lane, out + pair);
+  walk_pair<lf::kGateSE3>(D.k, A, L, i, f, th, lane, out + pair);
 }
 
 // The resident layout: the table holds pointers into the handles' own allocations (keyframe_handle.hpp), nothing of a key frame is in
 // the call's block.  The pair index is the wave's: taken through readfirstlane, so the compiler knows it uniform and the pair's table
 // entry — pose, constants, pointers — is read by scalar loads and stays in scalar registers.
+template <lf::Gate kGate>
 __global__ __launch_bounds__(256) void line_fuse_window_resident_kernel(const KfRes* __restrict__ kfs, FuseLines L, float th, int2* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int pair = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(256) void line_fuse_window_resident_kernel(const Kf
   }
   const KfRes& D = kfs[k];
   const Front f = lf::front(D.k, L.start + 3 * (size_t)i, L.end + 3 * (size_t)i, L.normal + 3 * (size_t)i, L.max_dist[i]);
-  walk_pair(D.k, D.a, L, i, f, th, lane, out + pair);
+  walk_pair<kGate>(D.k, D.a, L, i, f, th, lane, out + pair);
 }
 
 // pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there)
@@ -215,6 +220,7 @@ struct LinePart : fj::Part {
   uint8_t* const reached;
   int32_t* const stats;
   const int n_stats;   // 4: the source writes stats[3], the bytes it put into the call's copy in
+  lf::Gate gate = lf::kGateSE3;   // kGateSim3: the loop-closing overload (a resident source's)
 
   std::vector<lf::Result> results;   // held back: a full-theta pair refuses the call before anything is written
   size_t o_tab = 0, o_start = 0, o_end = 0, o_nrm = 0, o_maxd = 0, o_desc = 0, o_skip = 0;   // from the part's inputs
@@ -236,7 +242,7 @@ struct LinePart : fj::Part {
 
   lf::Result pair_host(const lf::KfGrid& G, const KfConst& c, int i) const {
     return lf::pair_host(c, G, L->start + 3 * (size_t)i, L->end + 3 * (size_t)i, L->normal + 3 * (size_t)i, L->max_dist[i], L->desc + 32 * (size_t)i,
-                         th, 0, 0);
+                         th, 0, 0, gate);
   }
 
   size_t n_pairs() const { return (size_t)n_kfs * L->m; }
@@ -411,12 +417,16 @@ KfArrays arrays_at(const char* block, const plvs_keyframe::Lines& s) {
 // nothing else.  Nothing of a key frame is built, staged or copied.
 struct ResidentLines : LinePart {
   const plvs_keyframe* const* const kfs;
-  const plvs_keyframe_pose* const poses;
+  const plvs_keyframe_pose* const poses;          // the SE3 search's
+  const plvs_keyframe_sim3_pose* const sim3;      // the Sim3 search's (one of the two is null)
   std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
 
-  ResidentLines(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_lines* L_, const uint8_t* skip_,
-                float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_, int32_t* stats_)
-      : LinePart(n_kfs_, L_, skip_, th_, best_idx_, best_dist_, reached_, stats_, 4), kfs(kfs_), poses(poses_) {}
+  ResidentLines(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, const plvs_keyframe_sim3_pose* sim3_, int n_kfs_,
+                const plvs_fuse_lines* L_, const uint8_t* skip_, float th_, int32_t* best_idx_, int32_t* best_dist_, uint8_t* reached_,
+                int32_t* stats_)
+      : LinePart(n_kfs_, L_, skip_, th_, best_idx_, best_dist_, reached_, stats_, 4), kfs(kfs_), poses(poses_), sim3(sim3_) {
+    if (sim3) gate = lf::kGateSim3;
+  }
 
   bool has_lines(int k) const override { return kfs[k]->ln.n > 0; }
   size_t table_entry() const override { return sizeof(KfRes); }
@@ -425,8 +435,11 @@ struct ResidentLines : LinePart {
     consts.resize((size_t)n_kfs);
     for (int k = 0; k < n_kfs; ++k) {
       KfConst& c = consts[k] = kfs[k]->ln.c;
-      for (int i = 0; i < 9; ++i) c.R[i] = poses[k].Rcw[i];
-      for (int i = 0; i < 3; ++i) { c.t[i] = poses[k].tcw[i]; c.Ow[i] = poses[k].Ow[i]; }
+      for (int i = 0; i < 9; ++i) c.R[i] = sim3 ? sim3[k].Rcw[i] : poses[k].Rcw[i];
+      for (int i = 0; i < 3; ++i) {
+        c.t[i] = sim3 ? sim3[k].tcw[i] : poses[k].tcw[i];
+        c.Ow[i] = sim3 ? sim3[k].Ow_lines[i] : poses[k].Ow[i];
+      }
     }
   }
 
@@ -436,8 +449,10 @@ struct ResidentLines : LinePart {
   }
 
   void launch_kfs(char*, const char* table, const FuseLines& FL, int2* rec, hipStream_t stream) override {
-    hipLaunchKernelGGL(line_fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const KfRes*>(table), FL, th, rec);
+    const KfRes* tab = reinterpret_cast<const KfRes*>(table);
+    const dim3 grid(plvs::ceil_div(n_pairs(), 4));
+    if (sim3) hipLaunchKernelGGL(line_fuse_window_resident_kernel<lf::kGateSim3>, grid, dim3(256), 0, stream, tab, FL, th, rec);
+    else hipLaunchKernelGGL(line_fuse_window_resident_kernel<lf::kGateSE3>, grid, dim3(256), 0, stream, tab, FL, th, rec);
   }
 
   lf::Result host_pair(int k, int i) override {   // on the handle's host copy
@@ -485,12 +500,12 @@ void plvs::kfhandle::stage_lines(const plvs_line_fuse_keyframe& kf, plvs_keyfram
 
 int plvs::fusejob::make_line_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
                                      const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
-                                     bool host_entry, std::unique_ptr<Part>* out) {
+                                     bool host_entry, std::unique_ptr<Part>* out, const plvs_keyframe_sim3_pose* sim3) {
   out->reset();
   int rc = check_call(kfs, n_kfs, L, th, best_idx, best_dist);
-  if (rc == PLVS_OK) rc = check_handles(kfs, poses, n_kfs, 2, host_entry);
+  if (rc == PLVS_OK) rc = check_handles(kfs, sim3 ? static_cast<const void*>(sim3) : poses, n_kfs, 2, host_entry);
   if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && L->m > 0) out->reset(new ResidentLines(kfs, poses, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
+  if (n_kfs > 0 && L->m > 0) out->reset(new ResidentLines(kfs, poses, sim3, n_kfs, L, skip, th, best_idx, best_dist, reached, stats));
   return PLVS_OK;
 }
 

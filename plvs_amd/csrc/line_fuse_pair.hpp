@@ -34,6 +34,12 @@
 //            line's right-image representation from uS - mbf * invSz (a product with the projection's own inverse depth)
 //     :2259  dist < bestDist from 256: the first minimum in enumeration order
 //
+// The Sim3 overload of loop closing and map merging, LineMatcher::Fuse(pKF, Scw, vpLines, th, vpReplaceLine) (:2321-2561), is the
+// gate policy kGateSim3 of the same text: the same ProjectLineWithCheck overload (:2397) on the caller's decomposition of Scw
+// (plvs_hip.h: plvs_keyframe_sim3_pose; Ow = -Rcw.transpose() * tcw, :2327), and per candidate the two point-to-line distances times
+// mvLineInvLevelSigma2[nPredictedLevel] (:2463-2464), NOT [klLevel]; the right-image check is compiled out (#if 0, :2471).
+// bestDist starts at INT_MAX (:2426) and (bestDist <= TH_LOW) && (bestIdx >= 0) decides (:2530): 256 serves.
+//
 // THETA NEEDS THE HOST'S atan2.  GetLine2dRepresentation calls atan2(ny, nx) on two floats with <math.h> in scope: the
 // compiled reference calls atan2f (tests/golden/line_fuse_reference_facts.json records the undefined symbol).  No device
 // arctangent equals it bit for bit, and theta decides the > pi refusal, the two split tests and the row indices of every
@@ -78,6 +84,7 @@ enum Reached : int {
 constexpr int kRows = 36, kCols = 160;             // LINE_THETA_GRID_ROWS, LINE_D_GRID_COLS (include/Frame.h:72-73)
 constexpr int kThLow = 60;                         // LineMatcher::TH_LOW (src/LineMatcher.cc:88)
 constexpr int kThetaUlps = 4;
+enum Gate : int { kGateSE3 = 0, kGateSim3 = 1 };   // which overload's candidate gate (see the head)
 constexpr float kChi2 = 3.84f;                     // kChiSquareLinePointProj, a const float (:98)
 constexpr float kEps = 1.1920929e-07f;             // std::numeric_limits<float>::epsilon()
 constexpr double kPi = 3.14159265358979323846, kPi2 = 1.57079632679489661923;   // M_PI, M_PI_2
@@ -287,15 +294,16 @@ PLVS_LFUSE_FN Rep right_rep(const KfConst& K, const Front& f) {
   (void)representation(f.uS - K.mbf * f.invSz, f.vS, f.uE - K.mbf * f.invEz, f.vE, &r);
   return r;
 }
-// :2148-2250 — true: the candidate's descriptor distance is taken
+// :2148-2250 (kGateSim3: :2437-2467, rr is not read) — true: the candidate's descriptor distance is taken
+template <Gate kGate = kGateSE3>
 PLVS_LFUSE_FN bool candidate_gate(const Rep& pr, const Rep& rr, int level, const Member& m, const float* inv_level_sigma2) {
   if (m.octave < level - 1 || m.octave > level) return false;
-  const float sig = inv_level_sigma2[m.octave];
+  const float sig = inv_level_sigma2[kGate == kGateSim3 ? level : m.octave];
   const float ds = pr.nx * m.sx + pr.ny * m.sy - pr.d;
   const float de = pr.nx * m.ex + pr.ny * m.ey - pr.d;
   const float ds2 = ds * ds, de2 = de * de;
   if (ds2 * sig > kChi2 || de2 * sig > kChi2) return false;
-  if (m.urs >= 0 && m.ure >= 0) {
+  if (kGate == kGateSE3 && m.urs >= 0 && m.ure >= 0) {
     const float dsr = rr.nx * m.urs + rr.ny * m.sy - rr.d;
     const float der = rr.nx * m.ure + rr.ny * m.ey - rr.d;
     const float dsr2 = dsr * dsr, der2 = der * der;
@@ -375,6 +383,7 @@ struct Walk {
   const uint32_t* qd;
   int best, best_idx;
   bool any, gated;
+  Gate gate;
 };
 inline void walk_leaf(Walk& w, const Leaf& leaf) {
   const Cells c = leaf_cells(*w.K, leaf);
@@ -384,7 +393,9 @@ inline void walk_leaf(Walk& w, const Leaf& leaf) {
     for (int j = s; j < e; ++j) {
       const Member& m = w.G->members[j];
       w.any = true;
-      if (!candidate_gate(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)) continue;
+      if (!(w.gate == kGateSim3 ? candidate_gate<kGateSim3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)
+                                : candidate_gate<kGateSE3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)))
+        continue;
       w.gated = true;
       uint32_t td[8];
       std::memcpy(td, w.G->desc + 32 * (size_t)m.idx, 32);
@@ -410,7 +421,8 @@ inline void walk_recursive(Walk& w, float tmin, float tmax, float dmin, float dm
 }
 
 // :2124-2263 for a pair whose tests passed, serially, with the level and theta given (the host's)
-inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, int level, float theta, float th, const uint8_t* line_desc) {
+inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, int level, float theta, float th, const uint8_t* line_desc,
+                            Gate gate = kGateSE3) {
   const float scale = G.scale_factors[level];
   const float dtheta = (float)(10 * kPi / 180.f) * scale;   // Frame::kDeltaTheta (src/Frame.cc:99)
   const float dd = th * 100.0f * scale;                     // th * Frame::kDeltaD * scale, left to right
@@ -419,7 +431,7 @@ inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, i
   uint32_t qd[8];
   std::memcpy(qd, line_desc, 32);
   const Rep rr = right_rep(K, f);
-  Walk w{&K, &G, &f.rep, &rr, level, qd, 256, -1, false, false};
+  Walk w{&K, &G, &f.rep, &rr, level, qd, 256, -1, false, false, gate};
   walk_recursive(w, tmin, tmax, f.rep.d - dd, f.rep.d + dd, 0);
   Result res{-1, -1, kEmptyWindow};
   if (!w.any) return res;
@@ -430,11 +442,11 @@ inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, i
 
 // the whole pair on the host: level and theta are the reference's own expressions on the host's libm
 inline Result pair_host(const KfConst& K, const KfGrid& G, const float* start, const float* end, const float* normal, float max_dist,
-                        const uint8_t* line_desc, float th, int log_double_overload, int atan_double_overload) {
+                        const uint8_t* line_desc, float th, int log_double_overload, int atan_double_overload, Gate gate = kGateSE3) {
   const Front f = front(K, start, end, normal, max_dist);
   if (f.reached != kEmptyWindow) return Result{-1, -1, f.reached};
   return search_window(K, G, f, predict_level_host(f.ratio, K.log_scale_factor, K.n_levels, log_double_overload),
-                       theta_host(f.rep, atan_double_overload), th, line_desc);
+                       theta_host(f.rep, atan_double_overload), th, line_desc, gate);
 }
 
 }  // namespace linefuse

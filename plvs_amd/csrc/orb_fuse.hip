@@ -11,6 +11,11 @@
 // host entry's code after the wait, and their result is simply the host's.
 //
 // Map mutation (AddObservation, AddMapPoint, Replace) stays the caller's: INTEGRATION.md has the replay.
+//
+// The Sim3 overload of LoopClosing::SearchAndFuse (src/ORBmatcher.cc:1437-1553, fuse_pair.hpp's kGateSim3) runs over resident key
+// frames only, in one of two layouts: the wave-per-pair kernel above with the other gate, or the sieve (loop_fuse_sieve_kernel) —
+// a loop's points are spread over many key frames' views, most pairs die in front(), and a wave per pair spends 64 lanes on each
+// such rejection.  The sieve gives a THREAD to every pair first and a wave only to the survivors.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -80,6 +85,7 @@ static_assert(sizeof(KfRes) == 160, "the per-call table entry: stats[3] of the r
 
 // One wave, one pair past the tests of front(): the window walk in 64-member strides, the gates, the (distance, enumeration position)
 // key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and the resident kernel both call it.
+template <fp::Gate kGate>
 __device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, const FusePoints& P, int i, const Front& f, float th, int lane,
                                           int2* __restrict__ rec) {
   if (f.reached != fp::kEmptyWindow) {
@@ -108,7 +114,7 @@ __device__ __forceinline__ void walk_pair(const KfConst& K, const KfArrays& A, c
       const FrameGrid::Member mb = members[j];
       if (!fp::in_area(mb.x, mb.y, f.u, f.v, radius)) continue;
       any = true;
-      if (!fp::candidate_gate(f.u, f.v, f.ur, f.level, mb.x, mb.y, mb.octave, u_right[mb.idx], sig)) continue;
+      if (!fp::candidate_gate<kGate>(f.u, f.v, f.ur, f.level, mb.x, mb.y, mb.octave, kGate == fp::kGateSE3 ? u_right[mb.idx] : -1.0f, sig)) continue;
       gated = true;
       const uint4 ta = desc[2 * (size_t)mb.idx], tb = desc[2 * (size_t)mb.idx + 1];
       const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
@@ -160,12 +166,13 @@ __global__ __launch_bounds__(256) void fuse_window_kernel(const char* __restrict
   const KfArrays A{reinterpret_cast<const FrameGrid::Member*>(base + D.o_mem), reinterpret_cast<const int*>(base + D.o_start),
                    reinterpret_cast<const float*>(base + D.o_ur), reinterpret_cast<const uint4*>(base + D.o_desc),
                    reinterpret_cast<const float*>(base + D.o_sf), reinterpret_cast<const float*>(base + D.o_sig), D.n};
-  walk_pair(D.k, A, P, i, f, th, lane, out + pair);
+  walk_pair<fp::kGateSE3>(D.k, A, P, i, f, th, lane, out + pair);
 }
 
 // The resident layout: the table holds pointers into the handles' own allocations (keyframe_handle.hpp), nothing of a key frame is in
 // the call's block.  The pair index is the wave's: taken through readfirstlane, so the compiler knows it uniform and the pair's table
 // entry — pose, constants, pointers — is read by scalar loads and stays in scalar registers.
+template <fp::Gate kGate>
 __global__ __launch_bounds__(256) void fuse_window_resident_kernel(const KfRes* __restrict__ kfs, FusePoints P, float th, int2* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int pair = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -177,7 +184,55 @@ __global__ __launch_bounds__(256) void fuse_window_resident_kernel(const KfRes* 
   }
   const KfRes& D = kfs[k];
   const Front f = fp::front(D.k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
-  walk_pair(D.k, D.a, P, i, f, th, lane, out + pair);
+  walk_pair<kGate>(D.k, D.a, P, i, f, th, lane, out + pair);
+}
+
+// The sieve layout of the Sim3 search.  A workgroup takes a tile of 256 consecutive points of ONE key frame (grid: n_kfs *
+// ceil(m / 256), a tile never straddles key frames), so the key frame is the workgroup's: its table entry stays in scalar registers.
+//   phase 1, a thread per pair: skip and front(); a rejected pair posts its record at once (consecutive threads, consecutive
+//     records); a survivor goes to a list in LDS — its place from the wave's ballot and the four waves' counts, no atomics, so the
+//     list is in tile order whatever the scheduling;
+//   phase 2, a wave per survivor: wave w takes entries w, w + 4, ... through walk_pair, the text of the other layout.
+// A list entry: index in the tile, u, v, level | ambiguous << 8 (16 B x 256 = 4 KiB).  ur is not kept: the Sim3 gate does not read it.
+__global__ __launch_bounds__(256) void loop_fuse_sieve_kernel(const KfRes* __restrict__ kfs, FusePoints P, float th, int tiles_per_kf,
+                                                              int2* __restrict__ out) {
+  __shared__ int4 list[256];
+  __shared__ int wave_count[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)tiles_per_kf));
+  const int tile0 = __builtin_amdgcn_readfirstlane((int)(blockIdx.x - (unsigned)k * (unsigned)tiles_per_kf) * 256);
+  const KfRes& D = kfs[k];
+  const int i = tile0 + tid;
+  bool survivor = false;
+  Front f{fp::kSkipped, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (i < P.m) {
+    const int pair = k * P.m + i;
+    if (!(P.skip && P.skip[pair])) f = fp::front(D.k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
+    survivor = f.reached == fp::kEmptyWindow;
+    if (!survivor) out[pair] = pack(-1, -1, f.reached, 0);
+  }
+  const unsigned long long mask = __ballot(survivor);
+  if (lane == 0) wave_count[wave] = __popcll(mask);
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int w = 0; w < 4; ++w) {
+    const int c = wave_count[w];
+    before += w < wave ? c : 0;
+    total += c;
+  }
+  if (survivor) list[before + __popcll(mask & ((1ull << lane) - 1ull))] = make_int4(tid, __float_as_int(f.u), __float_as_int(f.v), f.level | (f.ambiguous << 8));
+  __syncthreads();
+  total = __builtin_amdgcn_readfirstlane(total);
+  for (int e = wave; e < total; e += 4) {   // e < total <= 256: inside the list
+    const int4 ent = list[e];
+    Front g{fp::kEmptyWindow, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+    const int t = __builtin_amdgcn_readfirstlane(ent.x), lv = __builtin_amdgcn_readfirstlane(ent.w);
+    g.u = __int_as_float(__builtin_amdgcn_readfirstlane(ent.y));
+    g.v = __int_as_float(__builtin_amdgcn_readfirstlane(ent.z));
+    g.level = lv & 0xff;
+    g.ambiguous = lv >> 8;
+    walk_pair<fp::kGateSim3>(D.k, D.a, P, tile0 + t, g, th, lane, out + (k * P.m + tile0 + t));
+  }
 }
 
 // pose = false: a handle's constants, the pose left at 0 (a resident call puts its own there)
@@ -223,6 +278,7 @@ struct PointPart : fj::Part {
   const Outputs out;
   int32_t* const stats;
   const int n_stats;   // 4: the source writes stats[3], the bytes it put into the call's copy in
+  fp::Gate gate = fp::kGateSE3;   // kGateSim3: the loop-closing overload (a resident source's)
 
   size_t o_tab = 0, o_pos = 0, o_nrm = 0, o_mind = 0, o_maxd = 0, o_pd = 0, o_skip = 0;   // from the part's inputs
   int st_host = 0, st_windows = 0;
@@ -241,7 +297,10 @@ struct PointPart : fj::Part {
   virtual fp::Result host_pair(int k, int i) = 0;   // one pair on the host: pair_host() over the source's grid and constants
 
   fp::Result pair_host(const fp::KfGrid<FrameGrid::Member>& G, const KfConst& c, int i) const {
-    return fp::pair_host(c, G, P->pos + 3 * (size_t)i, P->normal + 3 * (size_t)i, P->min_dist[i], P->max_dist[i], P->desc + 32 * (size_t)i, th, 0);
+    const float *pos = P->pos + 3 * (size_t)i, *nrm = P->normal + 3 * (size_t)i;
+    const uint8_t* d = P->desc + 32 * (size_t)i;
+    return gate == fp::kGateSim3 ? fp::pair_host<fp::kGateSim3>(c, G, pos, nrm, P->min_dist[i], P->max_dist[i], d, th, 0)
+                                 : fp::pair_host<fp::kGateSE3>(c, G, pos, nrm, P->min_dist[i], P->max_dist[i], d, th, 0);
   }
 
   size_t n_pairs() const { return (size_t)n_kfs * P->m; }
@@ -333,6 +392,8 @@ struct PointPart : fj::Part {
 
 // test / measurement hook.  1: the projection in a launch of its own in front of the windows; 2: the copy in alone
 thread_local int g_chained = 0;
+// test / measurement hook of the Sim3 search.  0: the sieve, 1: a wave per pair
+thread_local int g_loop_layout = 0;
 
 // Key frames staged per call: a KfDev table, and behind the query every key frame's members, cell starts, u_right, descriptors and
 // levels; the fronts of the chained layout are its scratch
@@ -424,12 +485,16 @@ KfArrays arrays_at(const char* block, const plvs_keyframe::Points& s) {
 // nothing else.  Nothing of a key frame is built, staged or copied.
 struct ResidentPoints : PointPart {
   const plvs_keyframe* const* const kfs;
-  const plvs_keyframe_pose* const poses;
+  const plvs_keyframe_pose* const poses;          // the SE3 search's
+  const plvs_keyframe_sim3_pose* const sim3;      // the Sim3 search's (one of the two is null)
+  const int layout;                               // of the Sim3 search
   std::vector<KfConst> consts;   // per listed key frame: the handle's constants with the call's pose
 
-  ResidentPoints(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, int n_kfs_, const plvs_fuse_points* P_, const uint8_t* skip_,
-                 float th_, const Outputs& out_, int32_t* stats_)
-      : PointPart(n_kfs_, P_, skip_, th_, out_, stats_, 4), kfs(kfs_), poses(poses_) {}
+  ResidentPoints(const plvs_keyframe* const* kfs_, const plvs_keyframe_pose* poses_, const plvs_keyframe_sim3_pose* sim3_, int n_kfs_,
+                 const plvs_fuse_points* P_, const uint8_t* skip_, float th_, const Outputs& out_, int32_t* stats_)
+      : PointPart(n_kfs_, P_, skip_, th_, out_, stats_, 4), kfs(kfs_), poses(poses_), sim3(sim3_), layout(g_loop_layout) {
+    if (sim3) gate = fp::kGateSim3;
+  }
 
   bool has_points(int k) const override { return kfs[k]->pt.n > 0; }
   size_t table_entry() const override { return sizeof(KfRes); }
@@ -438,8 +503,11 @@ struct ResidentPoints : PointPart {
     consts.resize((size_t)n_kfs);
     for (int k = 0; k < n_kfs; ++k) {
       KfConst& c = consts[k] = kfs[k]->pt.c;
-      for (int i = 0; i < 4; ++i) c.q[i] = poses[k].q_cw[i];
-      for (int i = 0; i < 3; ++i) { c.t[i] = poses[k].tcw[i]; c.Ow[i] = poses[k].Ow[i]; }
+      for (int i = 0; i < 4; ++i) c.q[i] = sim3 ? sim3[k].q_cw[i] : poses[k].q_cw[i];
+      for (int i = 0; i < 3; ++i) {
+        c.t[i] = sim3 ? sim3[k].tcw[i] : poses[k].tcw[i];
+        c.Ow[i] = sim3 ? sim3[k].Ow_points[i] : poses[k].Ow[i];
+      }
     }
   }
 
@@ -449,8 +517,16 @@ struct ResidentPoints : PointPart {
   }
 
   int launch_kfs(char*, const char* table, const FusePoints& FP, int2* rec, hipStream_t stream) override {
-    hipLaunchKernelGGL(fuse_window_resident_kernel, dim3(plvs::ceil_div(n_pairs(), 4)), dim3(256), 0, stream,
-                       reinterpret_cast<const KfRes*>(table), FP, th, rec);
+    const KfRes* tab = reinterpret_cast<const KfRes*>(table);
+    const dim3 per_pair(plvs::ceil_div(n_pairs(), 4));
+    if (!sim3) {
+      hipLaunchKernelGGL(fuse_window_resident_kernel<fp::kGateSE3>, per_pair, dim3(256), 0, stream, tab, FP, th, rec);
+    } else if (layout == 1) {
+      hipLaunchKernelGGL(fuse_window_resident_kernel<fp::kGateSim3>, per_pair, dim3(256), 0, stream, tab, FP, th, rec);
+    } else {
+      const int tiles = (int)plvs::ceil_div((size_t)P->m, 256);
+      hipLaunchKernelGGL(loop_fuse_sieve_kernel, dim3((unsigned)n_kfs * (unsigned)tiles), dim3(256), 0, stream, tab, FP, th, tiles, rec);
+    }
     return PLVS_OK;
   }
 
@@ -494,12 +570,12 @@ void plvs::kfhandle::stage_points(const plvs_fuse_keyframe& kf, plvs_keyframe* h
 
 int plvs::fusejob::make_point_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_points* P,
                                       const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats,
-                                      bool host_entry, std::unique_ptr<Part>* out) {
+                                      bool host_entry, std::unique_ptr<Part>* out, const plvs_keyframe_sim3_pose* sim3) {
   out->reset();
   int rc = check_call(kfs, n_kfs, P, th, best_idx, best_dist);
-  if (rc == PLVS_OK) rc = check_handles(kfs, poses, n_kfs, 1, host_entry);
+  if (rc == PLVS_OK) rc = check_handles(kfs, sim3 ? static_cast<const void*>(sim3) : poses, n_kfs, 1, host_entry);
   if (rc != PLVS_OK) return rc;
-  if (n_kfs > 0 && P->m > 0) out->reset(new ResidentPoints(kfs, poses, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
+  if (n_kfs > 0 && P->m > 0) out->reset(new ResidentPoints(kfs, poses, sim3, n_kfs, P, skip, th, Outputs{best_idx, best_dist, reached}, stats));
   return PLVS_OK;
 }
 
@@ -530,5 +606,7 @@ int plvs_hip_orb_fuse_search_host(const plvs_fuse_keyframe* kfs, int n_kfs, cons
 }
 
 void plvs_hip_orb_fuse_test_chained(int mode) { g_chained = (mode == 1 || mode == 2) ? mode : 0; }
+
+void plvs_hip_loop_fuse_test_layout(int mode) { g_loop_layout = mode == 1 ? 1 : 0; }
 
 }  // extern "C"

@@ -5,7 +5,10 @@
     kf.close()                                                                       # with the key frame, or on SetBadFlag
 
 A handle holds what the constructor fixes; the pose travels with each call.  Outputs are those of ORBmatcher.FuseSearch /
-LineMatcher.FuseSearch / FuseSearchPointsAndLines, with one more entry in stats: the bytes of the call's copy in."""
+LineMatcher.FuseSearch / FuseSearchPointsAndLines, with one more entry in stats: the bytes of the call's copy in.
+
+The Sim3 Fuse searches of LoopClosing::SearchAndFuse (loop_fuse_search_kf, line_loop_fuse_search_kf,
+loop_fuse_search_points_and_lines_kf) take the same handles and a Sim3Pose per key frame: the caller's own decomposition of Scw."""
 import ctypes
 from dataclasses import dataclass
 
@@ -35,6 +38,24 @@ class KeyFramePose:
     def as_c(self):
         f = lambda a, n: (_f * n)(*(np.zeros(n, np.float32) if a is None else np.asarray(a, np.float32).reshape(n)).tolist())
         return _PoseC(f(self.q_cw, 4), f(self.Rcw, 9), f(self.tcw, 3), f(self.Ow, 3))
+
+
+class _Sim3PoseC(ctypes.Structure):
+    _fields_ = [("q_cw", _f * 4), ("Rcw", _f * 9), ("tcw", _f * 3), ("Ow_points", _f * 3), ("Ow_lines", _f * 3)]
+
+
+@dataclass
+class Sim3Pose:
+    """plvs_keyframe_sim3_pose: Scw as the two Sim3 Fuse overloads decompose it, by the caller's own Sophus / Eigen."""
+    q_cw: np.ndarray        # SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()).unit_quaternion().coeffs(); None: zeros
+    Rcw: np.ndarray         # Scw.rotationMatrix(), 9, column-major; None: zeros
+    tcw: np.ndarray         # Scw.translation() / Scw.scale()
+    Ow_points: np.ndarray   # Tcw.inverse().translation(); None: zeros
+    Ow_lines: np.ndarray    # -Rcw.transpose() * tcw; None: zeros
+
+    def as_c(self):
+        f = lambda a, n: (_f * n)(*(np.zeros(n, np.float32) if a is None else np.asarray(a, np.float32).reshape(n)).tolist())
+        return _Sim3PoseC(f(self.q_cw, 4), f(self.Rcw, 9), f(self.tcw, 3), f(self.Ow_points, 3), f(self.Ow_lines, 3))
 
 
 def pose_of(points=None, lines=None):
@@ -97,7 +118,7 @@ def _lists(key_frames, poses):
     K = len(key_frames)
     assert len(poses) == K
     hs = (_vp * max(K, 1))(*[None if kf is None else kf.handle for kf in key_frames])
-    ps = (_PoseC * max(K, 1))(*[p.as_c() for p in poses])
+    ps = ((_Sim3PoseC if poses and isinstance(poses[0], Sim3Pose) else _PoseC) * max(K, 1))(*[p.as_c() for p in poses])
     return K, hs, ps
 
 
@@ -133,7 +154,7 @@ def line_fuse_search_kf(key_frames, poses, lines, th=3.0, skip=None, host=False,
 
 
 def fuse_search_points_and_lines_kf(key_frames, poses, points=None, th_points=3.0, skip_points=None, lines=None, th_lines=3.0,
-                                    skip_lines=None, stream=None):
+                                    skip_lines=None, stream=None, _name="plvs_hip_fuse_search_points_and_lines_kf"):
     """FuseSearchPointsAndLines over ONE list of resident key frames (plvs_hip_fuse_search_points_and_lines_kf).
     -> (points' dict or None, lines' dict or None, stats [3]: launches, waits, bytes of the copy in)."""
     K, hs, ps = _lists(key_frames, poses)
@@ -148,10 +169,39 @@ def fuse_search_points_and_lines_kf(key_frames, poses, points=None, th_points=3.
         lsk = None if skip_lines is None else np.ascontiguousarray(skip_lines, np.uint8).reshape(K, lc.m)
         l_out = _stats4(_fuse_outputs(K, lc.m, True, True))
     stats = np.full(3, -1, np.int32)
-    f = _lib.lib.plvs_hip_fuse_search_points_and_lines_kf
+    f = getattr(_lib.lib, _name)
     f.argtypes = [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]
     _lib.check(f(hs if K else None, ps if K else None, K, None if pc is None else ctypes.byref(pc), _lib.np_ptr(psk), th_points,
                  *[_lib.np_ptr(a) for a in p_out], None if lc is None else ctypes.byref(lc), _lib.np_ptr(lsk), th_lines,
                  *[_lib.np_ptr(a) for a in l_out], _lib.np_ptr(stats), stream))
     as_dict = lambda o: dict(best_idx=o[0], best_dist=o[1], reached=o[2], stats=o[3])
     return (None if points is None else as_dict(p_out)), (None if lines is None else as_dict(l_out)), stats
+
+
+def loop_fuse_search_kf(key_frames, sim3_poses, points, th=4.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """The search of ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) over resident key frames
+    (plvs_hip_orb_loop_fuse_search_kf / _kf_host): key frame k = (key_frames[k], sim3_poses[k]), a Sim3Pose each.
+    -> dict(best_idx [K,M], best_dist [K,M], reached [K,M], stats [4])."""
+    return _single("plvs_hip_orb_loop_fuse_search_kf", key_frames, sim3_poses, points, th, skip, host, stream, want_reached, outputs)
+
+
+def line_loop_fuse_search_kf(key_frames, sim3_poses, lines, th=4.0, skip=None, host=False, stream=None, want_reached=True, outputs=True):
+    """The search of LineMatcher::Fuse(pKF, Scw, vpLines, th, vpReplaceLine) over resident key frames
+    (plvs_hip_line_loop_fuse_search_kf / _kf_host)."""
+    return _single("plvs_hip_line_loop_fuse_search_kf", key_frames, sim3_poses, lines, th, skip, host, stream, want_reached, outputs)
+
+
+def loop_fuse_search_points_and_lines_kf(key_frames, sim3_poses, points=None, th_points=4.0, skip_points=None, lines=None, th_lines=4.0,
+                                         skip_lines=None, stream=None):
+    """Both Sim3 searches over ONE list of resident key frames in one call (plvs_hip_loop_fuse_search_points_and_lines_kf).
+    -> (points' dict or None, lines' dict or None, stats [3]: launches, waits, bytes of the copy in)."""
+    return fuse_search_points_and_lines_kf(key_frames, sim3_poses, points, th_points, skip_points, lines, th_lines, skip_lines, stream,
+                                           _name="plvs_hip_loop_fuse_search_points_and_lines_kf")
+
+
+def loop_fuse_test_layout(mode):
+    """plvs_hip_loop_fuse_test_layout: 0 = the sieve (default), 1 = a wave per pair, for the calling thread's later Sim3 point searches."""
+    f = _lib.lib.plvs_hip_loop_fuse_test_layout
+    f.argtypes = [_i]
+    f.restype = None
+    f(mode)
