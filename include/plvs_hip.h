@@ -1096,7 +1096,12 @@ int plvs_hip_elas_gap_interpolation(plvs_elas* e, float* D, int width, int heigh
  * calls of the pair left in HBM (they always do; pass D = NULL there to skip the download): leftRightConsistencyCheck
  * (lr_threshold >= 0), removeSmallSegments (speckle_size > 0), gapInterpolation (ipol_gap_width > 0), adaptiveMean
  * (filter_adaptive_mean) — the right map only unless postprocess_only_left (PLVS sets it, src/PointCloudKeyFrame.cc:349).
- * D1 / D2: host destinations of the finished maps, may be NULL; the maps stay in HBM. */
+ * D1 / D2: host destinations of the finished maps, may be NULL; the maps stay in HBM.
+ * lr_threshold < 0 with speckle_size > 0 is refused (PLVS_ERR_INVALID_ARG, also by plvs_hip_elas_process): without the
+ * left/right check the maps still hold computeDisparity's -1, which breaks the precondition of removeSmallSegments above
+ * (in the reference a -1 seed absorbs neighbouring segments of disparity <= threshold - 1; the device's components do not),
+ * and the reference has no switch that skips the check.  lr_threshold < 0 with speckle_size <= 0 runs gapInterpolation and
+ * adaptiveMean on the unchecked maps. */
 int plvs_hip_elas_postprocess(plvs_elas* e, int width, int height, int postprocess_only_left, int filter_adaptive_mean,
                               float* D1, float* D2);
 /* PointCloudKeyFrame::ProcessStereoLibelas' disparity -> depth (src/PointCloudKeyFrame.cc:399-420) from the left map in HBM

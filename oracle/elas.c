@@ -199,7 +199,7 @@ void oracle_elas_adaptive_mean(float* D, int32_t width, int32_t height, int32_t 
   float val[8];
   /* horizontal: the window ends at u, its output is `back` pixels behind */
   for (int32_t v = 3; v < H - 3; ++v) {
-    for (int32_t u = 0; u < taps - 1; ++u) val[u] = D_copy[v * W + u];
+    for (int32_t u = 0; u < taps - 1 && u < W; ++u) val[u] = D_copy[v * W + u];   /* (a line shorter than the window: nothing follows) */
     for (int32_t u = taps - 1; u < W; ++u) {
       const float centre = D_copy[v * W + (u - back)];
       val[u % taps] = D_copy[v * W + u];
@@ -209,7 +209,7 @@ void oracle_elas_adaptive_mean(float* D, int32_t width, int32_t height, int32_t 
   }
   /* vertical */
   for (int32_t u = 3; u < W - 3; ++u) {
-    for (int32_t v = 0; v < taps - 1; ++v) val[v] = D_tmp[v * W + u];
+    for (int32_t v = 0; v < taps - 1 && v < H; ++v) val[v] = D_tmp[v * W + u];
     for (int32_t v = taps - 1; v < H; ++v) {
       const float centre = D_tmp[(v - back) * W + u];
       val[v % taps] = D_tmp[v * W + u];

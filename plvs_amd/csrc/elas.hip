@@ -1225,6 +1225,10 @@ int plvs_hip_elas_compute_disparity(plvs_elas* h, const int32_t* support, int n_
   return PLVS_OK;
 }
 
+// (what plvs_hip_elas_postprocess and plvs_hip_elas_process answer to lr_threshold < 0 with speckle_size > 0)
+static const char kNoCheckNeedsNoSpeckles[] =
+    "lr_threshold < 0 (no left/right check) needs speckle_size <= 0: removeSmallSegments takes maps whose invalid pixels all "
+    "hold -10, and only the left/right check turns computeDisparity's -1 into -10";
 // (host flavours of the post-processing stages: one upload, the stage, one download)
 #define ELAS_STAGE_SIZES()                                                          \
   hipStream_t s = h->stream;                                                        \
@@ -1290,6 +1294,8 @@ int plvs_hip_elas_gap_interpolation(plvs_elas* h, float* D, int width, int heigh
 // leftRightConsistencyCheck (lr_threshold >= 0), removeSmallSegments (speckle_size > 0), gapInterpolation
 // (ipol_gap_width > 0), adaptiveMean (filter_adaptive_mean) — the right map only unless postprocess_only_left.  D1 / D2
 // (host, may be NULL): where the finished maps go; they also stay in HBM for plvs_hip_elas_depth_dev.
+// lr_threshold < 0 together with speckle_size > 0 is refused: without the left/right check the maps still hold
+// computeDisparity's -1, outside removeSmallSegments' precondition (the reference has no such switch to follow).
 int plvs_hip_elas_postprocess(plvs_elas* h, int width, int height, int postprocess_only_left, int filter_adaptive_mean, float* D1,
                               float* D2) {
   PLVS_REQUIRE(h, "null argument");
@@ -1297,6 +1303,7 @@ int plvs_hip_elas_postprocess(plvs_elas* h, int width, int height, int postproce
   ELAS_STAGE_SIZES();
   PLVS_REQUIRE(h->res_w[0] == W && h->res_h[0] == H && h->res_w[1] == W && h->res_h[1] == H,
                "no disparity maps of this size in HBM (plvs_hip_elas_compute_disparity for the left and the right image first)");
+  PLVS_REQUIRE(h->prm.lr_threshold >= 0 || h->prm.speckle_size <= 0, kNoCheckNeedsNoSpeckles);
   float* d1 = h->res[0].p;
   float* d2 = h->res[1].p;
   int rc = PLVS_OK;
@@ -1448,6 +1455,7 @@ int plvs_hip_elas_process(plvs_elas* h, const uint8_t* I1, const uint8_t* I2, co
   PLVS_REQUIRE(h && I1 && I2 && dims, "null argument");
   const int width = dims[0], height = dims[1], stride = dims[2];
   PLVS_REQUIRE(width >= 16 && height >= 16 && stride >= width, "image size / bytes per line");
+  PLVS_REQUIRE(h->prm.lr_threshold >= 0 || h->prm.speckle_size <= 0, kNoCheckNeedsNoSpeckles);   // (before any work)
   int32_t gd[3];
   grid_dims_of(h, width, height, gd);
   PLVS_REQUIRE((int64_t)gd[1] * gd[2] >= 2 * (int64_t)gd[1] + 2,

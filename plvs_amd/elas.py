@@ -116,7 +116,10 @@ class ElasGPU:
     def postProcess(self, width, height, postprocess_only_left=True, filter_adaptive_mean=True, download=True):
         """The rest of Elas::process behind its two computeDisparity calls (elas.cpp:100-135) in one call on the maps they
         left in HBM: leftRightConsistencyCheck, removeSmallSegments, gapInterpolation, adaptiveMean — the right map only
-        unless postprocess_only_left (PLVS sets it).  -> (D1, D2) float32, or None with download=False (depthDev next)."""
+        unless postprocess_only_left (PLVS sets it).  -> (D1, D2) float32, or None with download=False (depthDev next).
+        lr_threshold < 0 skips the left/right check and then needs speckle_size <= 0: removeSmallSegments takes maps whose
+        invalid pixels all hold -10, the unchecked maps still hold -1; the combination raises PlvsHipError
+        (PLVS_ERR_INVALID_ARG), here and in process()."""
         f = L.plvs_hip_elas_postprocess
         f.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp]
         D1 = np.empty(self._out_shape(width, height), np.float32) if download else None
