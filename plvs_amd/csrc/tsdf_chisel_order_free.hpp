@@ -256,7 +256,12 @@ static void launch_walk_fast(plvs_tsdf_chisel* h, const WalkCall& c, const WalkP
   uint32_t* const counts[3] = {&h->d_wctr->ndeferred, &h->d_wctr->ndeferred2, &h->d_wctr->ndeferred3};
   const uint32_t* const list = pass.src < 0 ? nullptr : h->w_deferred.p + (size_t)pass.src * c.ntiles;
   const uint32_t* const nlist = pass.src < 0 ? nullptr : counts[pass.src];
-  const auto kernel = c.d_grid ? walk_fast<E, true> : walk_fast<E, false>;
+  // (the direct and the list form are two kernels — walk_fast's kList; the small table is a first pass only, its list
+  // form is not built: launch_walk_passes)
+  constexpr bool kHasList = E != kFastEntriesSmall;
+  const bool listed = kHasList && list != nullptr;
+  const auto kernel = c.d_grid ? (listed ? walk_fast<E, true, kHasList> : walk_fast<E, true, false>)
+                               : (listed ? walk_fast<E, false, kHasList> : walk_fast<E, false, false>);
   hipLaunchKernelGGL(kernel, dim3(pass.grid), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, c.d_xyz, c.n, h->offsets.p,
                      c.nclouds, h->poses.p, h->dir, &h->d_ctr->num_chunks, h->d_wctr, h->rgbw, (const uint32_t*)nullptr, c.out,
                      c.runs, TileMap{1u, 0u, 1u}, kRecStride, list, nlist, h->w_deferred.p + (size_t)pass.dst * c.ntiles,
@@ -268,9 +273,10 @@ static void launch_walk_fast(plvs_tsdf_chisel* h, const WalkCall& c, const WalkP
 static void launch_walk_passes(plvs_tsdf_chisel* h, const WalkPlan& plan, const WalkCall& c, hipStream_t s) {
   for (int i = 0; i < plan.npasses; ++i) {
     const WalkPass& pass = plan.pass[i];
-    // (the plan's 1024 is the small CLASS, not a size: see kPlanSmallClass)
-    if (pass.entries == kPlanSmallClass) launch_walk_fast<kFastEntriesSmall>(h, c, pass, s);
-    else if (pass.entries == kFastEntries) launch_walk_fast<kFastEntries>(h, c, pass, s);
+    // (the plan's 1024 is the small CLASS, not a size: see kPlanSmallClass; the plan gives it every tile — a list would
+    // go to the next table, which holds whatever the small one does: the same records either way)
+    if (pass.entries == kPlanSmallClass && pass.src < 0) launch_walk_fast<kFastEntriesSmall>(h, c, pass, s);
+    else if (pass.entries == kFastEntries || pass.entries == kPlanSmallClass) launch_walk_fast<kFastEntries>(h, c, pass, s);
     else launch_walk_fast<kFastEntriesBig>(h, c, pass, s);
   }
   hipLaunchKernelGGL((walk_tiles<true, true>), dim3(kDeferGrid), dim3(kWalkRays), 0, s, h->P, h->scale_u, h->scale_w, c.d_xyz,

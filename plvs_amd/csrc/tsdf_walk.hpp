@@ -415,7 +415,9 @@ __device__ __forceinline__ int lean_reach(const Ray& ray) {   // how far (in vox
   const float maxDist = sqnorm3(ray.end[0] - ray.start[0], ray.end[1] - ray.start[1], ray.end[2] - ray.start[2]);
   return (int)(__builtin_amdgcn_sqrtf(maxDist)) + 3;
 }
-template <bool kAcc, bool kRuns, class SH>
+// kRayOfVp: the ray's index in the tile is the thread's (walk_fast: rays are never re-dealt) — the last-visitor maximum
+// takes it from the bits of vp the loop carries anyway (one bit-field extract) and `rid` is not live across the loop.
+template <bool kAcc, bool kRuns, bool kRayOfVp, class SH>
 __device__ __forceinline__ uint32_t walk_lean(const Params& P, const Pose& pose, const Ray& ray, SH& S, int ox, int oy,
                                               int oz, int tid, float wu_scaled, uint32_t q_w, int32_t* e_wuu,
                                               unsigned long long* e_wc, uint32_t* e_last, uint16_t* vlog, uint32_t rid) {
@@ -467,7 +469,8 @@ __device__ __forceinline__ uint32_t walk_lean(const Params& P, const Pose& pose,
       if (kAcc) {
         atomicAdd(&e_wuu[e], __float2int_rn(wu_scaled * u));
         atomicAdd(&e_wc[e], (1ull << 32) | (unsigned long long)q_w);
-        atomicMax(&e_last[e], rid);   // (the ray's index in the tile: = tid unless the tile's rays were re-dealt)
+        // (the ray's index in the tile: = tid unless the tile's rays were re-dealt)
+        atomicMax(&e_last[e], kRayOfVp ? (vp >> 1) & (uint32_t)(kWalkRays - 1) : rid);
       }
       vp += (uint32_t)(kWalkRays * sizeof(uint16_t));
     }
@@ -917,7 +920,7 @@ __global__ __launch_bounds__(kWalkRays, kWalkEntries > 2048 ? 2 : (kWalkEntries 
         ray_begin(ray, &cur);   // (walk_lean's own ray_begin is this one: common subexpression)
         if (won_s && dir_peek_slot(peek_s) >= 0) S.cslot[ci_s] = dir_peek_slot(peek_s);
         if (won_e && dir_peek_slot(peek_e) >= 0) S.cslot[ci_e] = dir_peek_slot(peek_e);
-        nv = walk_lean<kAcc, kRuns>(P, pose, ray, S, ox, oy, oz, tid, wu_scaled, q_w, e_wuu, e_wc, e_last, vlog, (uint32_t)tid);
+        nv = walk_lean<kAcc, kRuns, false>(P, pose, ray, S, ox, oy, oz, tid, wu_scaled, q_w, e_wuu, e_wc, e_last, vlog, (uint32_t)tid);
       }
     } else if (walks) {
       WALK_PROF(0);
@@ -1393,7 +1396,7 @@ __device__ __forceinline__ void walk_fast_tile(
       if (!fits) S.overflow = 1u;   // the rays of the tile are too far apart
     }
     if (fits) {
-      nv = walk_lean<true, true>(P, pose, ray, S, ox, oy, oz, tid, wu * scale_u, (uint32_t)__float2int_rn(wu * scale_w), e_wuu,
+      nv = walk_lean<true, true, true>(P, pose, ray, S, ox, oy, oz, tid, wu * scale_u, (uint32_t)__float2int_rn(wu * scale_w), e_wuu,
                                  e_wc, e_last, vlog, rid);
     }
   }
@@ -1658,7 +1661,11 @@ __device__ __forceinline__ void walk_fast_tile(
   if (ticket_sg != 0xFFFFFFFFu) out.seg_ticket[ticket_sg] = ticket;
 }
 
-template <int E, bool kGrid = false>
+// kList: the direct form (workgroup b walks tile b; tile_list / ntile_list are not read) and the list form are two kernels:
+// walk_fast_tile is inlined once in each, so the register allocator serves ONE voxel loop and one flush per kernel — the
+// two copies in one body cost the 1536-entry instances 44 - 72 bytes of scratch per lane, one reload of it inside the
+// voxel loop (profiles/walk_loop_spills.md).
+template <int E, bool kGrid = false, bool kList = false>
 __global__ __launch_bounds__(kWalkRays, walk_fast_waves(E)) void walk_fast(
     Params P, float scale_u, float scale_w, const float* __restrict__ xyz, int npoints,
     const int32_t* __restrict__ offsets, int nclouds, const Pose* __restrict__ poses, Directory dir,
@@ -1666,19 +1673,19 @@ __global__ __launch_bounds__(kWalkRays, walk_fast_waves(E)) void walk_fast(
     const uint32_t* __restrict__ sat, AccOut out, RunOut runs, TileMap tmap, uint32_t rec_stride,
     const uint32_t* __restrict__ tile_list, const uint32_t* __restrict__ ntile_list, uint32_t* __restrict__ deferred,
     uint32_t* __restrict__ ndeferred, const GridSrc* __restrict__ grid) {
-  if (!tile_list) {
+  if constexpr (!kList) {
     walk_fast_tile<E, kGrid>(P, scale_u, scale_w, xyz, npoints, offsets, nclouds, poses, dir, num_chunks, ctr, rgbw, sat, out, runs,
                       tmap, rec_stride, deferred, ndeferred, blockIdx.x, false, grid);
-    return;
-  }
-  // a list: the workgroups of a small grid take its entries in turn (a grid of one workgroup per POSSIBLE entry would
-  // queue thousands of empty workgroups behind the one-per-CU limit of the large table's LDS)
-  const uint32_t nlist = *ntile_list;
-  for (uint32_t lb = blockIdx.x; lb < nlist; lb += gridDim.x) {
-    const uint32_t e = tile_list[lb];
-    walk_fast_tile<E, kGrid>(P, scale_u, scale_w, xyz, npoints, offsets, nclouds, poses, dir, num_chunks, ctr, rgbw, sat, out, runs,
-                      tmap, rec_stride, deferred, ndeferred, e & 0x7FFFFFFFu, (e >> 31) == 0u, grid);
-    __syncthreads();   // (the next tile reuses the shared state)
+  } else {
+    // a list: the workgroups of a small grid take its entries in turn (a grid of one workgroup per POSSIBLE entry would
+    // queue thousands of empty workgroups behind the one-per-CU limit of the large table's LDS)
+    const uint32_t nlist = *ntile_list;
+    for (uint32_t lb = blockIdx.x; lb < nlist; lb += gridDim.x) {
+      const uint32_t e = tile_list[lb];
+      walk_fast_tile<E, kGrid>(P, scale_u, scale_w, xyz, npoints, offsets, nclouds, poses, dir, num_chunks, ctr, rgbw, sat, out,
+                        runs, tmap, rec_stride, deferred, ndeferred, e & 0x7FFFFFFFu, (e >> 31) == 0u, grid);
+      __syncthreads();   // (the next tile reuses the shared state)
+    }
   }
 }
 
