@@ -1921,6 +1921,71 @@ int plvs_hip_line_loop_fuse_search_kf_host(const plvs_keyframe* const* kfs, cons
  * start, the layout of plvs_hip_orb_fuse_search_kf.  Both give the same outputs. */
 void plvs_hip_loop_fuse_test_layout(int mode);
 
+/* ------------------------------------------- Loop detection: SearchByProjection(pKF, Scw, ...) over resident key frames
+ * The four loop-closing overloads that decide whether a loop or merge is accepted:
+ *   ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming)                 src/ORBmatcher.cc:509-615
+ *   ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)      :617-730
+ *   LineMatcher::SearchByProjection(pKF, Scw, vpLines, vpMatched, th, ratioHamming)                 src/LineMatcher.cc:1767-1909
+ *   LineMatcher::SearchByProjection(pKF, Scw, vpLines, vpLinesKFs, vpMatched, vpMatchedKF, th, ratioHamming)      :1913-2037
+ * as LoopClosing::DetectCommonRegionsFromBoW and FindMatchesByProjection call them (src/LoopClosing.cc:912/923 th 8 ratio 1.5,
+ * :956/965 th 5 ratio 1.0, :1237/1245 th 3 ratio 1.5): K key frames x ONE list of M map points or lines in one call.  Key frame
+ * k = (kfs[k], sim3_poses[k]): the caller's decomposition of Scw as for the Sim3 Fuse searches above — the point overloads read
+ * Ow_points = Tcw.inverse().translation() (:518-519), the line overloads Ow_lines = -Rcw.transpose() * tcw (:1770-1773).
+ * skip[k * m + i]: pMP->isBad() || spAlreadyFound.count(pMP) at the time of the call (:534, :1791).
+ * occupied (may be NULL, and so may any occupied[k]): occupied[k][j] != 0 — vpMatched[j] of key frame k is not null on entry; n_k
+ * bytes each (the handle's key points or key lines).  Every call site of the reference passes an all-null vpMatched.
+ *
+ * These overloads are GREEDY: `if(vpMatched[idx]) continue` (:587, :701, :1863, :2008) leaves out what an earlier point of the
+ * same call took, so a pair's result depends on the pairs before it.  A candidate passes the level band [level - 1, level] alone
+ * (no chi-square or point-to-line gate), and a match needs bestDist <= TH_LOW * ratioHamming, the product and the comparison in
+ * f32 as the reference computes them (TH_LOW 50 for points, 60 for lines).
+ * projection (the point entries): which overload's projection —
+ *   PLVS_LOOP_PROJECT_CAMERA  Pinhole::project, fx * x / z + cx (:548): the overload without vpPointsKFs
+ *   PLVS_LOOP_PROJECT_INVZ    invz = 1 / z; u = fx * (x * invz) + cx (:657-662): the overload with vpPointsKFs.  u and v can differ
+ *                             from the other's in the last bit.
+ * The line overloads share one projection (ProjectLineWithCheck).
+ *
+ * Outputs, K x M each: match_idx[k * m + i] — the key point or key line j that vpMatched[j] = vpPoints[i] was written to, else -1
+ * (the caller stores vpMatched, and with the KF overloads vpMatchedKF[j] = vpPointsKFs[i], from it); match_dist — that match's
+ * distance, else -1; reached (may be NULL) — the PLVS_FUSE_* / PLVS_LINE_FUSE_* codes through EMPTY_WINDOW, then NO_CANDIDATE:
+ * nobody in the window passed the level band; ABOVE_TH_LOW: no unclaimed member at or below the threshold (bestDist staying 256
+ * because every banded member was claimed included); CANDIDATE: matched.  nmatches (K entries, may be NULL): the reference's
+ * return value per key frame.  stats (5 entries, may be NULL): [0] pairs whose level (or theta) the host decided, [1] pairs that
+ * reached the window, [2] launches, [3] bytes this kind put into the call's copy in, [4] pairs whose posted list was truncated
+ * and wholly claimed at their turn, evaluated once more by the host in the greedy pass.
+ * Refused before anything is launched or written: ratio_hamming negative or NaN; TH_LOW * ratio_hamming >= 256 (a pair without a
+ * candidate would write vpMatched[-1]); an unknown projection; and everything the _kf entries above refuse (th, sizes, null
+ * arrays, the handle checks, the theta refusal of the line side).  Every result equals the reference's bit for bit. */
+#define PLVS_LOOP_PROJECT_CAMERA 0
+#define PLVS_LOOP_PROJECT_INVZ 1
+int plvs_hip_orb_loop_search_by_projection_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                              const plvs_fuse_points* P, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                              float ratio_hamming, int projection, int32_t* match_idx, int32_t* match_dist,
+                                              uint8_t* reached, int32_t* nmatches, int32_t* stats, void* stream);
+int plvs_hip_line_loop_search_by_projection_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                               const plvs_fuse_lines* L, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                               float ratio_hamming, int32_t* match_idx, int32_t* match_dist, uint8_t* reached,
+                                               int32_t* nmatches, int32_t* stats, void* stream);
+/* Both in one call over one key-frame list: one copy in, both kernels on one stream, one wait, then both greedy passes.  points or
+ * lines may be NULL (not both).  stats (3 entries, may be NULL): launches, device waits, bytes of the copy in. */
+int plvs_hip_loop_search_by_projection_points_and_lines_kf(
+    const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs, const plvs_fuse_points* points,
+    const uint8_t* skip_points, const uint8_t* const* occupied_points, float th_points, float ratio_hamming_points, int projection,
+    int32_t* point_match_idx, int32_t* point_match_dist, uint8_t* point_reached, int32_t* point_nmatches, int32_t* point_stats,
+    const plvs_fuse_lines* lines, const uint8_t* skip_lines, const uint8_t* const* occupied_lines, float th_lines,
+    float ratio_hamming_lines, int32_t* line_match_idx, int32_t* line_match_dist, uint8_t* line_reached, int32_t* line_nmatches,
+    int32_t* line_stats, int32_t* stats, void* stream);
+/* The same on the host copy, serially, with no HIP call (PLVS_KEYFRAME_HOST_ONLY handles and others alike): every pair by the
+ * host's code in the same greedy pass.  stats[0] = stats[2] = stats[3] = stats[4] = 0. */
+int plvs_hip_orb_loop_search_by_projection_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                   const plvs_fuse_points* P, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                                   float ratio_hamming, int projection, int32_t* match_idx, int32_t* match_dist,
+                                                   uint8_t* reached, int32_t* nmatches, int32_t* stats);
+int plvs_hip_line_loop_search_by_projection_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                    const plvs_fuse_lines* L, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                                    float ratio_hamming, int32_t* match_idx, int32_t* match_dist, uint8_t* reached,
+                                                    int32_t* nmatches, int32_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

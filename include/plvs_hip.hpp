@@ -608,6 +608,99 @@ inline int LoopFuseSearchPointsAndLines(const std::vector<const KeyFrameHandle*>
   return n;
 }
 
+// Loop detection: the SearchByProjection(pKF, Scw, ...) overloads of ORBmatcher (src/ORBmatcher.cc:509-615, :617-730) and LineMatcher
+// (src/LineMatcher.cc:1767-1909, :1913-2037) over resident key frames: key frame k = (keyFrames[k], poses[k]) and ONE list of map
+// points or lines (plvs_hip.h has the semantics).  matchIdx[k * m + i]: the key point or key line that vpMatched[...] = vpPoints[i]
+// was written to, else -1 — the caller stores vpMatched (and, with the KF overloads, vpMatchedKF) from it.
+struct LoopSearchResult {
+  std::vector<int32_t> matchIdx, matchDist;   // K x M
+  std::vector<uint8_t> reached;               // K x M, PLVS_FUSE_* / PLVS_LINE_FUSE_*
+  std::vector<int32_t> nmatches;              // K: the reference's return values
+  int32_t stats[5] = {0, 0, 0, 0, 0};         // host-decided pairs, pairs at a window, launches, copy-in bytes, lists recomputed
+  void prepare(size_t pairs, size_t kfs) {
+    matchIdx.assign(pairs + 1, -1);
+    matchDist.assign(pairs + 1, -1);
+    reached.assign(pairs + 1, 0);
+    nmatches.assign(kfs + 1, 0);
+  }
+  int finish(size_t pairs, size_t kfs) {
+    matchIdx.resize(pairs);
+    matchDist.resize(pairs);
+    reached.resize(pairs);
+    nmatches.resize(kfs);
+    int n = 0;
+    for (int32_t v : nmatches) n += v;
+    return n;
+  }
+};
+namespace detail {
+// occupied: empty, or one entry per key frame (an empty entry: NULL — nothing of that key frame's vpMatched is set on entry)
+inline std::vector<const uint8_t*> occupied_pointers(const std::vector<std::vector<uint8_t>>& occupied, size_t kfs) {
+  if (!occupied.empty() && occupied.size() != kfs) throw std::invalid_argument("LoopSearchByProjection: one occupied entry per key frame, or none");
+  std::vector<const uint8_t*> p(occupied.size());
+  for (size_t k = 0; k < occupied.size(); ++k) p[k] = occupied[k].empty() ? nullptr : occupied[k].data();
+  return p;
+}
+}  // namespace detail
+// projection: PLVS_LOOP_PROJECT_CAMERA (the overload without vpPointsKFs) or PLVS_LOOP_PROJECT_INVZ (the one with).  -> the matches
+// of all key frames
+inline int LoopSearchByProjection(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_sim3_pose>& poses,
+                                  const plvs_fuse_points& vpPoints, const uint8_t* skip, const std::vector<std::vector<uint8_t>>& occupied,
+                                  float th, float ratioHamming, int projection, LoopSearchResult& result, bool onHost = false,
+                                  void* stream = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const std::vector<const uint8_t*> occ = detail::occupied_pointers(occupied, keyFrames.size());
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpPoints.m;
+  result.prepare(pairs, keyFrames.size());
+  if (onHost)
+    check(plvs_hip_orb_loop_search_by_projection_kf_host(raw.data(), poses.data(), K, &vpPoints, skip, occ.empty() ? nullptr : occ.data(), th,
+                                                         ratioHamming, projection, result.matchIdx.data(), result.matchDist.data(),
+                                                         result.reached.data(), result.nmatches.data(), result.stats));
+  else
+    check(plvs_hip_orb_loop_search_by_projection_kf(raw.data(), poses.data(), K, &vpPoints, skip, occ.empty() ? nullptr : occ.data(), th,
+                                                    ratioHamming, projection, result.matchIdx.data(), result.matchDist.data(),
+                                                    result.reached.data(), result.nmatches.data(), result.stats, stream));
+  return result.finish(pairs, keyFrames.size());
+}
+inline int LoopSearchByProjection(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<plvs_keyframe_sim3_pose>& poses,
+                                  const plvs_fuse_lines& vpLines, const uint8_t* skip, const std::vector<std::vector<uint8_t>>& occupied,
+                                  float th, float ratioHamming, LoopSearchResult& result, bool onHost = false, void* stream = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const std::vector<const uint8_t*> occ = detail::occupied_pointers(occupied, keyFrames.size());
+  const int K = (int)keyFrames.size();
+  const size_t pairs = keyFrames.size() * (size_t)vpLines.m;
+  result.prepare(pairs, keyFrames.size());
+  if (onHost)
+    check(plvs_hip_line_loop_search_by_projection_kf_host(raw.data(), poses.data(), K, &vpLines, skip, occ.empty() ? nullptr : occ.data(), th,
+                                                          ratioHamming, result.matchIdx.data(), result.matchDist.data(), result.reached.data(),
+                                                          result.nmatches.data(), result.stats));
+  else
+    check(plvs_hip_line_loop_search_by_projection_kf(raw.data(), poses.data(), K, &vpLines, skip, occ.empty() ? nullptr : occ.data(), th,
+                                                     ratioHamming, result.matchIdx.data(), result.matchDist.data(), result.reached.data(),
+                                                     result.nmatches.data(), result.stats, stream));
+  return result.finish(pairs, keyFrames.size());
+}
+// both in one call (every reference call site passes an all-null vpMatched: no `occupied` here); stats (3 entries, may be null):
+// launches, waits, bytes of the copy in
+inline int LoopSearchByProjectionPointsAndLines(const std::vector<const KeyFrameHandle*>& keyFrames,
+                                                const std::vector<plvs_keyframe_sim3_pose>& poses, const plvs_fuse_points& vpPoints,
+                                                const uint8_t* skipPoints, float thPoints, float ratioHammingPoints, int projection,
+                                                LoopSearchResult& points, const plvs_fuse_lines& vpLines, const uint8_t* skipLines,
+                                                float thLines, float ratioHammingLines, LoopSearchResult& lines, int32_t stats[3] = nullptr,
+                                                void* stream = nullptr) {
+  const std::vector<const plvs_keyframe*> raw = detail::raw_handles(keyFrames, poses);
+  const size_t pp = keyFrames.size() * (size_t)vpPoints.m, lp = keyFrames.size() * (size_t)vpLines.m;
+  points.prepare(pp, keyFrames.size());
+  lines.prepare(lp, keyFrames.size());
+  check(plvs_hip_loop_search_by_projection_points_and_lines_kf(
+      raw.data(), poses.data(), (int)keyFrames.size(), &vpPoints, skipPoints, nullptr, thPoints, ratioHammingPoints, projection,
+      points.matchIdx.data(), points.matchDist.data(), points.reached.data(), points.nmatches.data(), points.stats, &vpLines, skipLines, nullptr,
+      thLines, ratioHammingLines, lines.matchIdx.data(), lines.matchDist.data(), lines.reached.data(), lines.nmatches.data(), lines.stats, stats,
+      stream));
+  return points.finish(pp, keyFrames.size()) + lines.finish(lp, keyFrames.size());
+}
+
 // Frame::ComputeStereoMatches: mvuRight / mvDepth of the left keypoints (-1 = none).
 inline void ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& mvKeys,
                                  const std::vector<uint8_t>& mDescriptors, const std::vector<KeyPoint>& mvKeysRight,

@@ -80,6 +80,16 @@ int make_point_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose
 int make_line_part_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_pose* poses, int n_kfs, const plvs_fuse_lines* L,
                       const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist, uint8_t* reached, int32_t* stats, bool host_entry,
                       std::unique_ptr<Part>* out, const plvs_keyframe_sim3_pose* sim3 = nullptr);
+// The loop-closing SearchByProjection overloads (loop_search_pair.hpp; orb_loop_search.hip, line_loop_search.hip): the refusals,
+// then the part.  Its collect() and host_all() run the greedy pass; nmatches of an empty part is the entry's to zero.
+int make_loop_search_point_part(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3, int n_kfs, const plvs_fuse_points* P,
+                                const uint8_t* skip, const uint8_t* const* occupied, float th, float ratio_hamming, int projection,
+                                int32_t* match_idx, int32_t* match_dist, uint8_t* reached, int32_t* nmatches, int32_t* stats, bool host_entry,
+                                std::unique_ptr<Part>* out);
+int make_loop_search_line_part(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3, int n_kfs, const plvs_fuse_lines* L,
+                               const uint8_t* skip, const uint8_t* const* occupied, float th, float ratio_hamming, int32_t* match_idx,
+                               int32_t* match_dist, uint8_t* reached, int32_t* nmatches, int32_t* stats, bool host_entry,
+                               std::unique_ptr<Part>* out);
 // the refusals of a handle list, in this order: a NULL handle or a handle without the side the call needs (side: 1 = points,
 // 2 = lines), for a device entry a host-only handle — all before any HIP call — and then a handle of another device
 int check_handles(const plvs_keyframe* const* kfs, const void* poses, int n_kfs, int side, bool host_entry);

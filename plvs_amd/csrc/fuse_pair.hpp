@@ -25,6 +25,12 @@
 // gate policy kGateSim3 of the same text: :1467-1499 is :1294-1337 without ur (the pose is the caller's decomposition of Scw,
 // plvs_hip.h: plvs_keyframe_sim3_pose), and a candidate passes the level band alone (:1520) — no chi-square gate.  bestDist starts at
 // INT_MAX there (:1513) and is compared <= TH_LOW (:1535): 256 serves, no Hamming distance lies above it.
+//
+// The loop-closing ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (:509-615) and its overload with
+// vpPointsKFs / vpMatchedKF (:617-730) are the same text again (loop_search_pair.hpp): the gate kGateSim3, the projection policy —
+// the first overload calls Pinhole::project (:548, kProjectCamera), the second multiplies by invz (:657-662, kProjectInvz: x * invz is
+// rounded before fx multiplies it, so u and v can differ in the last bit) — the exclusion `if(vpMatched[idx]) continue` in front of
+// the level band (:587, :701: `claimed`), and bestDist <= TH_LOW * ratioHamming as an integer cut (:606, :720: `cut`).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -52,6 +58,7 @@ enum Reached : int {
 constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / ROWS: KeyFrame copies mnGridCols / mnGridRows from them
 constexpr int kThLow = 50;                      // ORBmatcher::TH_LOW
 enum Gate : int { kGateSE3 = 0, kGateSim3 = 1 };   // which overload's candidate gate (see the head)
+enum Projection : int { kProjectCamera = 0, kProjectInvz = 1 };   // plvs_hip.h: PLVS_LOOP_PROJECT_* (see the head)
 
 // what the pair loop reads of pKF besides its grid
 struct KfConst {
@@ -73,14 +80,21 @@ struct Front {
 PLVS_FUSE_FN float dot3(const V3& a, const V3& b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }
 
 // :1294-1337 for one pair
+template <Projection kProjection = kProjectCamera>
 PLVS_FUSE_FN Front front(const KfConst& K, const float* pos, const float* normal, float min_dist, float max_dist) {
   Front f{kBehind, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
   const V3 pw{pos[0], pos[1], pos[2]};
   const V3 pc = trackpose::se3_act(K.q, K.t, pw);
   if (pc.z < 0.0f) return f;
   const float invz = 1.0f / pc.z;
-  f.u = K.fx * pc.x / pc.z + K.cx;
-  f.v = K.fy * pc.y / pc.z + K.cy;
+  if (kProjection == kProjectInvz) {
+    const float x = pc.x * invz, y = pc.y * invz;
+    f.u = K.fx * x + K.cx;
+    f.v = K.fy * y + K.cy;
+  } else {
+    f.u = K.fx * pc.x / pc.z + K.cx;
+    f.v = K.fy * pc.y / pc.z + K.cy;
+  }
   f.reached = kOutside;
   if (!(f.u >= K.min_x && f.u < K.max_x && f.v >= K.min_y && f.v < K.max_y)) return f;
   f.ur = f.u - K.mbf * invz;
@@ -168,9 +182,11 @@ struct KfGrid {
 
 struct Result { int best_idx, best_dist, reached; };
 
-// :1340-1408 for a pair whose tests passed, serially, with the level given (the host's)
+// :1340-1408 for a pair whose tests passed, serially, with the level given (the host's).  claimed (may be null): the members a
+// greedy overload's earlier pairs took (vpMatched[idx] != null), left out behind the gate; cut: the largest distance that is taken
 template <Gate kGate = kGateSE3, typename Member>
-inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Front& f, int level, float th, const uint8_t* point_desc) {
+inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Front& f, int level, float th, const uint8_t* point_desc,
+                            const uint8_t* claimed = nullptr, int cut = kThLow) {
   Result res{-1, -1, kEmptyWindow};
   const float radius = th * G.scale_factors[level];
   Cells w;
@@ -187,6 +203,7 @@ inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Fro
       any = true;
       if (!candidate_gate<kGate>(f.u, f.v, f.ur, level, m->x, m->y, m->octave, G.u_right[m->idx], G.inv_level_sigma2)) continue;
       gated = true;
+      if (claimed && claimed[m->idx]) continue;
       uint32_t td[8];
       std::memcpy(td, G.desc + 32 * (size_t)m->idx, 32);
       const int d = hamming256(qd, td);
@@ -194,7 +211,7 @@ inline Result search_window(const KfConst& K, const KfGrid<Member>& G, const Fro
     }
   }
   if (!any) return res;
-  res.reached = !gated ? kNoCandidate : (best <= kThLow ? kCandidate : kAboveThLow);
+  res.reached = !gated ? kNoCandidate : (best <= cut ? kCandidate : kAboveThLow);
   if (res.reached == kCandidate) { res.best_idx = best_idx; res.best_dist = best; }
   return res;
 }

@@ -205,3 +205,99 @@ int plvs_hip_loop_fuse_search_points_and_lines_kf(const plvs_keyframe* const* kf
 }
 
 }  // extern "C"
+
+// ---- Loop detection: the SearchByProjection(pKF, Scw, ...) overloads (orb_loop_search.hip, line_loop_search.hip).  nmatches of
+// a call without pairs (no part is made) is zeroed here, behind every refusal; a part writes its own with its other outputs.
+static void zero_nmatches(int32_t* nmatches, int n_kfs) {
+  for (int k = 0; nmatches && k < n_kfs; ++k) nmatches[k] = 0;
+}
+
+extern "C" {
+
+int plvs_hip_orb_loop_search_by_projection_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                              const plvs_fuse_points* P, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                              float ratio_hamming, int projection, int32_t* match_idx, int32_t* match_dist, uint8_t* reached,
+                                              int32_t* nmatches, int32_t* stats, void* stream) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_loop_search_point_part(kfs, sim3_poses, n_kfs, P, skip, occupied, th, ratio_hamming, projection, match_idx, match_dist,
+                                                 reached, nmatches, stats, false, &part);
+  if (rc != PLVS_OK) return rc;
+  if (!part) zero_nmatches(nmatches, n_kfs);
+  return fj::run_single(part.get(), stats, 5, stream, false);
+}
+
+int plvs_hip_orb_loop_search_by_projection_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                   const plvs_fuse_points* P, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                                   float ratio_hamming, int projection, int32_t* match_idx, int32_t* match_dist,
+                                                   uint8_t* reached, int32_t* nmatches, int32_t* stats) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_loop_search_point_part(kfs, sim3_poses, n_kfs, P, skip, occupied, th, ratio_hamming, projection, match_idx, match_dist,
+                                                 reached, nmatches, stats, true, &part);
+  if (rc != PLVS_OK) return rc;
+  if (!part) zero_nmatches(nmatches, n_kfs);
+  return fj::run_single(part.get(), stats, 5, nullptr, true);
+}
+
+int plvs_hip_line_loop_search_by_projection_kf(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                               const plvs_fuse_lines* L, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                               float ratio_hamming, int32_t* match_idx, int32_t* match_dist, uint8_t* reached, int32_t* nmatches,
+                                               int32_t* stats, void* stream) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_loop_search_line_part(kfs, sim3_poses, n_kfs, L, skip, occupied, th, ratio_hamming, match_idx, match_dist, reached,
+                                                nmatches, stats, false, &part);
+  if (rc != PLVS_OK) return rc;
+  if (!part) zero_nmatches(nmatches, n_kfs);
+  return fj::run_single(part.get(), stats, 5, stream, false);
+}
+
+int plvs_hip_line_loop_search_by_projection_kf_host(const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs,
+                                                    const plvs_fuse_lines* L, const uint8_t* skip, const uint8_t* const* occupied, float th,
+                                                    float ratio_hamming, int32_t* match_idx, int32_t* match_dist, uint8_t* reached,
+                                                    int32_t* nmatches, int32_t* stats) {
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_loop_search_line_part(kfs, sim3_poses, n_kfs, L, skip, occupied, th, ratio_hamming, match_idx, match_dist, reached,
+                                                nmatches, stats, true, &part);
+  if (rc != PLVS_OK) return rc;
+  if (!part) zero_nmatches(nmatches, n_kfs);
+  return fj::run_single(part.get(), stats, 5, nullptr, true);
+}
+
+int plvs_hip_loop_search_by_projection_points_and_lines_kf(
+    const plvs_keyframe* const* kfs, const plvs_keyframe_sim3_pose* sim3_poses, int n_kfs, const plvs_fuse_points* P, const uint8_t* skip_points,
+    const uint8_t* const* occupied_points, float th_points, float ratio_hamming_points, int projection, int32_t* point_match_idx,
+    int32_t* point_match_dist, uint8_t* point_reached, int32_t* point_nmatches, int32_t* point_stats, const plvs_fuse_lines* L,
+    const uint8_t* skip_lines, const uint8_t* const* occupied_lines, float th_lines, float ratio_hamming_lines, int32_t* line_match_idx,
+    int32_t* line_match_dist, uint8_t* line_reached, int32_t* line_nmatches, int32_t* line_stats, int32_t* stats, void* stream) {
+  PLVS_REQUIRE(P || L, "neither points nor lines");
+  PLVS_REQUIRE(sim3_poses || n_kfs <= 0, "null poses");
+  std::unique_ptr<fj::Part> points, lines;
+  if (P) {   // both kinds' refusals before anything is launched or written
+    const int rc = fj::make_loop_search_point_part(kfs, sim3_poses, n_kfs, P, skip_points, occupied_points, th_points, ratio_hamming_points,
+                                                   projection, point_match_idx, point_match_dist, point_reached, point_nmatches, point_stats,
+                                                   false, &points);
+    if (rc != PLVS_OK) return rc;
+  }
+  if (L) {
+    const int rc = fj::make_loop_search_line_part(kfs, sim3_poses, n_kfs, L, skip_lines, occupied_lines, th_lines, ratio_hamming_lines,
+                                                  line_match_idx, line_match_dist, line_reached, line_nmatches, line_stats, false, &lines);
+    if (rc != PLVS_OK) return rc;
+  }
+  for (int s = 0; s < 5; ++s) {
+    if (P && point_stats) point_stats[s] = 0;
+    if (L && line_stats) line_stats[s] = 0;
+  }
+  if (P && !points) zero_nmatches(point_nmatches, n_kfs);
+  if (L && !lines) zero_nmatches(line_nmatches, n_kfs);
+  if (stats) stats[0] = stats[1] = stats[2] = 0;
+  int launches = 0, waits = 0;
+  size_t copied = 0;
+  const int rc = fj::run_parts(points.get(), lines.get(), static_cast<hipStream_t>(stream), stream == nullptr, false, &launches, &waits, &copied);
+  if (stats) { stats[0] = launches; stats[1] = waits; stats[2] = (int32_t)copied; }
+  return rc;
+}
+
+}  // extern "C"

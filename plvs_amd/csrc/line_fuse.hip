@@ -23,6 +23,7 @@
 #include "fuse_jobs.hpp"
 #include "keyframe_handle.hpp"
 #include "line_fuse_pair.hpp"
+#include "line_fuse_tables.hpp"
 
 namespace {
 
@@ -31,9 +32,13 @@ namespace fj = plvs::fusejob;
 using lf::Front;
 using lf::KfConst;
 using lf::Member;
+using plvs::linefusetab::arrays_at;
+using plvs::linefusetab::FuseLines;
+using plvs::linefusetab::KfArrays;
+using plvs::linefusetab::KfRes;
+using plvs::linefusetab::kPosBits;
 
 constexpr int kMaxLevels = 64;
-constexpr int kPosBits = 23;   // a lane's key: distance (9 bits) above the enumeration position
 
 // one key frame in the staged block: the constants and where its arrays start (bytes from the block's start)
 struct KfDev {
@@ -42,33 +47,10 @@ struct KfDev {
   unsigned long long o_mem, o_start, o_desc, o_sf, o_sig;
 };
 
-struct FuseLines {
-  const float *start, *end, *normal, *max_dist;
-  const uint4* desc;
-  const uint8_t* skip;   // n_kfs x m, or null
-  int m, n_pairs;
-};
-
 // the record a pair posts: best_idx, and best_dist (16 bits, 0xffff = -1) | reached << 16 | ambiguous << 24
 __host__ __device__ inline int2 pack(int best_idx, int best_dist, int reached, int ambiguous) {
   return make_int2(best_idx, (best_dist & 0xffff) | (reached << 16) | (ambiguous << 24));
 }
-
-// where the walk finds one key frame's arrays: resolved from the staged block's offsets (KfDev) or the handle's pointers (KfRes)
-struct KfArrays {
-  const Member* members;
-  const int* start;
-  const uint4* desc;
-  const float *sf, *sig;
-  int n_members;
-};
-
-// one key frame of a resident call's table: the call's pose inside the handle's constants, and pointers into the handle's allocation
-struct KfRes {
-  KfConst k;
-  KfArrays a;
-};
-static_assert(sizeof(KfRes) == 168, "the per-call table entry: stats[3] of the resident entries is documented and tested from it");
 
 // One wave, one pair past front(): theta's plan and its ambiguity, the walk of the one or two sub-windows in 64-member strides, the
 // gates, the (distance, enumeration position) key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and
@@ -407,12 +389,6 @@ struct StagedLines : LinePart {
 };
 
 // ---------------------------------------------------------------------------------------------------- resident key frames
-KfArrays arrays_at(const char* block, const plvs_keyframe::Lines& s) {
-  return KfArrays{reinterpret_cast<const Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
-                  reinterpret_cast<const uint4*>(block + s.o_desc), reinterpret_cast<const float*>(block + s.o_sf),
-                  reinterpret_cast<const float*>(block + s.o_sig), s.n_members};
-}
-
 // Key frames resident in HBM (keyframe_handle.hpp): a KfRes table — pose, constants, pointers into the handles' allocations — and
 // nothing else.  Nothing of a key frame is built, staged or copied.
 struct ResidentLines : LinePart {

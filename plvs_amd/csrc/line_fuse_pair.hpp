@@ -40,6 +40,11 @@
 // mvLineInvLevelSigma2[nPredictedLevel] (:2463-2464), NOT [klLevel]; the right-image check is compiled out (#if 0, :2471).
 // bestDist starts at INT_MAX (:2426) and (bestDist <= TH_LOW) && (bestIdx >= 0) decides (:2530): 256 serves.
 //
+// The loop-closing LineMatcher::SearchByProjection(pKF, Scw, vpLines, vpMatched, th, ratioHamming) (:1767-1909) and its overload
+// with vpLinesKFs / vpMatchedKF (:1913-2037) are the gate policy kGateBand of the same text: the Sim3 overload's front (:1770-1773,
+// :1827-1844), a candidate gate of the level band alone (:1868) behind the exclusion `if(vpMatched[idx]) continue` (:1863:
+// `claimed`), and (bestDist <= TH_LOW * ratioHamming) && (bestIdx >= 0) as an integer cut (:1894: `cut`; loop_search_pair.hpp).
+//
 // THETA NEEDS THE HOST'S atan2.  GetLine2dRepresentation calls atan2(ny, nx) on two floats with <math.h> in scope: the
 // compiled reference calls atan2f (tests/golden/line_fuse_reference_facts.json records the undefined symbol).  No device
 // arctangent equals it bit for bit, and theta decides the > pi refusal, the two split tests and the row indices of every
@@ -84,7 +89,7 @@ enum Reached : int {
 constexpr int kRows = 36, kCols = 160;             // LINE_THETA_GRID_ROWS, LINE_D_GRID_COLS (include/Frame.h:72-73)
 constexpr int kThLow = 60;                         // LineMatcher::TH_LOW (src/LineMatcher.cc:88)
 constexpr int kThetaUlps = 4;
-enum Gate : int { kGateSE3 = 0, kGateSim3 = 1 };   // which overload's candidate gate (see the head)
+enum Gate : int { kGateSE3 = 0, kGateSim3 = 1, kGateBand = 2 };   // which overload's candidate gate (see the head)
 constexpr float kChi2 = 3.84f;                     // kChiSquareLinePointProj, a const float (:98)
 constexpr float kEps = 1.1920929e-07f;             // std::numeric_limits<float>::epsilon()
 constexpr double kPi = 3.14159265358979323846, kPi2 = 1.57079632679489661923;   // M_PI, M_PI_2
@@ -294,10 +299,11 @@ PLVS_LFUSE_FN Rep right_rep(const KfConst& K, const Front& f) {
   (void)representation(f.uS - K.mbf * f.invSz, f.vS, f.uE - K.mbf * f.invEz, f.vE, &r);
   return r;
 }
-// :2148-2250 (kGateSim3: :2437-2467, rr is not read) — true: the candidate's descriptor distance is taken
+// :2148-2250 (kGateSim3: :2437-2467, rr is not read; kGateBand: :1868 alone) — true: the candidate's descriptor distance is taken
 template <Gate kGate = kGateSE3>
 PLVS_LFUSE_FN bool candidate_gate(const Rep& pr, const Rep& rr, int level, const Member& m, const float* inv_level_sigma2) {
   if (m.octave < level - 1 || m.octave > level) return false;
+  if (kGate == kGateBand) return true;
   const float sig = inv_level_sigma2[kGate == kGateSim3 ? level : m.octave];
   const float ds = pr.nx * m.sx + pr.ny * m.sy - pr.d;
   const float de = pr.nx * m.ex + pr.ny * m.ey - pr.d;
@@ -384,6 +390,7 @@ struct Walk {
   int best, best_idx;
   bool any, gated;
   Gate gate;
+  const uint8_t* claimed;   // may be null: the members a greedy overload's earlier pairs took, left out behind the gate
 };
 inline void walk_leaf(Walk& w, const Leaf& leaf) {
   const Cells c = leaf_cells(*w.K, leaf);
@@ -393,10 +400,12 @@ inline void walk_leaf(Walk& w, const Leaf& leaf) {
     for (int j = s; j < e; ++j) {
       const Member& m = w.G->members[j];
       w.any = true;
-      if (!(w.gate == kGateSim3 ? candidate_gate<kGateSim3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)
-                                : candidate_gate<kGateSE3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)))
+      if (!(w.gate == kGateSim3   ? candidate_gate<kGateSim3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)
+            : w.gate == kGateBand ? candidate_gate<kGateBand>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)
+                                  : candidate_gate<kGateSE3>(*w.pr, *w.rr, w.level, m, w.G->inv_level_sigma2)))
         continue;
       w.gated = true;
+      if (w.claimed && w.claimed[m.idx]) continue;
       uint32_t td[8];
       std::memcpy(td, w.G->desc + 32 * (size_t)m.idx, 32);
       const int d = hamming256(w.qd, td);
@@ -420,9 +429,9 @@ inline void walk_recursive(Walk& w, float tmin, float tmax, float dmin, float dm
   walk_leaf(w, Leaf{tmin, tmax, dmin, dmax});
 }
 
-// :2124-2263 for a pair whose tests passed, serially, with the level and theta given (the host's)
+// :2124-2263 for a pair whose tests passed, serially, with the level and theta given (the host's).  cut: the largest distance taken
 inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, int level, float theta, float th, const uint8_t* line_desc,
-                            Gate gate = kGateSE3) {
+                            Gate gate = kGateSE3, const uint8_t* claimed = nullptr, int cut = kThLow) {
   const float scale = G.scale_factors[level];
   const float dtheta = (float)(10 * kPi / 180.f) * scale;   // Frame::kDeltaTheta (src/Frame.cc:99)
   const float dd = th * 100.0f * scale;                     // th * Frame::kDeltaD * scale, left to right
@@ -431,22 +440,23 @@ inline Result search_window(const KfConst& K, const KfGrid& G, const Front& f, i
   uint32_t qd[8];
   std::memcpy(qd, line_desc, 32);
   const Rep rr = right_rep(K, f);
-  Walk w{&K, &G, &f.rep, &rr, level, qd, 256, -1, false, false, gate};
+  Walk w{&K, &G, &f.rep, &rr, level, qd, 256, -1, false, false, gate, claimed};
   walk_recursive(w, tmin, tmax, f.rep.d - dd, f.rep.d + dd, 0);
   Result res{-1, -1, kEmptyWindow};
   if (!w.any) return res;
-  res.reached = !w.gated ? kNoCandidate : (w.best <= kThLow ? kCandidate : kAboveThLow);
+  res.reached = !w.gated ? kNoCandidate : (w.best <= cut ? kCandidate : kAboveThLow);
   if (res.reached == kCandidate) { res.best_idx = w.best_idx; res.best_dist = w.best; }
   return res;
 }
 
 // the whole pair on the host: level and theta are the reference's own expressions on the host's libm
 inline Result pair_host(const KfConst& K, const KfGrid& G, const float* start, const float* end, const float* normal, float max_dist,
-                        const uint8_t* line_desc, float th, int log_double_overload, int atan_double_overload, Gate gate = kGateSE3) {
+                        const uint8_t* line_desc, float th, int log_double_overload, int atan_double_overload, Gate gate = kGateSE3,
+                        const uint8_t* claimed = nullptr, int cut = kThLow) {
   const Front f = front(K, start, end, normal, max_dist);
   if (f.reached != kEmptyWindow) return Result{-1, -1, f.reached};
   return search_window(K, G, f, predict_level_host(f.ratio, K.log_scale_factor, K.n_levels, log_double_overload),
-                       theta_host(f.rep, atan_double_overload), th, line_desc, gate);
+                       theta_host(f.rep, atan_double_overload), th, line_desc, gate, claimed, cut);
 }
 
 }  // namespace linefuse

@@ -24,31 +24,29 @@
 #include "fuse_jobs.hpp"
 #include "fuse_pair.hpp"
 #include "keyframe_handle.hpp"
+#include "orb_fuse_tables.hpp"
 #include "orb_window.hpp"
 
 namespace {
 
 using plvs::fusepair::Front;
 using plvs::fusepair::KfConst;
+using plvs::orbfuse::arrays_at;
+using plvs::orbfuse::FusePoints;
+using plvs::orbfuse::KfArrays;
+using plvs::orbfuse::KfRes;
+using plvs::orbfuse::kPosBits;
 using plvs::orbwin::FrameGrid;
 namespace fp = plvs::fusepair;
 namespace fj = plvs::fusejob;
 
 constexpr int kMaxLevels = 64;
-constexpr int kPosBits = 23;   // a lane's key: distance (9 bits) above the enumeration position
 
 // one key frame in the staged block: the constants and where its arrays start (bytes from the block's start)
 struct KfDev {
   KfConst k;
   int n, pad;
   unsigned long long o_mem, o_start, o_ur, o_desc, o_sf, o_sig;
-};
-
-struct FusePoints {
-  const float *pos, *normal, *min_dist, *max_dist;
-  const uint4* desc;
-  const uint8_t* skip;   // n_kfs x m, or null
-  int m, n_pairs;
 };
 
 // the record a pair posts: best_idx, and best_dist (16 bits, 0xffff = -1) | reached << 16 | ambiguous << 24
@@ -65,23 +63,6 @@ __global__ __launch_bounds__(256) void fuse_front_kernel(const KfDev* __restrict
   if (!(P.skip && P.skip[pair])) f = fp::front(kfs[k].k, P.pos + 3 * (size_t)i, P.normal + 3 * (size_t)i, P.min_dist[i], P.max_dist[i]);
   fronts[pair] = f;
 }
-
-// where the walk finds one key frame's arrays: resolved from the staged block's offsets (KfDev) or the handle's pointers (KfRes)
-struct KfArrays {
-  const FrameGrid::Member* members;
-  const int* start;
-  const float* u_right;
-  const uint4* desc;
-  const float *sf, *sig;
-  int n;
-};
-
-// one key frame of a resident call's table: the call's pose inside the handle's constants, and pointers into the handle's allocation
-struct KfRes {
-  KfConst k;
-  KfArrays a;
-};
-static_assert(sizeof(KfRes) == 160, "the per-call table entry: stats[3] of the resident entries is documented and tested from it");
 
 // One wave, one pair past the tests of front(): the window walk in 64-member strides, the gates, the (distance, enumeration position)
 // key, the cross-lane minimum and the posted record.  ONE text: the staged kernel and the resident kernel both call it.
@@ -475,12 +456,6 @@ struct StagedPoints : PointPart {
 };
 
 // ---------------------------------------------------------------------------------------------------- resident key frames
-KfArrays arrays_at(const char* block, const plvs_keyframe::Points& s) {
-  return KfArrays{reinterpret_cast<const FrameGrid::Member*>(block + s.o_mem), reinterpret_cast<const int*>(block + s.o_start),
-                  reinterpret_cast<const float*>(block + s.o_ur), reinterpret_cast<const uint4*>(block + s.o_desc),
-                  reinterpret_cast<const float*>(block + s.o_sf), reinterpret_cast<const float*>(block + s.o_sig), s.n};
-}
-
 // Key frames resident in HBM (keyframe_handle.hpp): a KfRes table — pose, constants, pointers into the handles' allocations — and
 // nothing else.  Nothing of a key frame is built, staged or copied.
 struct ResidentPoints : PointPart {

@@ -205,3 +205,91 @@ def loop_fuse_test_layout(mode):
     f.argtypes = [_i]
     f.restype = None
     f(mode)
+
+
+# ---- loop detection: the SearchByProjection(pKF, Scw, ...) overloads
+PROJECT_CAMERA, PROJECT_INVZ = 0, 1
+
+
+def _occupied(occupied, K):
+    """-> (the const uint8_t* const* argument, what keeps its arrays alive).  occupied: None, or K entries, each None or n_k bytes."""
+    if occupied is None:
+        return None, None
+    assert len(occupied) == K
+    keep = [None if o is None else np.ascontiguousarray(o, np.uint8) for o in occupied]
+    return (_vp * max(K, 1))(*[None if o is None else o.ctypes.data for o in keep]), keep
+
+
+def _loop_search_outputs(K, M, want_reached):
+    return (np.full((K, M), -2, np.int32), np.full((K, M), -2, np.int32), np.full((K, M), 255, np.uint8) if want_reached else None,
+            np.full(K, -1, np.int32), np.full(5, -1, np.int32))
+
+
+def _loop_search(name, key_frames, sim3_poses, items, th, ratio_hamming, projection, skip, occupied, host, stream, want_reached):
+    K, hs, ps = _lists(key_frames, sim3_poses)
+    ic = items.as_c()
+    M = ic.m
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, M)
+    occ, keep = _occupied(occupied, K)
+    match_idx, match_dist, reached, nmatches, stats = _loop_search_outputs(K, M, want_reached)
+    args = [hs if K else None, ps if K else None, K, ctypes.byref(ic), _lib.np_ptr(sk), occ, th, ratio_hamming]
+    types = [_vp, _vp, _i, _vp, _vp, _vp, _f, _f]
+    if projection is not None:
+        args.append(projection)
+        types.append(_i)
+    args += [_lib.np_ptr(match_idx), _lib.np_ptr(match_dist), _lib.np_ptr(reached), _lib.np_ptr(nmatches), _lib.np_ptr(stats)]
+    types += [_vp] * 5
+    if not host:
+        args.append(stream)
+        types.append(_vp)
+    f = getattr(_lib.lib, name + ("_host" if host else ""))
+    f.argtypes = types
+    _lib.check(f(*args))
+    return dict(match_idx=match_idx, match_dist=match_dist, reached=reached, nmatches=nmatches, stats=stats)
+
+
+def loop_search_by_projection_kf(key_frames, sim3_poses, points, th=8.0, ratio_hamming=1.5, projection=PROJECT_CAMERA, skip=None,
+                                 occupied=None, host=False, stream=None, want_reached=True):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (projection = PROJECT_CAMERA) or its overload with
+    vpPointsKFs / vpMatchedKF (PROJECT_INVZ) over resident key frames (plvs_hip_orb_loop_search_by_projection_kf / _kf_host): key frame
+    k = (key_frames[k], sim3_poses[k]), ONE list of points.  occupied[k][j] != 0: vpMatched[j] of key frame k is not null on entry.
+    -> dict(match_idx [K,M], match_dist [K,M], reached [K,M], nmatches [K], stats [5])."""
+    return _loop_search("plvs_hip_orb_loop_search_by_projection_kf", key_frames, sim3_poses, points, th, ratio_hamming, projection, skip,
+                        occupied, host, stream, want_reached)
+
+
+def line_loop_search_by_projection_kf(key_frames, sim3_poses, lines, th=8.0, ratio_hamming=1.5, skip=None, occupied=None, host=False,
+                                      stream=None, want_reached=True):
+    """LineMatcher::SearchByProjection(pKF, Scw, vpLines, vpMatched, th, ratioHamming) and its overload with vpLinesKFs / vpMatchedKF
+    (one projection serves both) over resident key frames (plvs_hip_line_loop_search_by_projection_kf / _kf_host).
+    -> dict(match_idx [K,M], match_dist [K,M], reached [K,M], nmatches [K], stats [5])."""
+    return _loop_search("plvs_hip_line_loop_search_by_projection_kf", key_frames, sim3_poses, lines, th, ratio_hamming, None, skip, occupied,
+                        host, stream, want_reached)
+
+
+def loop_search_by_projection_points_and_lines_kf(key_frames, sim3_poses, points=None, th_points=8.0, ratio_hamming_points=1.5,
+                                                  projection=PROJECT_CAMERA, skip_points=None, occupied_points=None, lines=None, th_lines=8.0,
+                                                  ratio_hamming_lines=1.5, skip_lines=None, occupied_lines=None, stream=None):
+    """Both searches over ONE list of resident key frames in one call (plvs_hip_loop_search_by_projection_points_and_lines_kf).
+    -> (points' dict or None, lines' dict or None, stats [3]: launches, waits, bytes of the copy in)."""
+    K, hs, ps = _lists(key_frames, sim3_poses)
+    pc = lc = psk = lsk = pocc = locc = None
+    p_out = l_out = (None,) * 5
+    if points is not None:
+        pc = points.as_c()
+        psk = None if skip_points is None else np.ascontiguousarray(skip_points, np.uint8).reshape(K, pc.m)
+        pocc, pkeep = _occupied(occupied_points, K)
+        p_out = _loop_search_outputs(K, pc.m, True)
+    if lines is not None:
+        lc = lines.as_c()
+        lsk = None if skip_lines is None else np.ascontiguousarray(skip_lines, np.uint8).reshape(K, lc.m)
+        locc, lkeep = _occupied(occupied_lines, K)
+        l_out = _loop_search_outputs(K, lc.m, True)
+    stats = np.full(3, -1, np.int32)
+    f = _lib.lib.plvs_hip_loop_search_by_projection_points_and_lines_kf
+    f.argtypes = [_vp, _vp, _i, _vp, _vp, _vp, _f, _f, _i] + [_vp] * 5 + [_vp, _vp, _vp, _f, _f] + [_vp] * 5 + [_vp, _vp]
+    _lib.check(f(hs if K else None, ps if K else None, K, None if pc is None else ctypes.byref(pc), _lib.np_ptr(psk), pocc, th_points,
+                 ratio_hamming_points, projection, *[_lib.np_ptr(a) for a in p_out], None if lc is None else ctypes.byref(lc), _lib.np_ptr(lsk),
+                 locc, th_lines, ratio_hamming_lines, *[_lib.np_ptr(a) for a in l_out], _lib.np_ptr(stats), stream))
+    as_dict = lambda o: dict(match_idx=o[0], match_dist=o[1], reached=o[2], nmatches=o[3], stats=o[4])
+    return (None if points is None else as_dict(p_out)), (None if lines is None else as_dict(l_out)), stats
