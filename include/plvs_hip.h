@@ -956,9 +956,14 @@ int plvs_hip_tsdf_chisel_mesh_chunks(plvs_tsdf_chisel* h, const int32_t* chunk_i
  * fills (Rt = Twc_new * Tcw_at_integration).  Voxels whose kfid has no entry are dropped, as in the reference
  * (stats.discarded, its "num discarded voxels").  stats.undefined counts voxels whose new chunk (floor(p / (16 res)))
  * and new voxel (floor(p / res)) roundings disagree so that the reference indexes outside the chunk's voxel array
- * (undefined behaviour there): they are dropped.  PLVS_ERR_CAPACITY if the deformed map needs more than max_chunks
- * chunks; the map is then unchanged.  The updated-chunk list is empty afterwards (the reference leaves
- * meshesToUpdate alone and moves the stored meshes instead: deform_mesh). */
+ * (undefined behaviour there): they are dropped.  For finite inputs at the supported resolutions (0.01 to 0.1) it is
+ * 0: 1 / (16 res) is 1 / res scaled by a power of two, exactly, in binary32, so floor(p / (16 res)) is
+ * floor(floor(p / res) / 16) and the local index stays in [0, 16).  PLVS_ERR_CAPACITY if the deformed map needs more
+ * than max_chunks chunks or a chunk id outside [-2^20, 2^20); the map is then unchanged.  A deformation map with a
+ * NaN or an infinity in any Rt entry is refused with PLVS_ERR_INVALID_ARG before anything is touched, by deform, by
+ * deform_mesh and, where d_Rt is pinned host memory the call can read, by deform_mesh_dev (the reference converts
+ * such a position to INT_MIN and indexes out of bounds).  The updated-chunk list is empty afterwards (the reference
+ * leaves meshesToUpdate alone and moves the stored meshes instead: deform_mesh). */
 typedef struct plvs_tsdf_deform_stats {
   int32_t new_chunks;   /* chunks of the deformed map                                  */
   int64_t moved;        /* voxels that moved (copied or merged)                        */

@@ -77,6 +77,13 @@ void oracle_chisel_ordered_end_call(void* p) {
     if (!oracle_chisel_has_chunk(h->map, k.x, k.y, k.z)) h->chunks.erase(k);
   h->fresh.clear();
 }
+// A chunk created outside an integrate call (oracle_chisel_set_chunk; ChunkManager::CreateChunk, ChunkManager.h:99,
+// in the reference): the id enters the container if it is not there.  It is no visit: end_call never erases it.
+void oracle_chisel_ordered_note_created(void* p, int cx, int cy, int cz) {
+  Ordered* h = static_cast<Ordered*>(p);
+  const Id k{cx, cy, cz};
+  if (h->chunks.find(k) == h->chunks.end()) h->chunks.insert(std::make_pair(k, true));
+}
 // Chisel::Reset -> ChunkManager::Reset: chunks.clear() (the bucket array stays); call with oracle_chisel_clear.
 void oracle_chisel_ordered_reset(void* p) {
   Ordered* h = static_cast<Ordered*>(p);

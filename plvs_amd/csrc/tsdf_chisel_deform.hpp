@@ -22,9 +22,10 @@
 //   deform_fold                  one thread per new voxel: copy the first, merge the rest, write the new planes;
 //   install                      the new directory and planes replace the old ones.
 // Bit-exact against the CPU restatement of the reference, which is itself pinned against the compiled reference
-// library (tests/test_tsdf_deform.py, tests/test_oracle_pinned_chisel_map.py).
+// library (tests/test_tsdf_deform.py, tests/test_tsdf_deform_crafted.py, tests/test_oracle_pinned_chisel_map.py).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <unordered_map>
 
 #include "tsdf_chisel_handle.hpp"
@@ -389,6 +390,14 @@ static void deform_state_free(plvs_tsdf_chisel* h) {
   h->dfm = nullptr;
 }
 
+// A NaN or an infinity in a transformation has no voxel to go to: (int)floorf(NaN) is 0 on the device, INT_MIN (and
+// an out-of-bounds index) in the reference.  Such a deformation map is refused before anything is touched.
+static bool deform_map_finite(const float* Rt, int n_map) {
+  for (size_t i = 0; i < 12 * (size_t)n_map; ++i)
+    if (!std::isfinite(Rt[i])) return false;
+  return true;
+}
+
 static void deform_note_created(plvs_tsdf_chisel* h, int cx, int cy, int cz) {   // upload_chunk on a tracked map
   const ChunkIdKey k{cx, cy, cz};
   if (h->dfm->chunks.find(k) == h->dfm->chunks.end()) h->dfm->chunks.insert(std::make_pair(k, true));
@@ -448,6 +457,7 @@ int plvs_hip_tsdf_chisel_deform(plvs_tsdf_chisel* h, const uint32_t* kfids, cons
   PLVS_REQUIRE(h->dfm, "deform is not enabled on this map (plvs_hip_tsdf_chisel_enable_deform on the empty map)");
   PLVS_REQUIRE(n_map >= 0 && (n_map == 0 || (kfids && Rt)), "bad deformation map");
   for (int i = 1; i < n_map; ++i) PLVS_REQUIRE(kfids[i] > kfids[i - 1], "kfids must be strictly increasing");
+  PLVS_REQUIRE(deform_map_finite(Rt, n_map), "non-finite entry in a transformation");
   ChiselDeformState* st = h->dfm;
   hipStream_t s = nullptr;
   int rc = halo_drop(h, s);
@@ -580,6 +590,11 @@ int plvs_hip_tsdf_chisel_deform_mesh_dev(float* d_vertices, float* d_normals, co
   PLVS_REQUIRE(n >= 0 && n_map >= 0, "bad sizes");
   if (n == 0 || n_map == 0) return PLVS_OK;
   PLVS_REQUIRE(d_vertices && d_normals && d_vertex_kfid && d_kfids && d_Rt, "null device pointer");
+  // a transformation table in pinned host memory can be read here; one in HBM is the caller's to vouch for
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, d_Rt) != hipSuccess) (void)hipGetLastError();   // (a pointer the runtime does not know)
+  else if (attr.type == hipMemoryTypeHost && attr.hostPointer)
+    PLVS_REQUIRE(deform_map_finite(static_cast<const float*>(attr.hostPointer), n_map), "non-finite entry in a transformation");
   hipLaunchKernelGGL(deform_mesh_kernel, dim3(ceil_div((size_t)n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_vertices,
                      d_normals, d_vertex_kfid, n, d_kfids, d_Rt, n_map);
   PLVS_KERNEL_CHECK();
@@ -592,6 +607,7 @@ int plvs_hip_tsdf_chisel_deform_mesh(float* vertices, float* normals, const uint
   if (n == 0 || n_map == 0) return PLVS_OK;
   PLVS_REQUIRE(vertices && normals && vertex_kfid && kfids && Rt, "null argument");
   for (int i = 1; i < n_map; ++i) PLVS_REQUIRE(kfids[i] > kfids[i - 1], "kfids must be strictly increasing");
+  PLVS_REQUIRE(deform_map_finite(Rt, n_map), "non-finite entry in a transformation");
   DevBuf<float> v, nr, rt;
   DevBuf<uint32_t> vk, kf;
   int rc = PLVS_OK;

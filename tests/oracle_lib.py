@@ -444,6 +444,10 @@ class _ChiselLike:
         a = [np.ascontiguousarray(sdf, np.float32).reshape(4096), np.ascontiguousarray(weight, np.float32).reshape(4096),
              np.ascontiguousarray(kfid, np.uint32).reshape(4096), np.ascontiguousarray(rgbw, np.uint32).reshape(4096)]
         f(self.h, int(cx), int(cy), int(cz), *[_ptr(x) for x in a])
+        if getattr(self, "ordered", None):                       # CreateChunk: the id joins the tracked container
+            g = self.lib.oracle_chisel_ordered_note_created
+            g.restype, g.argtypes = None, [_vp, _i, _i, _i]
+            g(self.ordered, int(cx), int(cy), int(cz))
 
     def mesh_chunk(self, cx, cy, cz):
         """ChunkManager::RecomputeMesh of one chunk -> (vertices, normals, colors [n,3] f32, kfids [n] u32)

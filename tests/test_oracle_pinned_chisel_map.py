@@ -277,6 +277,51 @@ def test_deform_equals_the_reference_library(oracle, res, drop):
     ref.close()
 
 
+def _crafted_names():
+    from tests import deform_crafted_scenario as S
+    return S.NAMES
+
+
+@pytest.mark.skipif(not os.path.exists(REF_SET_CHUNK),
+                    reason="oracle/_ref/libchisel_set_chunk_ref.so (built where /root/reference exists) not present")
+@pytest.mark.parametrize("name", _crafted_names())
+def test_deform_of_crafted_chunks_equals_the_reference_library(oracle, name):
+    """The cases of tests/deform_crafted_scenario.py (runs of thousands of claimants, the colour freeze, weights around
+    1e-15, kfids beyond 2^31, ids next to 2^20, emptied maps): chunks go in through CreateChunk and the voxels' setters,
+    so the oracle's container has to take them as the reference's does; then every deform, and the integrates after.
+    The deforms the device refuses are the only steps left out: they never reach its map."""
+    from tests import deform_crafted_scenario as S
+    c = S.case(name)
+    ref, ora = RefChisel(c["res"], S.small_cam(8)), oracle.chisel(c["res"]).track_order()
+
+    def same():
+        assert [tuple(x) for x in ora.chunk_order()] == [tuple(x) for x in ref.chunk_ids()]
+        return maps_identical(ref, ora)
+
+    deforms = 0
+    for step in c["steps"]:
+        if step[0] == "upload":
+            for cid, *planes in step[1]:
+                ref.set_chunk(*cid, *planes)
+                ora.set_chunk(*cid, *planes)
+        elif step[0] == "integrate":
+            kf = step[1]
+            ref.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+            ora.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+            ora.end_call()
+        elif step[0] == "deform":
+            n_new, _, undefined = ora.deform(step[2], step[3])
+            assert undefined == 0                                # (the reference would index out of bounds there)
+            ref.deform(step[2], step[3])
+            assert same() == n_new
+            deforms += 1
+        else:
+            continue
+        same()
+    assert deforms > 0
+    ref.close()
+
+
 def test_deform_moves_the_stored_meshes_as_the_reference_library_does(oracle):
     cam = small_cam(4)
     ref, ora = RefChisel(0.05, cam), oracle.chisel(0.05).track_order()

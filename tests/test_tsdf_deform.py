@@ -140,10 +140,22 @@ def test_hip_deform_with_carving_and_uploaded_chunks(oracle):
     kfs = make_keyframes(3, cam=cam, seed=79)
     ora = oracle.chisel(0.05).track_order()
     dev = TsdfChisel(0.05, max_chunks=4096).enable_deform()
-    for kf in kfs:
+    from tests.deform_crafted_scenario import fill
+    rng = np.random.default_rng(81)
+    for i, kf in enumerate(kfs):
         ora.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
         ora.end_call()
         dev.integrate(kf["xyz"], kf["rgb"], kf["kfid"], kf["Twc"])
+        if i == 0:
+            # between the integrates: a chunk the scans never reach is created, one they filled is replaced
+            # (CreateChunk enters the container only for the first)
+            taken = sorted(tuple(int(v) for v in c) for c in ora.chunk_ids())
+            for cid in ((40, -3, 2), taken[len(taken) // 2]):
+                planes = fill(rng, (0, 1, 2))
+                ora.set_chunk(*cid, *planes)
+                dev.set_chunk(*cid, *planes)
+            assert (40, -3, 2) in order_of(dev) and len(order_of(dev)) == len(taken) + 1
+        assert order_of(dev) == order_of(ora)
     depth = np.full((cam["height"], cam["width"]), 4.2, np.float32)     # carving resets voxels: they no longer move
     n_ora, _ = ora.carve(depth, cam["fx"], cam["fy"], cam["cx"], cam["cy"], kfs[0]["Twc"])
     n_dev = dev.carve(depth, cam["fx"], cam["fy"], cam["cx"], cam["cy"], kfs[0]["Twc"])
