@@ -41,6 +41,7 @@
 #include "tsdf_directory.hpp"
 #include "tsdf_tiles.hpp"
 #include "tsdf_walk_table.hpp"
+#include "tsdf_walk_visit.hpp"
 
 namespace {
 
@@ -143,6 +144,7 @@ constexpr int kOriginBias = 512;
 constexpr int log2_of(int v) { return v <= 1 ? 0 : 1 + log2_of(v / 2); }
 struct WalkShared {       // LDS state of walk_tiles
   static constexpr int kEntries = kWalkEntries, kBucketCount = kWalkEntries / 4, kLogLen = ::kLogLen;
+  static constexpr int kSpillCap = -1;         // (no list of late visits, no count of them: a ray behind a full log walks again)
   alignas(16) uint32_t ekey[kWalkEntries];
   int32_t org[3];                              // origin of the keys
   uint32_t cand[kWalkRays / 64];               // does the wave have a walking ray ...
@@ -167,8 +169,8 @@ struct WalkShared {       // LDS state of walk_tiles
 // E / kWalkRays entries, a bucket has four (home_bucket / next_bucket, tsdf_walk_table.hpp).
 // The LDS of a CU is handed out in blocks of 1280 B (gfx950): a 1536-entry tile with the visit log of the others would
 // take 54 176 B = 43 blocks, and three of them 129 of the CU's 128.  Its log keeps 15 visits per ray instead of 16
-// (53 152 B, 42 blocks): a ray with more visits walks again for its masks, as it does behind any full log — the same
-// masks, the same map.
+// (53 664 B with the list of late visits, 42 blocks): the visits of a ray behind its log go to that list (`spill`, below),
+// as they do behind any full log — the same masks, the same map.
 template <int E>
 struct FastShared {
   static constexpr int kEntries = E, kBucketCount = E / 4, kLogLen = E == 1536 ? ::kLogLen - 1 : ::kLogLen;
@@ -185,6 +187,13 @@ struct FastShared {
   uint16_t rcbase[kWalkChunks * kSlabs];  // the group's first run among the tile's (every wave writes the same table)
   uint32_t any_cold;                      // a voxel of the tile needs a run
   uint32_t nent, overflow;
+  // The visits behind a full log row (a ray with more than kLogLen visits: a far surface seen along the grid's diagonal), as
+  // ray << 16 | entry, in the order the counter hands out — the mask rounds OR them in beside the logs.  A tile with more of
+  // them than the list holds (nspill counts on) walks its long rays again instead: the same masks either way.
+  // 128 words: what is left below the 42 LDS blocks of the 1536-entry instance (53 760 B, profiles/walk_table_1536.md).
+  static constexpr int kSpillCap = 128;
+  uint32_t nspill;
+  uint32_t spill[kSpillCap];
 };
 
 
@@ -417,7 +426,9 @@ __device__ __forceinline__ int lean_reach(const Ray& ray) {   // how far (in vox
 }
 // kRayOfVp: the ray's index in the tile is the thread's (walk_fast: rays are never re-dealt) — the last-visitor maximum
 // takes it from the bits of vp the loop carries anyway (one bit-field extract) and `rid` is not live across the loop.
-template <bool kAcc, bool kRuns, bool kRayOfVp, class SH>
+// kVisitWords: the tile's rays are one image's (walk_fast_tile<E, true>) — a visit adds to the two words of
+// tsdf_walk_visit.hpp, e_wc[e] (the sums) and e_last[e] (count and ray sum): two atomics, no maximum; e_wuu is not used.
+template <bool kAcc, bool kRuns, bool kRayOfVp, bool kVisitWords = false, class SH>
 __device__ __forceinline__ uint32_t walk_lean(const Params& P, const Pose& pose, const Ray& ray, SH& S, int ox, int oy,
                                               int oz, int tid, float wu_scaled, uint32_t q_w, int32_t* e_wuu,
                                               unsigned long long* e_wc, uint32_t* e_last, uint16_t* vlog, uint32_t rid) {
@@ -464,9 +475,18 @@ __device__ __forceinline__ uint32_t walk_lean(const Params& P, const Pose& pose,
         }
       }
       if (__builtin_expect(e < 0, 0)) break;   // the table is full: the (sub-)tile is cut
-      if (kRuns && vp < (uint32_t)(SH::kLogLen * kWalkRays * sizeof(uint16_t)))
+      if (kRuns && vp < (uint32_t)(SH::kLogLen * kWalkRays * sizeof(uint16_t))) {
         *reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(vlog) + vp) = (uint16_t)e;
-      if (kAcc) {
+      } else if constexpr (kRuns && kRayOfVp && SH::kSpillCap >= 0) {   // (behind the log's last row: FastShared::spill)
+        const uint32_t n = atomicAdd(&S.nspill, 1u);
+        if (n < (uint32_t)SH::kSpillCap) S.spill[n] = (((vp >> 1) & (uint32_t)(kWalkRays - 1)) << 16) | (uint32_t)e;
+      }
+      if (kAcc && kVisitWords) {
+        static_assert(!kVisitWords || kRayOfVp, "the visit words are the lean tiles': the ray is the thread");
+        atomicAdd(&e_wc[e], plvs::tsdf::visit_sums_word(__float2int_rn(wu_scaled * u), q_w));
+        // (the ray in bits 1..9 of vp, the count's bit beside it: (ray << 10) | 1 is one and-or of vp << 9)
+        atomicAdd(&e_last[e], plvs::tsdf::visit_count_word((vp >> 1) & (uint32_t)(kWalkRays - 1)));
+      } else if (kAcc) {
         atomicAdd(&e_wuu[e], __float2int_rn(wu_scaled * u));
         atomicAdd(&e_wc[e], (1ull << 32) | (unsigned long long)q_w);
         // (the ray's index in the tile: = tid unless the tile's rays were re-dealt)
@@ -1300,9 +1320,13 @@ __device__ __forceinline__ void walk_fast_tile(
   constexpr bool kMidxOverlay = sizeof(S.ccnt) + sizeof(S.cbase) >= E * sizeof(uint16_t);
   __shared__ uint16_t e_midx_own[kMidxOverlay ? 1 : E];
   uint16_t* const e_midx = kMidxOverlay ? reinterpret_cast<uint16_t*>(S.ccnt) : e_midx_own;
+  // kGrid — the rays of the tile are one image's — keeps the two visit words of tsdf_walk_visit.hpp per entry instead: the
+  // sums (64 bits, words 0 .. 2E) and the count with the ray sum (words 2E .. 3E).  The last E words are mask area only.
+  static_assert(plvs::tsdf::visit_words_hold<kWalkRays>(), "count and ray sum of a whole tile fit the count word");
   int32_t* const e_wuu = reinterpret_cast<int32_t*>(raw);                                 // sum of w_u * u, fixed point
-  unsigned long long* const e_wc = reinterpret_cast<unsigned long long*>(raw + E);   // visits << 32 | sum of w_u
-  uint32_t* const e_last = raw + 3 * E;                                             // last visiting ray
+  unsigned long long* const e_wc = reinterpret_cast<unsigned long long*>(kGrid ? raw : raw + E);   // visits << 32 | sum of w_u (kGrid: the sums)
+  uint32_t* const e_last = raw + (kGrid ? 2 : 3) * E;                               // last visiting ray (kGrid: the count word)
+  constexpr int kAccWords = kGrid ? 3 : 4;                                          // words per entry the walk adds into
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   // (tile = the local tile: output regions; listed_other = a listed tile that is not an overflow: passed on)
   const uint32_t gtile = tmap.tile_of(tile);             // its place in the point stream
@@ -1339,11 +1363,12 @@ __device__ __forceinline__ void walk_fast_tile(
 #pragma unroll
     for (int k = 0; k < kWalkChunks * kSlabs / kWalkRays; ++k) S.rcnt[tid + k * kWalkRays] = 0u;
 #pragma unroll
-    for (int k = 0; k < 4 * kPer; ++k) raw[tid + k * kWalkRays] = 0u;
+    for (int k = 0; k < kAccWords * kPer; ++k) raw[tid + k * kWalkRays] = 0u;
     if (tid == 0) {
       S.run_total = 0;
       S.vis_total = 0;
       S.any_cold = 0;
+      S.nspill = 0;
     }
     Ray ray;
     if (kGrid) {
@@ -1396,8 +1421,8 @@ __device__ __forceinline__ void walk_fast_tile(
       if (!fits) S.overflow = 1u;   // the rays of the tile are too far apart
     }
     if (fits) {
-      nv = walk_lean<true, true, true>(P, pose, ray, S, ox, oy, oz, tid, wu * scale_u, (uint32_t)__float2int_rn(wu * scale_w), e_wuu,
-                                 e_wc, e_last, vlog, rid);
+      nv = walk_lean<true, true, true, kGrid>(P, pose, ray, S, ox, oy, oz, tid, wu * scale_u, (uint32_t)__float2int_rn(wu * scale_w),
+                                              e_wuu, e_wc, e_last, vlog, rid);
     }
   }
   uint32_t ekey[kPer];
@@ -1471,7 +1496,9 @@ __device__ __forceinline__ void walk_fast_tile(
     for (int k = 0; k < kPer; ++k) {
       if (vkey[k] == 0xFFFFFFFFu) continue;
       const uint32_t vid = vkey[k] % (uint32_t)kChunkVox;
-      ewc[k] = e_wc[tid + k * kWalkRays];
+      // (kGrid: the count word alone lives across the barrier — visits, and the ray where there is one; the sums are read
+      // where the record is written)
+      if (!kGrid) ewc[k] = e_wc[tid + k * kWalkRays];
       elast[k] = e_last[tid + k * kWalkRays];
       rank[k] = atomicAdd(&S.ccnt[ci[k] * kSlabs + (int)(vid / kSlabVox)], 1u);
     }
@@ -1481,7 +1508,7 @@ __device__ __forceinline__ void walk_fast_tile(
       const bool cold = sat ? ((cw[k] >> (vkey[k] & 31u)) & 1u) == 0u : (cw[k] >> 24) < 254u;
       if (cold) {   // its colour still depends on the order of the visits
         need |= 1u << k;
-        multi = multi || (uint32_t)(ewc[k] >> 32) > 1u;
+        multi = multi || (kGrid ? plvs::tsdf::visit_count(elast[k]) : (uint32_t)(ewc[k] >> 32)) > 1u;
         // (its place among the runs of its (chunk, slab) group — the runs of a tile leave it grouped like its records)
         rrank[k] = atomicAdd(&S.rcnt[ci[k] * kSlabs + (int)((vkey[k] % (uint32_t)kChunkVox) / kSlabVox)], 1u);
       }
@@ -1565,13 +1592,22 @@ __device__ __forceinline__ void walk_fast_tile(
       }
     }
   }
+  const uint32_t tile_key = kGrid ? grid_order_key(*grid, gt, 0u) : 0u;
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {
     if (vkey[k] == 0xFFFFFFFFu) continue;
     const uint32_t vid = vkey[k] % (uint32_t)kChunkVox;
-    const uint4 r = make_uint4(vid | ((uint32_t)(ewc[k] >> 32) << 12),
-                               grid ? grid_order_key(*grid, gt, elast[k]) : first + elast[k],
-                               (uint32_t)e_wuu[tid + k * kWalkRays], (uint32_t)ewc[k]);
+    uint4 r;
+    if (kGrid) {
+      // (the order key of the tile's first pixel for every entry: the apply stage reads the image of a maximum of such
+      // keys and nothing else; the tiles walk_tiles takes write a key per entry, of the same image wherever they meet these)
+      const unsigned long long sums = e_wc[tid + k * kWalkRays];
+      r = make_uint4(vid | (plvs::tsdf::visit_count(elast[k]) << 12), tile_key, plvs::tsdf::visit_sum_wuu(sums),
+                     plvs::tsdf::visit_sum_w(sums));
+    } else {
+      r = make_uint4(vid | ((uint32_t)(ewc[k] >> 32) << 12), first + elast[k], (uint32_t)e_wuu[tid + k * kWalkRays],
+                     (uint32_t)ewc[k]);
+    }
     out.rec[rbase + S.cbase[ci[k] * kSlabs + (int)(vid / kSlabVox)] + rank[k]] = r;
   }
   WALK_PROF(6);     // records
@@ -1595,7 +1631,9 @@ __device__ __forceinline__ void walk_fast_tile(
       const size_t d = ((size_t)tile << runs.r1_log2) + mrun[k];
       runs.dkey[d] = vkey[k];
       uint4* dst = reinterpret_cast<uint4*>(runs.masks + d * kMaskWords);
-      const uint32_t word = elast[k] >> 5, bit = 1u << (elast[k] & 31u);
+      // (kGrid: one visit, the ray sum of the count word is the ray)
+      const uint32_t one = kGrid ? plvs::tsdf::visit_ray_sum(elast[k]) : elast[k];
+      const uint32_t word = one >> 5, bit = 1u << (one & 31u);
 #pragma unroll
       for (int q = 0; q < kMaskWords / 4; ++q)
         dst[q] = make_uint4(word == 4u * q ? bit : 0u, word == 4u * q + 1u ? bit : 0u, word == 4u * q + 2u ? bit : 0u,
@@ -1608,31 +1646,28 @@ __device__ __forceinline__ void walk_fast_tile(
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < kPer; ++k) e_midx[tid + k * kWalkRays] = (uint16_t)mrun[k];
+    // The visits behind a full log (FastShared::spill): from the list, one per thread and round — or, where the tile has
+    // more of them than the list holds, from a second walk of its long rays behind
+    // the rounds.  An OR either way: the same masks.
+    constexpr uint32_t kSpillCap = (uint32_t)FastShared<E>::kSpillCap;
+    static_assert(kSpillCap <= (uint32_t)kWalkRays, "a thread per listed visit");
+    const uint32_t nspill = S.nspill;   // (complete since barrier 2)
     for (uint32_t r0 = 0; fits_runs && r0 < nruns; r0 += kMaskCapE) {
       __syncthreads();   // e_midx complete / the previous round's masks are out
-#pragma unroll
-      for (int k = 0; k < kMaskCapE * kMaskWords / kWalkRays; ++k) raw[tid + k * kWalkRays] = 0u;
+      // (the masks of this round's runs and no more: a run has an index below nruns, nothing past them is set or read)
+      const uint32_t nclear = min(nruns - r0, (uint32_t)kMaskCapE) * (uint32_t)kMaskWords;
+#pragma unroll 1
+      for (uint32_t i = (uint32_t)tid; i < nclear; i += (uint32_t)kWalkRays) raw[i] = 0u;
       __syncthreads();
-      if (nv) {
-        const uint32_t logged = min(nv, (uint32_t)kLogLen);
-        for (uint32_t k = 0; k < logged; ++k) {
-          const uint32_t m = (uint32_t)e_midx[vlog[k * kWalkRays + tid]] - r0;   // 0xFFFF - r0 stays out of range
-          if (m < (uint32_t)kMaskCapE) atomicOr(&raw[m * kMaskWords + (rid >> 5)], 1u << (rid & 31));
-        }
-        if (nv > (uint32_t)kLogLen) {   // the log is full: the rest of the ray is walked again
-          const Pose& pose = poses[cloud];
-          Ray ray;
-          if (tile_ray_src(P, xyz, grid, gt, pose, first, rid, &ray, &ctr->err))
-            walk_one(P, pose, ray, 0u, 0xFFFFFFFFu, [&](uint32_t k, int vx, int vy, int vz, float) {
-              if (k >= (uint32_t)kLogLen) {
-                uint32_t key;
-                const int e = rel_key(vx, vy, vz, ox, oy, oz, &key) ? table_find(S, table_key(key)) : -1;
-                const uint32_t m = e >= 0 ? (uint32_t)e_midx[e] - r0 : 0xFFFFFFFFu;
-                if (m < (uint32_t)kMaskCapE) atomicOr(&raw[m * kMaskWords + (rid >> 5)], 1u << (rid & 31));
-              }
-              return true;
-            });
-        }
+      const uint32_t logged = min(nv, (uint32_t)kLogLen);
+      for (uint32_t k = 0; k < logged; ++k) {
+        const uint32_t m = (uint32_t)e_midx[vlog[k * kWalkRays + tid]] - r0;   // 0xFFFF - r0 stays out of range
+        if (m < (uint32_t)kMaskCapE) atomicOr(&raw[m * kMaskWords + (rid >> 5)], 1u << (rid & 31));
+      }
+      if ((uint32_t)tid < nspill && nspill <= kSpillCap) {   // (whose ray it was is in the list's word)
+        const uint32_t w = S.spill[tid], sr = w >> 16;
+        const uint32_t m = (uint32_t)e_midx[w & 0xFFFFu] - r0;
+        if (m < (uint32_t)kMaskCapE) atomicOr(&raw[m * kMaskWords + (sr >> 5)], 1u << (sr & 31));
       }
       __syncthreads();
 #pragma unroll
@@ -1645,6 +1680,34 @@ __device__ __forceinline__ void walk_fast_tile(
         uint4* dst = reinterpret_cast<uint4*>(runs.masks + d * kMaskWords);
 #pragma unroll
         for (int q = 0; q < kMaskWords / 4; ++q) dst[q] = make_uint4(mk[4 * q], mk[4 * q + 1], mk[4 * q + 2], mk[4 * q + 3]);
+      }
+    }
+    if (fits_runs && nspill > kSpillCap) {   // (uniform)
+      // the long rays walk again, once, behind the rounds: their late visits go into the masks where these now are, in
+      // global memory.  Outside the rounds, so that the state of a general walk is not live beside theirs — inside, it put
+      // the lean kernels' flush into scratch.
+      // What orders the plain mask stores of the tile's other threads in front of these atomics: __syncthreads() is a
+      // release fence, the barrier and an acquire fence, all at WORKGROUP scope, and the storing and the OR-ing thread are
+      // of one workgroup — so the stores happen-before the atomics in the HSA / LLVM AMDGPU memory model, whatever scope
+      // the atomics themselves have.  In hardware: the release waits for the stores' acknowledgement from the L2, where the
+      // atomics execute.  In a threadgroup-split build (-mtgsplit: a workgroup's waves on several CUs) the compiler makes
+      // the same workgroup-scope fences write back and invalidate as agent-scope ones do, so the guarantee is the model's,
+      // not the build mode's.  No later reader inside this kernel: the fold reads the masks in a later launch.
+      __syncthreads();
+      if (nv > (uint32_t)kLogLen) {
+        const Pose& pose = poses[cloud];
+        Ray ray;
+        if (tile_ray_src(P, xyz, grid, gt, pose, first, rid, &ray, &ctr->err))
+          walk_one(P, pose, ray, 0u, 0xFFFFFFFFu, [&](uint32_t k, int vx, int vy, int vz, float) {
+            if (k >= (uint32_t)kLogLen) {
+              uint32_t key;
+              const int e = rel_key(vx, vy, vz, ox, oy, oz, &key) ? table_find(S, table_key(key)) : -1;
+              const uint32_t m = e >= 0 ? (uint32_t)e_midx[e] : 0xFFFFu;
+              if (m != 0xFFFFu)
+                atomicOr(&runs.masks[(((size_t)tile << runs.r1_log2) + m) * kMaskWords + (rid >> 5)], 1u << (rid & 31));
+            }
+            return true;
+          });
       }
     }
   }
