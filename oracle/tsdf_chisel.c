@@ -677,6 +677,18 @@ typedef struct {
   int n, cap;
 } mesh_out;
 
+/* What oracle_chisel_mesh_classes counts into its `cls` (tests/mesh_crafted_scenario.py; NULL for every other caller):
+ * [0, 256) cubes per configuration, then */
+enum { MESH_CLS_FLAT = 256,        /* edge vertices of the flat branch, |s0 - s1| < 1e-6 */
+       MESH_CLS_TRILINEAR,         /* vertices coloured from eight voxels */
+       MESH_CLS_FALLBACK,          /* ... by Chunk::GetColorAt */
+       MESH_CLS_COLOR_ZERO,        /* ... left at 0: no chunk at the vertex, or GetColorAt refused */
+       MESH_CLS_GRADIENT,          /* gradient normals written */
+       MESH_CLS_GRADIENT_BETWEEN,  /* gradients refused at a voxel with weight in (1e-15, 1e-12] */
+       MESH_CLS_LINEAR_ID,         /* look-ups whose linear id is in [0, 4096) while a coordinate is not in [0, 16) */
+       MESH_CLS_TRILINEAR_LINEAR_ID,   /* trilinear colourings that blend a voxel such a look-up returned */
+       MESH_CLS_N };
+
 static const chunk_t* mesh_find(const oracle_chisel* o, int x, int y, int z) {
   const int32_t id[3] = {x, y, z};
   int found = 0;
@@ -692,9 +704,10 @@ static void mesh_origin(const oracle_chisel* o, const chunk_t* c, float org[3]) 
 }
 
 /* MarchingCubes::MeshCube(vertexCoords, vertexSDF, const uint32_t& vertexKfid, ...) */
-static void mesh_cube(const float cc[8][3], const float sdf[8], uint32_t kfid, mesh_out* m) {
+static void mesh_cube(const float cc[8][3], const float sdf[8], uint32_t kfid, mesh_out* m, uint32_t* cls) {
   int index = 0;
   for (int i = 0; i < 8; i++) index |= (sdf[i] < 0) ? (1 << i) : 0;
+  if (cls) cls[index]++;
   if (index == 0) return;
   float edge[12][3];
   memset(edge, 0, sizeof edge);
@@ -704,6 +717,7 @@ static void mesh_cube(const float cc[8][3], const float sdf[8], uint32_t kfid, m
       const float minDiff = 1e-6f;
       const float sdfDiff = sdf[e0] - sdf[e1];
       if (fabsf(sdfDiff) < minDiff) {
+        if (cls) cls[MESH_CLS_FLAT]++;
         for (int k = 0; k < 3; k++) edge[i][k] = cc[e0][k] + 0.5f * cc[e1][k];
       } else {
         const float t = sdf[e0] / sdfDiff;
@@ -739,7 +753,7 @@ static void mesh_cube(const float cc[8][3], const float sdf[8], uint32_t kfid, m
 
 /* ExtractInsideVoxelMeshKfid / ExtractBorderVoxelMeshKfid: the border variant with every corner
  * inside the chunk reduces to the inside variant, so one function serves both loops. */
-static void mesh_voxel(const oracle_chisel* o, const chunk_t* ch, int x, int y, int z, mesh_out* m) {
+static void mesh_voxel_cls(const oracle_chisel* o, const chunk_t* ch, int x, int y, int z, mesh_out* m, uint32_t* cls) {
   float org[3];
   mesh_origin(o, ch, org);
   const float res = o->resolution;
@@ -764,10 +778,13 @@ static void mesh_voxel(const oracle_chisel* o, const chunk_t* ch, int x, int y, 
     sdf[i] = src->sdf[id];
     if (i == 0) kfid = src->kfid[id];
   }
-  mesh_cube(cc, sdf, kfid, m);
+  mesh_cube(cc, sdf, kfid, m, cls);
+}
+static void mesh_voxel(const oracle_chisel* o, const chunk_t* ch, int x, int y, int z, mesh_out* m) {
+  mesh_voxel_cls(o, ch, x, y, z, m, NULL);
 }
 
-static const uint32_t* mesh_color_voxel(const oracle_chisel* o, float px, float py, float pz) {   /* GetColorVoxel, :818 */
+static const uint32_t* mesh_color_voxel(const oracle_chisel* o, float px, float py, float pz, uint32_t* cls) {   /* GetColorVoxel, :818 */
   const float pos[3] = {px, py, pz};
   const chunk_t* c = mesh_chunk_at(o, pos);
   if (!c) return NULL;
@@ -777,24 +794,27 @@ static const uint32_t* mesh_color_voxel(const oracle_chisel* o, float px, float 
   const int vx = (int)floorf((pos[0] - org[0]) * inv), vy = (int)floorf((pos[1] - org[1]) * inv),
             vz = (int)floorf((pos[2] - org[2]) * inv);
   const int id = (vz * 16 + vy) * 16 + vx;
+  if (cls && id >= 0 && id < CHUNK_VOX && ((vx | vy | vz) & ~15)) cls[MESH_CLS_LINEAR_ID]++;
   return (id >= 0 && id < CHUNK_VOX) ? &c->rgbw[id] : NULL;
 }
 
-static void mesh_interpolate_color(const oracle_chisel* o, const float p[3], float out[3]) {   /* :718-805 */
+static void mesh_interpolate_color_cls(const oracle_chisel* o, const float p[3], float out[3], uint32_t* cls) {   /* :718-805 */
   const float inv = 1.f / o->resolution;                          /* ChunkManager.cpp:67 */
   const float x = p[0], y = p[1], z = p[2];
   const int x_0 = (int)floorf(x * inv), y_0 = (int)floorf(y * inv), z_0 = (int)floorf(z * inv);
   const int x_1 = x_0 + 1, y_1 = y_0 + 1, z_1 = z_0 + 1;
-  const uint32_t* v_000 = mesh_color_voxel(o, (float)x_0, (float)y_0, (float)z_0);
-  const uint32_t* v_001 = mesh_color_voxel(o, (float)x_0, (float)y_0, (float)z_1);
-  const uint32_t* v_011 = mesh_color_voxel(o, (float)x_0, (float)y_1, (float)z_1);
-  const uint32_t* v_111 = mesh_color_voxel(o, (float)x_1, (float)y_1, (float)z_1);
-  const uint32_t* v_110 = mesh_color_voxel(o, (float)x_1, (float)y_1, (float)z_0);
-  const uint32_t* v_100 = mesh_color_voxel(o, (float)x_1, (float)y_0, (float)z_0);
-  const uint32_t* v_010 = mesh_color_voxel(o, (float)x_0, (float)y_1, (float)z_0);
-  const uint32_t* v_101 = mesh_color_voxel(o, (float)x_1, (float)y_0, (float)z_1);
+  const uint32_t quirks_before = cls ? cls[MESH_CLS_LINEAR_ID] : 0;
+  const uint32_t* v_000 = mesh_color_voxel(o, (float)x_0, (float)y_0, (float)z_0, cls);
+  const uint32_t* v_001 = mesh_color_voxel(o, (float)x_0, (float)y_0, (float)z_1, cls);
+  const uint32_t* v_011 = mesh_color_voxel(o, (float)x_0, (float)y_1, (float)z_1, cls);
+  const uint32_t* v_111 = mesh_color_voxel(o, (float)x_1, (float)y_1, (float)z_1, cls);
+  const uint32_t* v_110 = mesh_color_voxel(o, (float)x_1, (float)y_1, (float)z_0, cls);
+  const uint32_t* v_100 = mesh_color_voxel(o, (float)x_1, (float)y_0, (float)z_0, cls);
+  const uint32_t* v_010 = mesh_color_voxel(o, (float)x_0, (float)y_1, (float)z_0, cls);
+  const uint32_t* v_101 = mesh_color_voxel(o, (float)x_1, (float)y_0, (float)z_1, cls);
   if (!v_000 || !v_001 || !v_011 || !v_111 || !v_110 || !v_100 || !v_010 || !v_101) {
     out[0] = out[1] = out[2] = 0.0f;
+    if (cls) cls[MESH_CLS_COLOR_ZERO]++;                           /* (moved to FALLBACK below once a voxel answers) */
     const chunk_t* c = mesh_chunk_at(o, p);
     if (!c) return;
     float org[3];
@@ -806,12 +826,15 @@ static void mesh_interpolate_color(const oracle_chisel* o, const float p[3], flo
     const int cx = (int)((p[0] - org[0]) * cinv), cy = (int)((p[1] - org[1]) * cinv), cz = (int)((p[2] - org[2]) * cinv);
     if (cx < 0 || cx >= 16 || cy < 0 || cy >= 16 || cz < 0 || cz >= 16) return;
     const uint32_t col = c->rgbw[(cz * 16 + cy) * 16 + cx];
+    if (cls) { cls[MESH_CLS_COLOR_ZERO]--; cls[MESH_CLS_FALLBACK]++; }
     const float invMaxVal = 1.f / 255.0f;
     out[0] = (float)(col & 255u) * invMaxVal;
     out[1] = (float)((col >> 8) & 255u) * invMaxVal;
     out[2] = (float)((col >> 16) & 255u) * invMaxVal;
     return;
   }
+  if (cls) cls[MESH_CLS_TRILINEAR]++;
+  if (cls && cls[MESH_CLS_LINEAR_ID] != quirks_before) cls[MESH_CLS_TRILINEAR_LINEAR_ID]++;
   const float xd = (x - (float)x_0) / (float)(x_1 - x_0);
   const float yd = (y - (float)y_0) / (float)(y_1 - y_0);
   const float zd = (z - (float)z_0) / (float)(z_1 - z_0);
@@ -829,8 +852,11 @@ static void mesh_interpolate_color(const oracle_chisel* o, const float p[3], flo
     out[ch] = c / 255.0f;
   }
 }
+static void mesh_interpolate_color(const oracle_chisel* o, const float p[3], float out[3]) {
+  mesh_interpolate_color_cls(o, p, out, NULL);
+}
 
-static int mesh_get_sdf(const oracle_chisel* o, const float posf[3], double* dist) {   /* GetSDF, :692-716 */
+static int mesh_get_sdf(const oracle_chisel* o, const float posf[3], double* dist, uint32_t* cls) {   /* GetSDF, :692-716 */
   const chunk_t* c = mesh_chunk_at(o, posf);
   if (!c) return 0;
   float org[3];
@@ -839,6 +865,10 @@ static int mesh_get_sdf(const oracle_chisel* o, const float posf[3], double* dis
   const int vx = (int)floorf((posf[0] - org[0]) * inv), vy = (int)floorf((posf[1] - org[1]) * inv),
             vz = (int)floorf((posf[2] - org[2]) * inv);
   const int id = (vz * 16 + vy) * 16 + vx;
+  if (cls && id >= 0 && id < CHUNK_VOX) {
+    if ((vx | vy | vz) & ~15) cls[MESH_CLS_LINEAR_ID]++;
+    if (!(c->weight[id] > 1e-12) && !(c->weight[id] <= 1e-15)) cls[MESH_CLS_GRADIENT_BETWEEN]++;   /* the caller returns */
+  }
   if (id >= 0 && id < CHUNK_VOX && c->weight[id] > 1e-12) {
     *dist = c->sdf[id];
     return 1;
@@ -846,21 +876,21 @@ static int mesh_get_sdf(const oracle_chisel* o, const float posf[3], double* dis
   return 0;
 }
 
-static void mesh_gradient_normal(const oracle_chisel* o, const float pos[3], float* normal) {   /* :840-858 */
+static void mesh_gradient_normal_cls(const oracle_chisel* o, const float pos[3], float* normal, uint32_t* cls) {   /* :840-858 */
   const float res = o->resolution, inv = 1.f / res, half = 0.5f * res;   /* ChunkManager.cpp:67, :89 */
   const float posf[3] = {floorf(pos[0] * inv) * res + half, floorf(pos[1] * inv) * res + half,
                          floorf(pos[2] * inv) * res + half};
   double dist, dp[3], dm[3];
-  if (!mesh_get_sdf(o, posf, &dist)) return;
+  if (!mesh_get_sdf(o, posf, &dist, cls)) return;
   for (int k = 0; k < 3; k++) {                                    /* +x, +y, +z */
     float q[3] = {posf[0], posf[1], posf[2]};
     q[k] = posf[k] + res;
-    if (!mesh_get_sdf(o, q, &dp[k])) return;
+    if (!mesh_get_sdf(o, q, &dp[k], cls)) return;
   }
   for (int k = 0; k < 3; k++) {                                    /* -x, -y, -z */
     float q[3] = {posf[0], posf[1], posf[2]};
     q[k] = posf[k] - res;
-    if (!mesh_get_sdf(o, q, &dm[k])) return;
+    if (!mesh_get_sdf(o, q, &dm[k], cls)) return;
   }
   float g[3] = {(float)(dp[0] - dm[0]), (float)(dp[1] - dm[1]), (float)(dp[2] - dm[2])};
   const float z = sqnorm3(g);
@@ -869,7 +899,11 @@ static void mesh_gradient_normal(const oracle_chisel* o, const float pos[3], flo
   if (mag > 1e-12) {
     const float r = 1.0f / mag;
     normal[0] = g[0] * r; normal[1] = g[1] * r; normal[2] = g[2] * r;
+    if (cls) cls[MESH_CLS_GRADIENT]++;
   }
+}
+static void mesh_gradient_normal(const oracle_chisel* o, const float pos[3], float* normal) {
+  mesh_gradient_normal_cls(o, pos, normal, NULL);
 }
 
 /* Returns the number of vertices of chunk (cx, cy, cz) (0 if the chunk does not exist), writing up to
@@ -891,6 +925,33 @@ int oracle_chisel_mesh_chunk(const oracle_chisel* o, int cx, int cy, int cz, flo
   const int n = m.n < cap ? m.n : cap;
   for (int i = 0; i < n; i++) mesh_interpolate_color(o, vertices + 3 * (size_t)i, colors + 3 * (size_t)i);   /* :158-161 */
   for (int i = 0; i < n; i++) mesh_gradient_normal(o, vertices + 3 * (size_t)i, normals + 3 * (size_t)i);    /* :163 */
+  return m.n;
+}
+
+/* Test hook: the same walk as oracle_chisel_mesh_chunk, counting into out[MESH_CLS_N = 264] (zeroed here) which
+ * branches the chunk's mesh takes — see the enum above.  Returns the number of vertices. */
+int oracle_chisel_mesh_classes(const oracle_chisel* o, int cx, int cy, int cz, uint32_t* out) {
+  memset(out, 0, MESH_CLS_N * sizeof(uint32_t));
+  const chunk_t* ch = mesh_find(o, cx, cy, cz);
+  if (!ch) return 0;
+  const int cap = CHUNK_VOX * 15;
+  float* buf = (float*)malloc((size_t)cap * 9 * sizeof(float));
+  uint32_t* kfids = (uint32_t*)malloc((size_t)cap * sizeof(uint32_t));
+  float *vertices = buf, *normals = buf + 3 * (size_t)cap, *colors = buf + 6 * (size_t)cap;
+  mesh_out m = {vertices, normals, kfids, 0, cap};
+  for (int z = 0; z < 15; z++)
+    for (int y = 0; y < 15; y++)
+      for (int x = 0; x < 15; x++) mesh_voxel_cls(o, ch, x, y, z, &m, out);
+  for (int z = 0; z < 15; z++)
+    for (int y = 0; y < 16; y++) mesh_voxel_cls(o, ch, 15, y, z, &m, out);
+  for (int z = 0; z < 15; z++)
+    for (int x = 0; x < 15; x++) mesh_voxel_cls(o, ch, x, 15, z, &m, out);
+  for (int y = 0; y < 16; y++)
+    for (int x = 0; x < 16; x++) mesh_voxel_cls(o, ch, x, y, 15, &m, out);
+  for (int i = 0; i < m.n; i++) mesh_interpolate_color_cls(o, vertices + 3 * (size_t)i, colors + 3 * (size_t)i, out);
+  for (int i = 0; i < m.n; i++) mesh_gradient_normal_cls(o, vertices + 3 * (size_t)i, normals + 3 * (size_t)i, out);
+  free(buf);
+  free(kfids);
   return m.n;
 }
 

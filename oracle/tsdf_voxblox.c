@@ -940,9 +940,18 @@ typedef struct {
   int n, cap;
 } vb_mesh_out;
 
-static void vb_mesh_cube(const float cc[8][3], const float sdf[8], vb_mesh_out* m) {
+/* What oracle_voxblox_mesh_classes counts into its `cls` (tests/mesh_crafted_scenario.py; NULL for every other caller):
+ * [0, 256) cubes per configuration, then */
+enum { VB_CLS_FLAT = 256,          /* edge vertices of the flat branch, |s0 - s1| < 1e-6 */
+       VB_CLS_CLAMP_LOW,           /* colour look-ups with a voxel index clamped up to 0 */
+       VB_CLS_CLAMP_HIGH,          /* ... clamped down to 15 */
+       VB_CLS_UNOBSERVED,          /* colours refused: the nearest voxel's weight <= min_weight */
+       VB_CLS_N };
+
+static void vb_mesh_cube_cls(const float cc[8][3], const float sdf[8], vb_mesh_out* m, uint32_t* cls) {
   int index = 0;
   for (int i = 0; i < 8; i++) index |= (sdf[i] < 0) ? (1 << i) : 0;
+  if (cls) cls[index]++;
   if (index == 0) return;
   float edge[12][3];
   memset(edge, 0, sizeof edge);
@@ -954,6 +963,7 @@ static void vb_mesh_cube(const float cc[8][3], const float sdf[8], vb_mesh_out* 
         const float t = sdf[e0] / diff;
         for (int k = 0; k < 3; k++) edge[i][k] = cc[e0][k] + t * (cc[e1][k] - cc[e0][k]);
       } else {
+        if (cls) cls[VB_CLS_FLAT]++;
         for (int k = 0; k < 3; k++) edge[i][k] = 0.5f * (cc[e0][k] + cc[e1][k]);
       }
     }
@@ -978,6 +988,7 @@ static void vb_mesh_cube(const float cc[8][3], const float sdf[8], vb_mesh_out* 
     m->n += 3;
   }
 }
+static void vb_mesh_cube(const float cc[8][3], const float sdf[8], vb_mesh_out* m) { vb_mesh_cube_cls(cc, sdf, m, NULL); }
 
 static const vblock_t* vb_mesh_find(const oracle_voxblox* o, int x, int y, int z) {
   const int32_t id[3] = {x, y, z};
@@ -991,7 +1002,7 @@ static void vb_block_origin(const oracle_voxblox* o, const vblock_t* b, float or
   for (int k = 0; k < 3; k++) org[k] = (float)b->id[k] * block_size;
 }
 
-static void vb_mesh_voxel(const oracle_voxblox* o, const vblock_t* blk, int x, int y, int z, vb_mesh_out* m) {
+static void vb_mesh_voxel_cls(const oracle_voxblox* o, const vblock_t* blk, int x, int y, int z, vb_mesh_out* m, uint32_t* cls) {
   float org[3], coords[3];
   vb_block_origin(o, blk, org);
   const int v[3] = {x, y, z};
@@ -1012,7 +1023,10 @@ static void vb_mesh_voxel(const oracle_voxblox* o, const vblock_t* blk, int x, i
     sdf[i] = src->distance[id];
     for (int k = 0; k < 3; k++) cc[i][k] = coords[k] + (float)kVbCubeIndexOffsets[k][i] * o->voxel_size;
   }
-  vb_mesh_cube(cc, sdf, m);
+  vb_mesh_cube_cls(cc, sdf, m, cls);
+}
+static void vb_mesh_voxel(const oracle_voxblox* o, const vblock_t* blk, int x, int y, int z, vb_mesh_out* m) {
+  vb_mesh_voxel_cls(o, blk, x, y, z, m, NULL);
 }
 
 /* voxblox::Mesh of block (bx, by, bz) after updateMeshForBlock: vertices / normals n x 3 f32, colors n x 4 u8
@@ -1045,6 +1059,40 @@ int oracle_voxblox_mesh_block(const oracle_voxblox* o, int bx, int by, int bz, f
     if (!(blk->weight[id] <= VB_MESH_MIN_WEIGHT)) c = blk->rgba[id];
     for (int k = 0; k < 4; k++) colors[4 * (size_t)i + k] = (uint8_t)(c >> (8 * k));
   }
+  return m.n;
+}
+
+/* Test hook: the same walk as oracle_voxblox_mesh_block, counting into out[VB_CLS_N = 260] (zeroed here) which
+ * branches the block's mesh takes — see the enum above.  Returns the number of vertices. */
+int oracle_voxblox_mesh_classes(const oracle_voxblox* o, int bx, int by, int bz, uint32_t* out) {
+  memset(out, 0, VB_CLS_N * sizeof(uint32_t));
+  const vblock_t* blk = vb_mesh_find(o, bx, by, bz);
+  if (!blk) return 0;
+  const int cap = BLOCK_VOX * 15;
+  float* vertices = (float*)malloc((size_t)cap * 6 * sizeof(float));
+  vb_mesh_out m = {vertices, vertices + 3 * (size_t)cap, 0, cap};
+  for (int x = 0; x < VPS - 1; x++)
+    for (int y = 0; y < VPS - 1; y++)
+      for (int z = 0; z < VPS - 1; z++) vb_mesh_voxel_cls(o, blk, x, y, z, &m, out);
+  for (int z = 0; z < VPS; z++)
+    for (int y = 0; y < VPS; y++) vb_mesh_voxel_cls(o, blk, VPS - 1, y, z, &m, out);
+  for (int z = 0; z < VPS; z++)
+    for (int x = 0; x < VPS - 1; x++) vb_mesh_voxel_cls(o, blk, x, VPS - 1, z, &m, out);
+  for (int y = 0; y < VPS - 1; y++)
+    for (int x = 0; x < VPS - 1; x++) vb_mesh_voxel_cls(o, blk, x, y, VPS - 1, &m, out);
+  float org[3];
+  vb_block_origin(o, blk, org);
+  for (int i = 0; i < m.n; i++) {                                 /* updateMeshColor, as oracle_voxblox_mesh_block */
+    int idx[3];
+    for (int k = 0; k < 3; k++) {
+      int g = (int)floorf((vertices[3 * (size_t)i + k] - org[k]) * o->voxel_size_inv + 1e-6f);
+      if (g < 0) out[VB_CLS_CLAMP_LOW]++;
+      if (g > VPS - 1) out[VB_CLS_CLAMP_HIGH]++;
+      idx[k] = g < 0 ? 0 : (g > VPS - 1 ? VPS - 1 : g);
+    }
+    if (blk->weight[idx[0] + VPS * (idx[1] + idx[2] * VPS)] <= VB_MESH_MIN_WEIGHT) out[VB_CLS_UNOBSERVED]++;
+  }
+  free(vertices);
   return m.n;
 }
 

@@ -587,6 +587,53 @@ def test_voxblox_mesh_integrator_equals_the_reference_source():
     assert total > 15000
 
 
+def _crafted_voxblox_names():
+    from tests import mesh_crafted_scenario as S
+    return S.VOXBLOX_NAMES
+
+
+VREF_SET_BLOCK = os.path.join(ROOT, "oracle", "_ref", "libvoxblox_set_block_ref.so")
+
+
+@needs_vref
+@pytest.mark.skipif(not os.path.exists(VREF_SET_BLOCK), reason="oracle/_ref/libvoxblox_set_block_ref.so not present")
+@pytest.mark.parametrize("name", _crafted_voxblox_names())
+def test_voxblox_meshes_of_crafted_blocks_equal_the_reference_source(name):
+    """The voxblox cases of tests/mesh_crafted_scenario.py (all 254 cube configurations, flat edges, weights at 1e-4 and
+    one ulp above, blocks far out): the blocks are written through the reference's Layer / Block / TsdfVoxel
+    (ref_voxblox_set_block) and read back, then MeshIntegrator::updateMeshForBlock of every id of the case's lists is
+    the oracle's mesh byte for byte."""
+    from tests import mesh_crafted_scenario as S
+    from tests import oracle_lib
+    ref = ctypes.CDLL(VREF)
+    setter = ctypes.CDLL(VREF_SET_BLOCK)                        # (a library of its own beside VREF, linked against it)
+    setter.ref_voxblox_set_block.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3
+    ref.ref_voxblox_get_block.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3
+    ref.ref_voxblox_mesh_block.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_int]
+    ref.ref_voxblox_destroy.argtypes = [ctypes.c_void_p]
+    c = S.case(name)
+    ora = S.oracle_map(oracle_lib.load(), c)
+    h = _ref_map(ref, c["res"], False, "simple")
+    for cid, *planes in c["uploads"]:
+        setter.ref_voxblox_set_block(h, *map(int, cid), *[np.ascontiguousarray(p).ctypes.data for p in planes])
+        back = np.zeros(4096, np.float32), np.zeros(4096, np.float32), np.zeros(4096, np.uint32)
+        assert ref.ref_voxblox_get_block(h, *map(int, cid), *[b.ctypes.data for b in back]) == 1
+        for p, b in zip(planes, back):
+            assert p.tobytes() == b.tobytes(), cid
+    cap = 4096 * 15
+    v, n = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.float32)
+    col = np.zeros((cap, 4), np.uint8)
+    total = 0
+    for cid in sorted({tuple(int(x) for x in b) for l in c["lists"] for b in l}):
+        nv = ref.ref_voxblox_mesh_block(h, *cid, v.ctypes.data, n.ctypes.data, col.ctypes.data, cap)
+        ov, on, oc = S.oracle_mesh(ora, "voxblox", cid)
+        assert nv == len(ov), (cid, nv, len(ov))
+        assert v[:nv].tobytes() == ov.tobytes() and n[:nv].tobytes() == on.tobytes() and col[:nv].tobytes() == oc.tobytes(), cid
+        total += nv
+    ref.ref_voxblox_destroy(h)
+    assert total > 20000
+
+
 # ------------------------------------------------------------------ LBD matcher (multi-index hashing k-NN)
 LREF = os.path.join(ROOT, "oracle", "_ref", "liblbd_matcher_ref.so")
 needs_lref = pytest.mark.skipif(not os.path.exists(LREF), reason="oracle/_ref/liblbd_matcher_ref.so not present")

@@ -19,6 +19,7 @@ from tests.test_tsdf_loadmap import surface_cloud
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libchisel_full_ref.so")
 REF_SET_CHUNK = os.path.join(ROOT, "oracle", "_ref", "libchisel_set_chunk_ref.so")
+REF_MESH_IDS = os.path.join(ROOT, "oracle", "_ref", "libchisel_mesh_ids_ref.so")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(REF),
                                 reason="oracle/_ref/libchisel_full_ref.so (built where /root/reference exists) not present")
@@ -108,6 +109,13 @@ class RefChisel:
 
     def update_meshes(self):
         self.lib.ref_chisel_full_update_meshes(self.h)
+
+    def recompute_meshes(self, ids):
+        """ChunkManager::RecomputeMeshes of these ids: what update_meshes does with the set only an integrate fills."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1, 3)
+        lib = ctypes.CDLL(REF_MESH_IDS)                          # (a library of its own beside REF, linked against it)
+        lib.ref_chisel_recompute_meshes.argtypes = [_vp, _vp, _i]
+        lib.ref_chisel_recompute_meshes(self.h, _ptr(ids), len(ids))
 
     def mesh_chunk(self, cx, cy, cz):
         cap = 4096 * 15
@@ -319,6 +327,37 @@ def test_deform_of_crafted_chunks_equals_the_reference_library(oracle, name):
             continue
         same()
     assert deforms > 0
+    ref.close()
+
+
+def _crafted_mesh_names():
+    from tests import mesh_crafted_scenario as S
+    return S.CHISEL_NAMES
+
+
+@pytest.mark.skipif(not (os.path.exists(REF_SET_CHUNK) and os.path.exists(REF_MESH_IDS)),
+                    reason="oracle/_ref/libchisel_set_chunk_ref.so / libchisel_mesh_ids_ref.so (built where /root/reference exists) not present")
+@pytest.mark.parametrize("name", _crafted_mesh_names())
+def test_meshes_of_crafted_chunks_equal_the_reference_library(oracle, name):
+    """The chisel cases of tests/mesh_crafted_scenario.py (all 254 cube configurations, flat edges, the eight-voxel colour
+    blend, weights between 1e-15 and 1e-12, ids far out and next to 2^20): chunks go in through the voxels' setters,
+    RecomputeMeshes gets the ids of the case's lists (update_meshes would mesh nothing: no integrate marked a chunk),
+    and every chunk's mesh — vertices, normals, colours, kfids — is the oracle's byte for byte."""
+    from tests import mesh_crafted_scenario as S
+    c = S.case(name)
+    ref, ora = RefChisel(c["res"], small_cam(8)), S.oracle_map(oracle, c)
+    for cid, *planes in c["uploads"]:
+        ref.set_chunk(*cid, *planes)
+    ids = sorted({tuple(int(v) for v in x) for l in c["lists"] for x in l})
+    ref.recompute_meshes(np.array(ids, np.int32))
+    total = 0
+    for cid in ids:
+        got, want = ora.mesh_chunk(*cid), ref.mesh_chunk(*cid)
+        for what, a, b in zip(("vertices", "normals", "colours", "kfids"), got, want):
+            assert a.shape == b.shape, f"{what} count differs in chunk {cid}: {a.shape} vs {b.shape}"
+            assert a.tobytes() == b.tobytes(), f"{what} differ in chunk {cid}"
+        total += len(want[0])
+    assert total > 20000
     ref.close()
 
 

@@ -187,7 +187,8 @@ def test_hip_mesh_of_an_analytic_sphere_through_upload_chunk(oracle):
                 sdf = np.transpose(np.linalg.norm(pts - centre, axis=-1) - r, (2, 1, 0)).astype(np.float32).reshape(-1)
                 sdf[rng.integers(0, 4096, 40)] = 0.0
                 flat = rng.integers(0, 4095, 30)                                 # neighbours closer than 1e-6: the flat-edge vertex
-                sdf[flat + 1] = -sdf[flat] + np.float32(3e-7) * np.sign(sdf[flat])
+                a = rng.uniform(1e-8, 4.9e-7, 30).astype(np.float32) * np.where(sdf[flat] < 0, -1, 1).astype(np.float32)
+                sdf[flat], sdf[flat + 1] = a, -a                                 # (|s0 - s1| = 2 a < 1e-6, signs differ)
                 w = np.ones(4096, np.float32)
                 w[rng.integers(0, 4096, 60)] = 0.0
                 kfid = rng.integers(0, 1000, 4096).astype(np.uint32)
@@ -200,6 +201,9 @@ def test_hip_mesh_of_an_analytic_sphere_through_upload_chunk(oracle):
         for x, y in zip(ref.get_chunk(*cid), hip.get_chunk(*cid)):
             assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x, y.view(np.uint32) if y.dtype == np.float32 else y)
     todo = _neighbourhood(ids)
+    from tests import mesh_crafted_scenario as S
+    flat_edges = sum(int(S.classes(ref, "chisel", cid)[1][256 + S.CHISEL_CLASSES.index("flat")]) for cid in ids)
+    assert flat_edges > 0                                                        # the mesh holds flat-edge vertices
     m = hip.mesh_chunks(np.array(todo, np.int32))
     first, total = m["chunk_first"], 0
     for i, cid in enumerate(todo):
