@@ -1991,6 +1991,66 @@ int plvs_hip_line_loop_search_by_projection_kf_host(const plvs_keyframe* const* 
                                                     float ratio_hamming, int32_t* match_idx, int32_t* match_dist, uint8_t* reached,
                                                     int32_t* nmatches, int32_t* stats);
 
+/* ----------------------------------------------------------- SearchByBoW over resident key frames
+ * The first stage of loop detection and of relocalisation:
+ *   int ORBmatcher::SearchByBoW(KeyFramePtr& pKF1, KeyFramePtr& pKF2, vector<MapPointPtr>& vpMatches12)   src/ORBmatcher.cc:853-997
+ *       as LoopClosing::DetectCommonRegionsFromBoW calls it once per covisible of a candidate (src/LoopClosing.cc:769-780);
+ *   int ORBmatcher::SearchByBoW(KeyFramePtr& pKF, Frame& F, vector<MapPointPtr>& vpMapPointMatches)       :300-507
+ *       as Tracking::Relocalization calls it once per candidate (src/Tracking.cc:4907-4930) and TrackReferenceKeyFrame once (:3308);
+ * single-camera frames (NLeft == -1).  Both are greedy, but node-local: DBoW2::FeatureVector::addFeature puts a feature under ONE
+ * node, so a claim (vbMatched2[idx2], vpMapPointMatches[realIdxF]) only reaches later features of the same node, and every
+ * (pair, common node) is an independent sequential problem.  The device runs the whole greedy pass, one wave per (pair, node);
+ * the rotation histogram and ComputeThreeMaxima run on the host after the wait.  Every output equals the reference's.
+ *
+ * A handle gets its BoW side — what KeyFrame::ComputeBoW fixes (src/KeyFrame.cc:235) — at creation: bow == NULL is
+ * plvs_hip_keyframe_create; bow needs the point side.  Deep-copied into the handle's block (host copy and the one device
+ * allocation).  Refused before any HIP call or allocation: node ids not strictly ascending, offsets not monotone (or negative), a
+ * feature index >= n, a feature index listed more than once anywhere in the vector (DBoW2 guarantees it, the device's greedy pass
+ * rests on it), a NULL angle. */
+typedef struct plvs_keyframe_bow {
+  plvs_featvec_view vec;   /* pKF->mFeatVec, in-order traversal as plvs_featvec_view defines it   */
+  const float* angle;      /* pKF->mvKeysUn[i].angle, degrees, n entries                          */
+} plvs_keyframe_bow;
+int plvs_hip_keyframe_create_bow(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, const plvs_keyframe_bow* bow,
+                                 uint32_t flags, plvs_keyframe** out);
+/* info (4): nodes (-1: no BoW side), listed features, the longest node list, bytes the side adds to the device allocation */
+int plvs_hip_keyframe_bow_info(const plvs_keyframe* kf, int64_t* info);
+/* SearchByBoW(pKF1, pKF2[k], vpMatches12[k]) for k < n_kfs2 in one call.  valid1[i] (n1 bytes), valid2[k][j] (n_k bytes):
+ * vpMapPoints[i] && !isBad() at the time of the call.  nn_ratio = mfNNratio, check_orientation = mbCheckOrientation.
+ * match_idx[k * n1 + i1]: the key point of kfs2[k] whose map point vpMatches12[i1] holds on return (after the rotation check), else
+ * -1; match_dist: that match's distance, else -1; nmatches[k] (may be NULL): the return value.
+ * stats (6, may be NULL): [0] launches, [1] device waits, [2] bytes of the copy in, [3] (pair, node) jobs with a common node,
+ * [4] jobs whose claimed-side list needed more than one pass of 64 lanes, [5] jobs the device handed to the host's code (always 0:
+ * the kernel loops in passes of 64 and has no length limit).
+ * Refused before anything is launched or written: a NULL handle, a handle without a BoW side, a PLVS_KEYFRAME_HOST_ONLY handle in a
+ * device entry (all before any HIP call), a handle of another device than the current one; nn_ratio negative or NaN; NULL
+ * outputs or validity arrays.  n_kfs2 == 0, no common node, or nothing valid: no launch, the outputs say "no match".
+ * stream: NULL — the calling thread's own; the call waits on it either way. */
+int plvs_hip_orb_search_by_bow_kf(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs2,
+                                  const uint8_t* const* valid2, int n_kfs2, float nn_ratio, int check_orientation, int32_t* match_idx,
+                                  int32_t* match_dist, int32_t* nmatches, int32_t* stats, void* stream);
+/* SearchByBoW(pKF[k], F, vvpMapPointMatches[k]) for k < n_kfs in one call.  F->angle = F.mvKeys[i].angle; F->vec gets the checks of
+ * a handle's vector, uniqueness included (a vector that fails them is refused; plvs_hip_orb_search_by_bow still serves it).
+ * assigned[k * F->n + iF]: the key point of kfs[k] whose map point goes to frame key point iF, else -1 (the meaning of
+ * plvs_hip_orb_search_by_bow's); match_dist, nmatches, stats, the refusals and stream as above. */
+typedef struct plvs_bow_frame {
+  int32_t n;             /* F.N, < 2^23                */
+  const uint8_t* desc;   /* F.mDescriptors, n x 32     */
+  const float* angle;    /* F.mvKeys[i].angle, degrees */
+  plvs_featvec_view vec; /* F.mFeatVec                 */
+} plvs_bow_frame;
+int plvs_hip_orb_search_by_bow_frame_kf(const plvs_keyframe* const* kfs, const uint8_t* const* kf_valid, int n_kfs, const plvs_bow_frame* F,
+                                        float nn_ratio, int check_orientation, int32_t* assigned, int32_t* match_dist, int32_t* nmatches,
+                                        int32_t* stats, void* stream);
+/* The same per-job code, serially, on the handles' host copies with no HIP call (PLVS_KEYFRAME_HOST_ONLY handles and others
+ * alike).  stats[0] = stats[1] = stats[2] = stats[5] = 0. */
+int plvs_hip_orb_search_by_bow_kf_host(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs2,
+                                       const uint8_t* const* valid2, int n_kfs2, float nn_ratio, int check_orientation, int32_t* match_idx,
+                                       int32_t* match_dist, int32_t* nmatches, int32_t* stats);
+int plvs_hip_orb_search_by_bow_frame_kf_host(const plvs_keyframe* const* kfs, const uint8_t* const* kf_valid, int n_kfs,
+                                             const plvs_bow_frame* F, float nn_ratio, int check_orientation, int32_t* assigned,
+                                             int32_t* match_dist, int32_t* nmatches, int32_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 // Errors of the library surface as std::runtime_error carrying plvs_hip_last_error(); there is no
 // CPU fallback anywhere.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -429,6 +430,10 @@ class KeyFrameHandle {
   KeyFrameHandle(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, bool hostOnly = false) {
     check(plvs_hip_keyframe_create(points, lines, hostOnly ? PLVS_KEYFRAME_HOST_ONLY : 0u, &h_));
   }
+  // with the BoW side (what KeyFrame::ComputeBoW fixes; BowSearch below flattens a DBoW2::FeatureVector into `bow`)
+  KeyFrameHandle(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, const plvs_keyframe_bow* bow, bool hostOnly = false) {
+    check(plvs_hip_keyframe_create_bow(points, lines, bow, hostOnly ? PLVS_KEYFRAME_HOST_ONLY : 0u, &h_));
+  }
   ~KeyFrameHandle() { reset(); }
   KeyFrameHandle(KeyFrameHandle&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
   KeyFrameHandle& operator=(KeyFrameHandle&& o) noexcept {
@@ -449,6 +454,13 @@ class KeyFrameHandle {
     int64_t v[6];
     check(plvs_hip_keyframe_info(h_, v));
     return Info{v[0], v[1], v[2], v[3], v[4], v[5]};
+  }
+  // vocabulary nodes (-1: no BoW side), listed features, the longest node list, bytes the side adds to the device allocation
+  struct BowInfo { int64_t nodes, listed, longest, deviceBytes; };
+  BowInfo bowInfo() const {
+    int64_t v[4];
+    check(plvs_hip_keyframe_bow_info(h_, v));
+    return BowInfo{v[0], v[1], v[2], v[3]};
   }
 
  private:
@@ -700,6 +712,97 @@ inline int LoopSearchByProjectionPointsAndLines(const std::vector<const KeyFrame
       stream));
   return points.finish(pp, keyFrames.size()) + lines.finish(lp, keyFrames.size());
 }
+
+// ORBmatcher::SearchByBoW over resident key frames (plvs_hip.h has the semantics): SearchByBoW(pKF1, pKF2[k], vpMatches12[k]) for
+// every covisible of a loop candidate, and SearchByBoW(pKF[k], F, vvpMapPointMatches[k]) for every relocalisation candidate, each in
+// one call.  A DBoW2::FeatureVector IS a std::map<NodeId, std::vector<unsigned int>>: the mirror flattens its in-order traversal.
+struct FlatFeatureVector {
+  std::vector<uint32_t> nodeId;
+  std::vector<int32_t> offset;
+  std::vector<uint32_t> index;
+  FlatFeatureVector() : offset(1, 0) {}
+  explicit FlatFeatureVector(const std::map<unsigned int, std::vector<unsigned int>>& featVec) : offset(1, 0) {
+    for (const auto& node : featVec) {
+      nodeId.push_back(node.first);
+      index.insert(index.end(), node.second.begin(), node.second.end());
+      offset.push_back((int32_t)index.size());
+    }
+  }
+  plvs_featvec_view view() const { return plvs_featvec_view{(int32_t)nodeId.size(), nodeId.data(), offset.data(), index.data()}; }
+};
+class BowSearch {
+ public:
+  BowSearch(float nnratio = 0.6f, bool checkOri = true) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}   // ORBmatcher's constructor
+  // the handle of a key frame with its BoW side: mFeatVec and mvKeysUn[i].angle (degrees)
+  static KeyFrameHandle MakeKeyFrame(const plvs_fuse_keyframe& points, const plvs_line_fuse_keyframe* lines,
+                                     const std::map<unsigned int, std::vector<unsigned int>>& mFeatVec, const std::vector<float>& angles,
+                                     bool hostOnly = false) {
+    const FlatFeatureVector flat(mFeatVec);
+    const plvs_keyframe_bow bow{flat.view(), angles.data()};
+    return KeyFrameHandle(&points, lines, &bow, hostOnly);
+  }
+  struct Result {
+    std::vector<int32_t> match, matchDist;   // K x n: matchIdx of the key-frame kind, assigned of the frame kind
+    std::vector<int32_t> nmatches;           // K: the reference's return values
+    int32_t stats[6] = {0, 0, 0, 0, 0, 0};   // launches, waits, copy-in bytes, jobs, jobs beyond one pass, jobs handed to the host
+  };
+  // valid1[i], valid2[k][j]: vpMapPoints[i] && !isBad().  result.match[k * n1 + i1]: the key point of keyFrames2[k] whose map point
+  // vpMatches12[i1] holds.  -> the matches of all pairs
+  int SearchByBoW(const KeyFrameHandle& kf1, const std::vector<uint8_t>& valid1, const std::vector<const KeyFrameHandle*>& keyFrames2,
+                  const std::vector<std::vector<uint8_t>>& valid2, Result& result, bool onHost = false, void* stream = nullptr) const {
+    if (valid2.size() != keyFrames2.size()) throw std::invalid_argument("SearchByBoW: one validity array per key frame");
+    const size_t K = keyFrames2.size(), n1 = (size_t)std::max<int64_t>(kf1.info().nPoints, 0);
+    std::vector<const plvs_keyframe*> raw(K + 1, nullptr);
+    std::vector<const uint8_t*> valid(K + 1, nullptr);
+    for (size_t k = 0; k < K; ++k) { raw[k] = keyFrames2[k] ? keyFrames2[k]->get() : nullptr; valid[k] = valid2[k].data(); }
+    prepare(result, K, n1);
+    if (onHost)
+      check(plvs_hip_orb_search_by_bow_kf_host(kf1.get(), valid1.data(), raw.data(), valid.data(), (int)K, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                               result.match.data(), result.matchDist.data(), result.nmatches.data(), result.stats));
+    else
+      check(plvs_hip_orb_search_by_bow_kf(kf1.get(), valid1.data(), raw.data(), valid.data(), (int)K, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                          result.match.data(), result.matchDist.data(), result.nmatches.data(), result.stats, stream));
+    return finish(result, K, n1);
+  }
+  // F: mDescriptors (n x 32), mvKeys[i].angle, mFeatVec.  result.match[k * n + iF]: the key point of keyFrames[k] whose map point goes to
+  // vvpMapPointMatches[k][iF]
+  int SearchByBoW(const std::vector<const KeyFrameHandle*>& keyFrames, const std::vector<std::vector<uint8_t>>& kfValid,
+                  const uint8_t* fDescriptors, const std::vector<float>& fAngles, const std::map<unsigned int, std::vector<unsigned int>>& fFeatVec,
+                  Result& result, bool onHost = false, void* stream = nullptr) const {
+    if (kfValid.size() != keyFrames.size()) throw std::invalid_argument("SearchByBoW: one validity array per key frame");
+    const size_t K = keyFrames.size(), n = fAngles.size();
+    const FlatFeatureVector flat(fFeatVec);
+    const plvs_bow_frame F{(int32_t)n, fDescriptors, fAngles.data(), flat.view()};
+    std::vector<const plvs_keyframe*> raw(K + 1, nullptr);
+    std::vector<const uint8_t*> valid(K + 1, nullptr);
+    for (size_t k = 0; k < K; ++k) { raw[k] = keyFrames[k] ? keyFrames[k]->get() : nullptr; valid[k] = kfValid[k].data(); }
+    prepare(result, K, n);
+    if (onHost)
+      check(plvs_hip_orb_search_by_bow_frame_kf_host(raw.data(), valid.data(), (int)K, &F, mfNNratio, mbCheckOrientation ? 1 : 0,
+                                                     result.match.data(), result.matchDist.data(), result.nmatches.data(), result.stats));
+    else
+      check(plvs_hip_orb_search_by_bow_frame_kf(raw.data(), valid.data(), (int)K, &F, mfNNratio, mbCheckOrientation ? 1 : 0, result.match.data(),
+                                                result.matchDist.data(), result.nmatches.data(), result.stats, stream));
+    return finish(result, K, n);
+  }
+
+ private:
+  static void prepare(Result& r, size_t K, size_t n) {
+    r.match.assign(K * n + 1, -1);
+    r.matchDist.assign(K * n + 1, -1);
+    r.nmatches.assign(K + 1, 0);
+  }
+  static int finish(Result& r, size_t K, size_t n) {
+    r.match.resize(K * n);
+    r.matchDist.resize(K * n);
+    r.nmatches.resize(K);
+    int total = 0;
+    for (int32_t v : r.nmatches) total += v;
+    return total;
+  }
+  float mfNNratio;
+  bool mbCheckOrientation;
+};
 
 // Frame::ComputeStereoMatches: mvuRight / mvDepth of the left keypoints (-1 = none).
 inline void ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& mvKeys,

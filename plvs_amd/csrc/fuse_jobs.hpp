@@ -90,6 +90,11 @@ int make_loop_search_line_part(const plvs_keyframe* const* kfs, const plvs_keyfr
                                const uint8_t* skip, const uint8_t* const* occupied, float th, float ratio_hamming, int32_t* match_idx,
                                int32_t* match_dist, uint8_t* reached, int32_t* nmatches, int32_t* stats, bool host_entry,
                                std::unique_ptr<Part>* out);
+// SearchByBoW over handles (orb_bow_search.hip): the refusals, then the part (null for a call without key frames; nmatches is then
+// the entry's to zero).  kf1 != null: SearchByBoW(kf1, kfs[k]) with valid1 / valid[k]; else SearchByBoW(kfs[k], F) with valid[k].
+int make_bow_search_part(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs, const uint8_t* const* valid,
+                         int n_kfs, const plvs_bow_frame* F, bool frame_kind, float nn_ratio, int check_orientation, int32_t* match,
+                         int32_t* match_dist, int32_t* nmatches, int32_t* stats, bool host_entry, std::unique_ptr<Part>* out);
 // the refusals of a handle list, in this order: a NULL handle or a handle without the side the call needs (side: 1 = points,
 // 2 = lines), for a device entry a host-only handle — all before any HIP call — and then a handle of another device
 int check_handles(const plvs_keyframe* const* kfs, const void* poses, int n_kfs, int side, bool host_entry);

@@ -31,6 +31,11 @@ struct plvs_keyframe {
     int n = 0, n_members = 0, n_levels = 0;
     size_t o_mem = 0, o_start = 0, o_desc = 0, o_sf = 0, o_sig = 0;
   } ln;
+  struct Bow {                 // mFeatVec and the angles (bow_search_pair.hpp): offsets rebased to 0, index holds the listed features alone
+    bool present = false;
+    int nnodes = 0, listed = 0, longest = 0;
+    size_t o_node = 0, o_off = 0, o_idx = 0, o_angle = 0, bytes = 0;
+  } bow;
 };
 
 namespace plvs {
@@ -50,6 +55,10 @@ int check_point_keyframe(const plvs_fuse_keyframe& kf, bool need_pose);
 int check_line_keyframe(const plvs_line_fuse_keyframe& kf, bool need_pose);
 void stage_points(const plvs_fuse_keyframe& kf, plvs_keyframe* h);
 void stage_lines(const plvs_line_fuse_keyframe& kf, plvs_keyframe* h);
+// the BoW side over the point side's n key points (orb_bow_search.hip): the refusals (-> the listed features and the longest node
+// list), and the side appended to the block — after stage_points
+int check_bow(const plvs_keyframe_bow& bow, int n, int* listed, int* longest);
+void stage_bow(const plvs_keyframe_bow& bow, int listed, int longest, plvs_keyframe* h);
 
 }  // namespace kfhandle
 }  // namespace plvs

@@ -30,6 +30,11 @@ int plvs::fusejob::check_handles(const plvs_keyframe* const* kfs, const void* po
 extern "C" {
 
 int plvs_hip_keyframe_create(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, uint32_t flags, plvs_keyframe** out) {
+  return plvs_hip_keyframe_create_bow(points, lines, nullptr, flags, out);
+}
+
+int plvs_hip_keyframe_create_bow(const plvs_fuse_keyframe* points, const plvs_line_fuse_keyframe* lines, const plvs_keyframe_bow* bow,
+                                 uint32_t flags, plvs_keyframe** out) {
   PLVS_REQUIRE(out, "null out");
   *out = nullptr;
   PLVS_REQUIRE((flags & ~PLVS_KEYFRAME_HOST_ONLY) == 0, "unknown flag");
@@ -42,10 +47,17 @@ int plvs_hip_keyframe_create(const plvs_fuse_keyframe* points, const plvs_line_f
     const int rc = plvs::kfhandle::check_line_keyframe(*lines, false);
     if (rc != PLVS_OK) return rc;
   }
+  int bow_listed = 0, bow_longest = 0;
+  if (bow) {
+    PLVS_REQUIRE(points, "a BoW side needs the point side");
+    const int rc = plvs::kfhandle::check_bow(*bow, points->view.n, &bow_listed, &bow_longest);
+    if (rc != PLVS_OK) return rc;
+  }
   std::unique_ptr<plvs_keyframe> h(new plvs_keyframe);
   h->flags = flags;
   if (points) plvs::kfhandle::stage_points(*points, h.get());
   if (lines) plvs::kfhandle::stage_lines(*lines, h.get());
+  if (bow) plvs::kfhandle::stage_bow(*bow, bow_listed, bow_longest, h.get());
   if (!(flags & PLVS_KEYFRAME_HOST_ONLY)) {
     const size_t bytes = h->host.size();
     PLVS_HIP_TRY(hipGetDevice(&h->device));
@@ -82,6 +94,15 @@ int plvs_hip_keyframe_info(const plvs_keyframe* kf, int64_t* info) {
   info[3] = (int64_t)kf->host.size();
   info[4] = kf->flags;
   info[5] = kf->device;
+  return PLVS_OK;
+}
+
+int plvs_hip_keyframe_bow_info(const plvs_keyframe* kf, int64_t* info) {
+  PLVS_REQUIRE(kf && info, "null handle / info");
+  info[0] = kf->bow.present ? kf->bow.nnodes : -1;
+  info[1] = kf->bow.listed;
+  info[2] = kf->bow.longest;
+  info[3] = kf->dev ? (int64_t)kf->bow.bytes : 0;
   return PLVS_OK;
 }
 
@@ -298,6 +319,48 @@ int plvs_hip_loop_search_by_projection_points_and_lines_kf(
   const int rc = fj::run_parts(points.get(), lines.get(), static_cast<hipStream_t>(stream), stream == nullptr, false, &launches, &waits, &copied);
   if (stats) { stats[0] = launches; stats[1] = waits; stats[2] = (int32_t)copied; }
   return rc;
+}
+
+}  // extern "C"
+
+// ---- SearchByBoW over handles (orb_bow_search.hip): one key frame against K key frames, and K key frames against one frame
+static int bow_search(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs, const uint8_t* const* valid, int n_kfs,
+                      const plvs_bow_frame* F, bool frame_kind, float nn_ratio, int check_orientation, int32_t* match, int32_t* match_dist,
+                      int32_t* nmatches, int32_t* stats, void* stream, bool host_entry) {
+  std::unique_ptr<fj::Part> part;
+  const int rc = fj::make_bow_search_part(kf1, valid1, kfs, valid, n_kfs, F, frame_kind, nn_ratio, check_orientation, match, match_dist,
+                                          nmatches, stats, host_entry, &part);
+  return rc != PLVS_OK ? rc : fj::run_single(part.get(), stats, 6, stream, host_entry);
+}
+
+extern "C" {
+
+int plvs_hip_orb_search_by_bow_kf(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs2,
+                                  const uint8_t* const* valid2, int n_kfs2, float nn_ratio, int check_orientation, int32_t* match_idx,
+                                  int32_t* match_dist, int32_t* nmatches, int32_t* stats, void* stream) {
+  return bow_search(kf1, valid1, kfs2, valid2, n_kfs2, nullptr, false, nn_ratio, check_orientation, match_idx, match_dist, nmatches, stats,
+                    stream, false);
+}
+
+int plvs_hip_orb_search_by_bow_frame_kf(const plvs_keyframe* const* kfs, const uint8_t* const* kf_valid, int n_kfs, const plvs_bow_frame* F,
+                                        float nn_ratio, int check_orientation, int32_t* assigned, int32_t* match_dist, int32_t* nmatches,
+                                        int32_t* stats, void* stream) {
+  return bow_search(nullptr, nullptr, kfs, kf_valid, n_kfs, F, true, nn_ratio, check_orientation, assigned, match_dist, nmatches, stats, stream,
+                    false);
+}
+
+int plvs_hip_orb_search_by_bow_kf_host(const plvs_keyframe* kf1, const uint8_t* valid1, const plvs_keyframe* const* kfs2,
+                                       const uint8_t* const* valid2, int n_kfs2, float nn_ratio, int check_orientation, int32_t* match_idx,
+                                       int32_t* match_dist, int32_t* nmatches, int32_t* stats) {
+  return bow_search(kf1, valid1, kfs2, valid2, n_kfs2, nullptr, false, nn_ratio, check_orientation, match_idx, match_dist, nmatches, stats,
+                    nullptr, true);
+}
+
+int plvs_hip_orb_search_by_bow_frame_kf_host(const plvs_keyframe* const* kfs, const uint8_t* const* kf_valid, int n_kfs,
+                                             const plvs_bow_frame* F, float nn_ratio, int check_orientation, int32_t* assigned,
+                                             int32_t* match_dist, int32_t* nmatches, int32_t* stats) {
+  return bow_search(nullptr, nullptr, kfs, kf_valid, n_kfs, F, true, nn_ratio, check_orientation, assigned, match_dist, nmatches, stats, nullptr,
+                    true);
 }
 
 }  // extern "C"

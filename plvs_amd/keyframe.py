@@ -8,7 +8,10 @@ A handle holds what the constructor fixes; the pose travels with each call.  Out
 LineMatcher.FuseSearch / FuseSearchPointsAndLines, with one more entry in stats: the bytes of the call's copy in.
 
 The Sim3 Fuse searches of LoopClosing::SearchAndFuse (loop_fuse_search_kf, line_loop_fuse_search_kf,
-loop_fuse_search_points_and_lines_kf) take the same handles and a Sim3Pose per key frame: the caller's own decomposition of Scw."""
+loop_fuse_search_points_and_lines_kf) take the same handles and a Sim3Pose per key frame: the caller's own decomposition of Scw.
+
+ORBmatcher::SearchByBoW over handles made with a KeyFrameBow (search_by_bow_kf: one key frame against K key frames, loop detection's
+first stage; search_by_bow_frame_kf: K key frames against one BowFrame, relocalisation), each one call."""
 import ctypes
 from dataclasses import dataclass
 
@@ -16,11 +19,12 @@ import numpy as np
 
 from . import _lib
 from .linematcher import FuseLines, LineFuseKeyFrame, _fuse_outputs  # noqa: F401
-from .orbmatcher import FuseKeyFrame, FusePoints  # noqa: F401
+from .orbmatcher import FeatureVector, FuseKeyFrame, FusePoints, _FeatVecC  # noqa: F401
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 HOST_ONLY = 1
 INFO = ("n_points", "n_lines", "device_bytes", "host_bytes", "flags", "device")
+BOW_INFO = ("nodes", "listed", "longest", "device_bytes")
 
 
 class _PoseC(ctypes.Structure):
@@ -64,11 +68,26 @@ def pose_of(points=None, lines=None):
     return KeyFramePose(None if points is None else points.q_cw, None if lines is None else lines.Rcw, src.tcw, src.Ow)
 
 
-class ResidentKeyFrame:
-    """plvs_hip_keyframe_create: a deep copy of `points` and / or `lines` (their pose fields are not read), with both grids, on the
-    host and — unless host_only — in one device allocation."""
+class _KeyFrameBowC(ctypes.Structure):
+    _fields_ = [("vec", _FeatVecC), ("angle", _vp)]
 
-    def __init__(self, points=None, lines=None, host_only=False):
+
+@dataclass
+class KeyFrameBow:
+    """plvs_keyframe_bow: what KeyFrame::ComputeBoW fixes of a key frame."""
+    vec: FeatureVector    # pKF->mFeatVec
+    angle: np.ndarray     # pKF->mvKeysUn[i].angle, degrees; None: a NULL angle (refused)
+
+    def as_c(self):
+        self._angle = None if self.angle is None else np.ascontiguousarray(self.angle, np.float32)
+        return _KeyFrameBowC(self.vec.as_c(), _lib.np_ptr(self._angle))
+
+
+class ResidentKeyFrame:
+    """plvs_hip_keyframe_create / plvs_hip_keyframe_create_bow: a deep copy of `points` and / or `lines` (their pose fields are not
+    read), with both grids, and of `bow` (a KeyFrameBow; needs points), on the host and — unless host_only — in one device allocation."""
+
+    def __init__(self, points=None, lines=None, host_only=False, bow=None):
         self._h = _vp()
         pc = None if points is None else points.as_c()
         lc = None if lines is None else lines.as_c()
@@ -76,10 +95,16 @@ class ResidentKeyFrame:
             pc.q_cw = pc.tcw = pc.Ow = None      # the pose is the call's: create does not read these
         if lc is not None:
             lc.Rcw = lc.tcw = lc.Ow = None
-        f = _lib.lib.plvs_hip_keyframe_create
-        f.argtypes = [_vp, _vp, ctypes.c_uint32, _vp]
-        _lib.check(f(None if pc is None else ctypes.byref(pc), None if lc is None else ctypes.byref(lc), HOST_ONLY if host_only else 0,
-                     ctypes.byref(self._h)))
+        args = [None if pc is None else ctypes.byref(pc), None if lc is None else ctypes.byref(lc)]
+        if bow is None:
+            f = _lib.lib.plvs_hip_keyframe_create
+            f.argtypes = [_vp, _vp, ctypes.c_uint32, _vp]
+        else:
+            bc = bow.as_c()
+            args.append(ctypes.byref(bc))
+            f = _lib.lib.plvs_hip_keyframe_create_bow
+            f.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp]
+        _lib.check(f(*args, HOST_ONLY if host_only else 0, ctypes.byref(self._h)))
 
     @property
     def handle(self):
@@ -93,6 +118,13 @@ class ResidentKeyFrame:
         f.argtypes = [_vp, _vp]
         _lib.check(f(self.handle, _lib.np_ptr(out)))
         return dict(zip(INFO, out.tolist()))
+
+    def bow_info(self):
+        out = np.zeros(4, np.int64)
+        f = _lib.lib.plvs_hip_keyframe_bow_info
+        f.argtypes = [_vp, _vp]
+        _lib.check(f(self.handle, _lib.np_ptr(out)))
+        return dict(zip(BOW_INFO, out.tolist()))
 
     def close(self):
         if self._h:
@@ -293,3 +325,68 @@ def loop_search_by_projection_points_and_lines_kf(key_frames, sim3_poses, points
                  locc, th_lines, ratio_hamming_lines, *[_lib.np_ptr(a) for a in l_out], _lib.np_ptr(stats), stream))
     as_dict = lambda o: dict(match_idx=o[0], match_dist=o[1], reached=o[2], nmatches=o[3], stats=o[4])
     return (None if points is None else as_dict(p_out)), (None if lines is None else as_dict(l_out)), stats
+
+
+# ---- SearchByBoW over resident key frames: loop detection's first stage, relocalisation
+class _BowFrameC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("desc", _vp), ("angle", _vp), ("vec", _FeatVecC)]
+
+
+@dataclass
+class BowFrame:
+    """plvs_bow_frame: what SearchByBoW(pKF, F) reads of the frame."""
+    desc: np.ndarray      # F.mDescriptors, n x 32
+    angle: np.ndarray     # F.mvKeys[i].angle, degrees
+    vec: FeatureVector    # F.mFeatVec
+
+    def as_c(self):
+        self._d = np.ascontiguousarray(self.desc, np.uint8).reshape(-1, 32)
+        self._a = np.ascontiguousarray(self.angle, np.float32)
+        return _BowFrameC(self._d.shape[0], _lib.np_ptr(self._d), _lib.np_ptr(self._a), self.vec.as_c())
+
+
+def _valid_list(valid, K):
+    assert len(valid) == K
+    keep = [None if v is None else np.ascontiguousarray(v, np.uint8) for v in valid]
+    return (_vp * max(K, 1))(*[None if v is None else v.ctypes.data for v in keep]), keep
+
+
+def _bow_outputs(K, n, outputs):
+    """outputs: None, or (match, match_dist, nmatches, stats) to write into (the refusal tests pass their own)."""
+    if outputs is not None:
+        return outputs
+    return np.full((K, n), -2, np.int32), np.full((K, n), -2, np.int32), np.full(K, -7, np.int32), np.full(6, -1, np.int32)
+
+
+def search_by_bow_kf(kf1, valid1, key_frames2, valid2, nn_ratio=0.9, check_orientation=True, host=False, stream=None, n1=None, outputs=None):
+    """ORBmatcher::SearchByBoW(pKF1, pKF2[k], vpMatches12[k]) for every k in one call (plvs_hip_orb_search_by_bow_kf / _kf_host).
+    valid1 [n1], valid2[k] [n_k]: vpMapPoints[i] && !isBad().  -> dict(match_idx [K,n1], match_dist [K,n1], nmatches [K], stats [6])."""
+    K = len(key_frames2)
+    hs = (_vp * max(K, 1))(*[None if kf is None else kf.handle for kf in key_frames2])
+    vl, keep = _valid_list(valid2, K)
+    v1 = None if valid1 is None else np.ascontiguousarray(valid1, np.uint8)
+    if n1 is None:
+        n1 = kf1.info()["n_points"] if kf1 is not None else 0
+    match_idx, match_dist, nmatches, stats = _bow_outputs(K, max(n1, 0), outputs)
+    f = getattr(_lib.lib, "plvs_hip_orb_search_by_bow_kf" + ("_host" if host else ""))
+    f.argtypes = [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp] + ([] if host else [_vp])
+    args = [None if kf1 is None else kf1.handle, _lib.np_ptr(v1), hs if K else None, vl if K else None, K, nn_ratio, int(check_orientation),
+            _lib.np_ptr(match_idx), _lib.np_ptr(match_dist), _lib.np_ptr(nmatches), _lib.np_ptr(stats)]
+    _lib.check(f(*(args if host else args + [stream])))
+    return dict(match_idx=match_idx, match_dist=match_dist, nmatches=nmatches, stats=stats)
+
+
+def search_by_bow_frame_kf(key_frames, kf_valid, frame, nn_ratio=0.75, check_orientation=True, host=False, stream=None, outputs=None):
+    """ORBmatcher::SearchByBoW(pKF[k], F, vvpMapPointMatches[k]) for every k in one call (plvs_hip_orb_search_by_bow_frame_kf / _kf_host).
+    -> dict(assigned [K,F.n]: the key point of key frame k whose map point goes to the frame's key point, match_dist, nmatches [K], stats [6])."""
+    K = len(key_frames)
+    hs = (_vp * max(K, 1))(*[None if kf is None else kf.handle for kf in key_frames])
+    vl, keep = _valid_list(kf_valid, K)
+    fc = None if frame is None else frame.as_c()
+    assigned, match_dist, nmatches, stats = _bow_outputs(K, 0 if fc is None else fc.n, outputs)
+    f = getattr(_lib.lib, "plvs_hip_orb_search_by_bow_frame_kf" + ("_host" if host else ""))
+    f.argtypes = [_vp, _vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp] + ([] if host else [_vp])
+    args = [hs if K else None, vl if K else None, K, None if fc is None else ctypes.byref(fc), nn_ratio, int(check_orientation),
+            _lib.np_ptr(assigned), _lib.np_ptr(match_dist), _lib.np_ptr(nmatches), _lib.np_ptr(stats)]
+    _lib.check(f(*(args if host else args + [stream])))
+    return dict(assigned=assigned, match_dist=match_dist, nmatches=nmatches, stats=stats)
